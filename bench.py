@@ -18,6 +18,10 @@ redundantly, and the only collective is the all_gather of 100 (score, index) pai
                                         # multi-device handle (abo_mgpu_*: worker thread per device, RCCL all-gather)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
          --master-port 29500 bench.py --gpus 8 --steps 5 --warmup 2
+
+A plain run sets up, warms up, times --steps steps and prints the line.  --full adds what takes runs of its own: the CPU
+baseline, the `variants` (the reference's call shape, the other contraction engine) and, on the default C3 line, the
+`secondary` configurations.  --dump-outputs DIR writes what the timed path returned in its last step as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -477,6 +481,30 @@ def quick_c1_shape(abo, synth, torch, dev, local_rank, k_top=100, steps=200, war
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float64 (indices included: exact below 2^53)"""
+    if not dirname:
+        return
+    out = {k: np.ascontiguousarray(v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v), dtype=np.float64)
+           for k, v in arrays.items()}
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py --dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES} byte limit")
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(dirname, f"{k}.npy"), a)
+
+
+def fitted_alpha(abo, handle, n):
+    """alpha = K^-1 y of a fitted handle, read back to the host (abo_get_factor without L / L^-1)"""
+    a = np.empty(n)
+    abo._lib.check(abo._lib.lib().abo_get_factor(handle, None, a.ctypes.data, None))
+    return a
+
+
 def exchange_record(args, use_dist, local_rank):
     """What the collective layer itself saw: backend, world size from the process group, and the device every rank
     runs on — gathered through the group (outside the timed region), so the first multi-GPU line can be checked for N ranks on N
@@ -500,7 +528,7 @@ def exchange_record(args, use_dist, local_rank):
     return rec
 
 
-def run_c5(args, cfg, world, rank, local_rank, dev, use_dist=False, steps=None, warmup=None):
+def run_c5(args, cfg, world, rank, local_rank, dev, use_dist=False, steps=None, warmup=None, dump_dir=None):
     """BASELINE config 5.  A step = greedy q-EI over the resident grid (q = 8 picks, each: EI + arg-max,
     fantasy bordered append, O(N·M) down-date), roll the grid posterior back, append the real (noisy)
     observation of the first pick to the parent model, down-date.  The full refresh (refit + grid
@@ -613,6 +641,8 @@ def run_c5(args, cfg, world, rank, local_rank, dev, use_dist=False, steps=None, 
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     ms = elapsed * 1e3 / n_steps
+    if rank == 0:
+        dump_outputs(dump_dir, {"qei_points": pts, "qei_indices": idxs, "qei_ei": vals})
     xchg = exchange_record(args, use_dist, local_rank)
     # The same step when NOTHING carries over from the step before (ABO_QEI_NO_REUSE: every batch builds its own block — one pass
     # over K_ZX per step): three untimed-for-`value` steps.  `value` is what the loop above measured — a BO loop, where the blocks and
@@ -810,6 +840,7 @@ def run_single_process(args):
             per_dev.append([t["fit_total_ms"] + t["acq_total_ms"] for t in st])
             phases.append(st[0])
     ms = (time.perf_counter() - t_all) * 1e3 / args.steps
+    dump_outputs(args.dump_outputs, {"top_scores": tv, "top_indices": ti, "alpha": fitted_alpha(abo, model.shard(0), N)})
     med = {k: float(np.median([p[k] for p in phases])) for k in phases[0]}
     exchange, why = model.exchange(), model.exchange_note()
     out = {
@@ -885,6 +916,7 @@ def run_single_process_c5(args):
         if step >= args.warmup:
             step_ms.append((time.perf_counter() - t0) * 1e3)
     ms = (time.perf_counter() - t_all) * 1e3 / args.steps
+    dump_outputs(args.dump_outputs, {"qei_points": pts, "qei_indices": picks[0], "qei_ei": picks[1]})
     exchange, why = model.exchange(), model.exchange_note()
     out = {
         "metric": "GP-update+acq-eval ms per BO step at N train pts x M candidates",
@@ -916,8 +948,13 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the C2 and C5 entries of the default C3 line (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also time what the headline does not need: the CPU baseline, the variants (host arrays, scores to host, the "
+                         "other contraction engine) and, on the default C3 line, the secondary configurations")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the C2 and C5 entries of the default C3 line (profiling runs)")
     ap.add_argument("--cpu-sample-m", type=int, default=21846,
                     help="candidates PER REPETITION of the CPU-baseline sample (default 3 x 21846 = 65538 in all; BASELINE.md §4 "
                          "allows timing 65536 candidates and scaling linearly in M)")
@@ -978,7 +1015,7 @@ def main():
 
     cfg = CONFIGS[args.config]
     if args.config == "c5":
-        out = run_c5(args, cfg, world, rank, local_rank, dev, use_dist)
+        out = run_c5(args, cfg, world, rank, local_rank, dev, use_dist, dump_dir=args.dump_outputs)
         if rank == 0:
             print(json.dumps(out))
         if use_dist:
@@ -1034,13 +1071,15 @@ def main():
     if use_dist:
         elapsed = reduce_max(elapsed)
     ms_per_step = elapsed * 1e3 / args.steps
+    if rank == 0:
+        dump_outputs(args.dump_outputs, {"top_scores": top[0], "top_indices": top[1], "alpha": fitted_alpha(abo, model._require(), N)})
     xchg = exchange_record(args, use_dist, local_rank)
 
     # SURVEY 8(d) asks for the metric in two shapes.  `value` above is "arg-max / top-100 only"; the reference's own
     # API shape (acq_utils.jl:50) also hands the M scores back to the host: timed here on two extra steps
     # (untimed for `value`), scores landing in a host array through the C-ABI's D2H copy.
     variants = None
-    if world == 1:
+    if world == 1 and args.full:
         # the caller's arrays live across BO steps (one untimed step first: the first pass over 8 MiB of fresh pageable memory and
         # the library's score buffer are one-time costs — round 3 timed them into two steps and read +14 ms for an 8 MiB copy)
         host_scores, htv, hti = np.empty(M_per), np.empty(K_TOP), np.empty(K_TOP, dtype=np.int64)
@@ -1125,7 +1164,7 @@ def main():
             out["variants"] = variants
         # the legs below are auxiliary: a failure in one of them (a host without SciPy's LAPACK threads, a device too full for the C5
         # grid, ...) is reported in its place and must not take the measured headline line with it
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(cfg, args.cpu_sample_m, args.cpu_reps)
                 if out["cpu_baseline"].get("host_blas", {}).get("under_threaded"):
@@ -1137,7 +1176,7 @@ def main():
             except Exception as e:                      # noqa: BLE001 - reported, not swallowed
                 out["cpu_baseline"] = {"error": f"{type(e).__name__}: {e}"}
                 print(f"bench: cpu_baseline leg failed: {e!r}", file=sys.stderr)
-        if world == 1 and args.config == "c3" and not args.no_secondary:
+        if world == 1 and args.config == "c3" and args.full and not args.no_secondary:
             # the other single-GPU configurations of BASELINE.json, timed by the same run: C2 (small N) and C5
             # (incremental update + greedy q-EI on a resident grid; its own roofline is the HBM-streaming down-date)
             del model, Zd

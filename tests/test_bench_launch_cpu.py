@@ -48,3 +48,15 @@ def test_plain_multi_gpu_argv_reaches_the_multi_device_branch_not_sys_exit():
     assert r.returncode != 0
     assert "--share-device rehearses 2 shards on GPU 0" in r.stderr, r.stderr[-800:]
     assert "torch.distributed.run" not in r.stderr
+
+
+def test_dump_outputs_writes_float64_arrays_within_the_limit(tmp_path):
+    """--dump-outputs: one DIR/<name>.npy per array, float64 (indices included), and nothing past the 64 MB limit"""
+    import numpy as np
+    bench.dump_outputs(str(tmp_path / "d"), {"top_scores": np.array([0.5, 0.25]), "top_indices": np.array([7, 3], dtype=np.int64)})
+    s, i = np.load(tmp_path / "d" / "top_scores.npy"), np.load(tmp_path / "d" / "top_indices.npy")
+    assert s.dtype == np.float64 and i.dtype == np.float64 and s.tolist() == [0.5, 0.25] and i.tolist() == [7.0, 3.0]
+    bench.dump_outputs(None, {"never": np.zeros(1)})                            # no DIR: nothing written, no error
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": np.zeros(bench.DUMP_LIMIT_BYTES // 8 + 1)})
+    assert not (tmp_path / "big").exists()
