@@ -21,11 +21,15 @@ EXPORTS = ["abo_create", "abo_set_contraction", "abo_create_grad", "abo_predict_
            "abo_mgpu_cand_qei", "abo_refine", "abo_optimize_acquisition", "abo_mgpu_optimize_acquisition", "abo_fit_acq", "abo_mgpu_create_grad", "abo_mgpu_append_grad", "abo_mgpu_cand_get", "abo_acq_terms", "abo_acq_lhs", "abo_refine_terms",
            "abo_optimize_acquisition_terms", "abo_mgpu_optimize_acquisition_terms",
            "abo_set_qei_block", "abo_cand_qei", "abo_cand_qei_begin", "abo_cand_qei_top", "abo_cand_qei_block", "abo_cand_qei_pick",
-           "abo_cand_qei_end", "abo_cand_qei_has", "abo_cand_qei_stats", "abo_mgpu_cand_qei_stats", "abo_cand_qei_eligible", "abo_fill_distance"]
+           "abo_cand_qei_end", "abo_cand_qei_has", "abo_cand_qei_stats", "abo_mgpu_cand_qei_stats", "abo_cand_qei_eligible", "abo_fill_distance",
+           "abo_update", "abo_mgpu_update"]
 TEST_EXPORTS = ["abo_test_gemm_nt", "abo_test_kappa", "abo_test_oz_plan", "abo_test_oz_contract", "abo_test_acq_grad",
                 "abo_test_acq_grad_terms"]
 ABI_VERSION = 7
 CONTRACT_AUTO, CONTRACT_FP64, CONTRACT_INT8 = 0, 1, 2
+# what abo_update / abo_mgpu_update ran (include/abo_hip.h)
+UPDATE_SHARED, UPDATE_APPENDED, UPDATE_REFIT = 0, 1, 2
+UPDATE_PATHS = {UPDATE_SHARED: "shared", UPDATE_APPENDED: "appended", UPDATE_REFIT: "refit"}
 
 
 class AboParams(C.Structure):
@@ -197,6 +201,8 @@ def lib():
     L.abo_optimize_acquisition_terms.argtypes = [vp, tp, i32, vp, vp, i32, i64, i32, C.c_uint64, C.POINTER(AboRefineOpts),
                                                  vp, C.POINTER(f64), vp, vp, vp, vp]
     L.abo_mgpu_optimize_acquisition_terms.argtypes = L.abo_optimize_acquisition_terms.argtypes
+    L.abo_update.argtypes = [vp, C.POINTER(AboParams), vp, vp, i64, i32, vp, i32, C.POINTER(i64), C.POINTER(i32), C.POINTER(vp)]
+    L.abo_mgpu_update.argtypes = [vp, C.POINTER(AboParams), vp, vp, i64, i32, vp, C.POINTER(i64), C.POINTER(i32), C.POINTER(vp)]
     L.abo_fit_acq.argtypes = [vp, vp, i64, i32, vp, i32, C.POINTER(i64), vp, i64, i32, i32, f64, f64, i64, vp, i32, vp, vp, i32]
     for name in EXPORTS + (TEST_EXPORTS if hooks else []):
         getattr(L, name).restype = i32

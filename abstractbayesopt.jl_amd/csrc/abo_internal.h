@@ -65,6 +65,29 @@ const double* cand_points(const abo_cand* c);      // device, [M][d]
 const double* cand_mu(const abo_cand* c);          // device, [M]
 int64_t cand_size(const abo_cand* c);
 
+// ---- abo_update / abo_mgpu_update (update.hip): what they read of a handle, and the append / pool / wait machinery of api.hip
+struct GpState {
+    bool fitted = false;
+    int device = 0, d = 0, p_out = 1;
+    int64_t npts = 0, rows = 0;          // training points, factor rows (p_out per point)
+    int64_t cap_rows = 0;                // capacity of the factor storage, rows
+    int64_t max_live = 0;                // rows of the largest live view on that storage (> rows: another view appended past this one)
+    double noise_used = 0.0;             // the noise the factor was built with (> noise_var: the jitter ladder ran)
+    const void* storage = nullptr;       // identity of the factor storage
+    const double* Xraw = nullptr;        // device, [npts][d] as the caller handed them over
+    const double* ybuf = nullptr;        // device, [rows] raw targets, point-major (i·p + q)
+    const double* mean_vec = nullptr;    // host, p_out prior means
+};
+bool gp_state(abo_gp* g, GpState* out);   // false: not fitted (device, p_out and mean_vec are filled in all the same)
+// the bordered append of one observation (p_out values in yv) to view g, into the fresh handle n (append_impl / append_grad_impl:
+// a full refit with doubled capacity when the storage is full or claimed by a larger view)
+int32_t gp_append_into(abo_gp* g, abo_gp* n, const double* x, const double* yv, int64_t* info);
+const void* gp_storage(const abo_gp* g);
+char* gp_pin(abo_gp* g, size_t* bytes);   // the handle's page-locked staging block past the fit scalars (null if it has none)
+hipError_t stream_wait(hipStream_t s);     // the polled wait every call ends with
+hipError_t scratch_alloc(int dev, size_t bytes, void** p, size_t* cap);   // the device-memory pool
+void scratch_free(int dev, void* p, size_t cap);
+
 // Process teardown.  `exiting()` turns true when the process has started to exit (an atexit hook registered behind the HIP
 // runtime's own, so it runs BEFORE the runtime tears down, and the library's static destructor): from then on no entry point
 // touches the device — a finaliser that runs late (a Julia / Python handle destroyed from an exit handler, a static

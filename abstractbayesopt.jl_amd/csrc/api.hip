@@ -3067,6 +3067,36 @@ int64_t abo::cand_size(const abo_cand* c) { return c->M; }
 int32_t abo::set_error(int32_t code, const char* text) { return fail(code, "%s", text); }
 const char* abo::last_error_text() { return g_err; }
 
+// internal accessors for abo_update (update.hip)
+bool abo::gp_state(abo_gp* g, GpState* o) {
+    *o = GpState{};
+    o->device = g->prm.device;
+    o->p_out = g->p_out;
+    o->mean_vec = g->mean_vec;
+    o->fitted = g->fitted && g->st != nullptr;
+    if (!o->fitted) return false;
+    Storage* st = g->st;
+    o->d = g->d;
+    o->npts = g->npts; o->rows = g->N; o->cap_rows = st->cap; o->max_live = st->max_live();
+    o->noise_used = st->noise_used;
+    o->storage = st;
+    o->Xraw = st->Xraw.as<double>(); o->ybuf = st->ybuf.as<double>();
+    return true;
+}
+int32_t abo::gp_append_into(abo_gp* g, abo_gp* n, const double* x, const double* yv, int64_t* info) {
+    n->oz_engine = g->oz_engine; n->oz_nmod = g->oz_nmod;
+    return g->p_out > 1 ? append_grad_impl(g, n, x, yv, info) : append_impl(g, n, x, yv[0], info);
+}
+const void* abo::gp_storage(const abo_gp* g) { return g->fitted ? g->st : nullptr; }
+char* abo::gp_pin(abo_gp* g, size_t* bytes) {
+    if (!g->ctx || !g->ctx->pin) { *bytes = 0; return nullptr; }
+    *bytes = PIN_BYTES - PIN_OUT;                    // [0, PIN_OUT) holds a fit's scalars
+    return g->ctx->pin + PIN_OUT;
+}
+hipError_t abo::stream_wait(hipStream_t s) { return wait_stream(s); }
+hipError_t abo::scratch_alloc(int dev, size_t bytes, void** p, size_t* cap) { return pool_alloc(dev, bytes, p, cap); }
+void abo::scratch_free(int dev, void* p, size_t cap) { pool_free(dev, p, cap); }
+
 extern "C" {
 
 int32_t abo_cand_save(abo_gp* g, abo_cand* c) {

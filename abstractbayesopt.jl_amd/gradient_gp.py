@@ -36,9 +36,9 @@ class HipGradientGP(HipStandardGP):
     """GradientGP(kernel, p, noise_var; mean=gradConstMean(zeros(p))) (GradientGP.jl:617-639)."""
 
     def __init__(self, kernel: Kernel, p: int, noise_var: float, mean=None, device: int | None = None, jitter: float = 0.0,
-                 chunk: int = 0, n_max: int = 0, contraction: str | None = None):
+                 chunk: int = 0, n_max: int = 0, contraction: str | None = None, incremental_update: bool = False):
         super().__init__(kernel, noise_var, mean=None, device=device, jitter=jitter, chunk=chunk, n_max=n_max,
-                         contraction=contraction)
+                         contraction=contraction, incremental_update=incremental_update)
         self.p = int(p)
         self.mean = gradConstMean(np.zeros(self.p)) if mean is None else mean
         if len(self.mean.c) != self.p:
@@ -80,15 +80,23 @@ def update(model: HipGradientGP, xs, ys) -> HipGradientGP:
     hp = C.c_void_p()
     prm = model._params()
     prm.mean_c = float(model.mean.c[0])
-    mean = np.ascontiguousarray(model.mean.c)
+    mean = np.ascontiguousarray(model.mean.c, dtype=np.float64)
+    info = C.c_int64(0)
+    from .surrogate import _with_path, parse_contraction
+    if getattr(model, "incremental_update", False) and model._h is not None:
+        path = C.c_int32(_lib.UPDATE_REFIT)
+        _lib.check(L.abo_update(model._h.ptr, C.byref(prm), mean.ctypes.data, xp, n, d, y.ctypes.data, HOST, C.byref(info),
+                                C.byref(path), C.byref(hp)), info.value)
+        h = _Handle(hp.value)
+        if getattr(model, "contraction", None) is not None:
+            _lib.check(L.abo_set_contraction(h.ptr, *parse_contraction(model.contraction)))
+        return _with_path(model._clone(h), path.value)
     _lib.check(L.abo_create_grad(C.byref(prm), model.p, mean.ctypes.data, C.byref(hp)))
     h = _Handle(hp.value)
     if getattr(model, "contraction", None) is not None:
-        from .surrogate import parse_contraction
         _lib.check(L.abo_set_contraction(h.ptr, *parse_contraction(model.contraction)))
-    info = C.c_int64(0)
     _lib.check(L.abo_fit(h.ptr, xp, n, d, y.ctypes.data, HOST, C.byref(info)), info.value)
-    return model._clone(h)
+    return _with_path(model._clone(h), _lib.UPDATE_REFIT)
 
 
 def _grad_predict(model: HipGradientGP, x, want_mu=True, want_var=True):
@@ -174,18 +182,21 @@ def rescale_model(model: HipGradientGP, sigma):
     if hasattr(model, "devices"):                        # a sharded group keeps its device list
         from .multigpu import HipShardedGradientGP
         return HipShardedGradientGP(k, model.p, model.noise_var / s1 ** 2, mean=gradConstMean(model.mean.c / s1),
-                                    devices=model.devices, jitter=model.jitter, chunk=model.chunk, n_max=model.n_max)
+                                    devices=model.devices, jitter=model.jitter, chunk=model.chunk, n_max=model.n_max,
+                                    incremental_update=getattr(model, "incremental_update", False))
     return HipGradientGP(k, model.p, model.noise_var / s1 ** 2, mean=gradConstMean(model.mean.c / s1), device=model.device,
-                         jitter=model.jitter, chunk=model.chunk, n_max=model.n_max, contraction=model.contraction)
+                         jitter=model.jitter, chunk=model.chunk, n_max=model.n_max, contraction=model.contraction,
+                         incremental_update=getattr(model, "incremental_update", False))
 
 
 def _update_model_parameters(model: HipGradientGP, kernel: Kernel):
     if hasattr(model, "devices"):
         from .multigpu import HipShardedGradientGP
         return HipShardedGradientGP(kernel, model.p, model.noise_var, mean=model.mean, devices=model.devices, jitter=model.jitter,
-                                    chunk=model.chunk, n_max=model.n_max)
+                                    chunk=model.chunk, n_max=model.n_max, incremental_update=getattr(model, "incremental_update", False))
     return HipGradientGP(kernel, model.p, model.noise_var, mean=model.mean, device=model.device, jitter=model.jitter,
-                         chunk=model.chunk, n_max=model.n_max, contraction=model.contraction)
+                         chunk=model.chunk, n_max=model.n_max, contraction=model.contraction,
+                         incremental_update=getattr(model, "incremental_update", False))
 
 
 def nlml(model: HipGradientGP, params, xs, ys) -> float:

@@ -51,8 +51,10 @@ def _host(a, dtype=np.float64):
 class HipShardedGP(HipStandardGP):
     """StandardGP(kernel, noise_var; mean) replicated on `devices` (a device may be listed twice: two shards on it)."""
 
-    def __init__(self, kernel, noise_var, mean=None, devices=(0,), jitter: float = 0.0, chunk: int = 0, n_max: int = 0):
-        super().__init__(kernel, noise_var, mean=mean, device=int(devices[0]), jitter=jitter, chunk=chunk, n_max=n_max)
+    def __init__(self, kernel, noise_var, mean=None, devices=(0,), jitter: float = 0.0, chunk: int = 0, n_max: int = 0,
+                 incremental_update: bool = False):
+        super().__init__(kernel, noise_var, mean=mean, device=int(devices[0]), jitter=jitter, chunk=chunk, n_max=n_max,
+                         incremental_update=incremental_update)
         self.devices = [int(v) for v in devices]
         self._g = None
 
@@ -102,9 +104,11 @@ class HipShardedGradientGP(HipShardedGP):
     the (d+1)N-row system is fitted on every device, candidates are sharded, acquisitions address the function output;
     `append` takes one observation [f(x), ∇f(x)…] and greedy q-EI conditions on the posterior mean of all p outputs."""
 
-    def __init__(self, kernel, p: int, noise_var, mean=None, devices=(0,), jitter: float = 0.0, chunk: int = 0, n_max: int = 0):
+    def __init__(self, kernel, p: int, noise_var, mean=None, devices=(0,), jitter: float = 0.0, chunk: int = 0, n_max: int = 0,
+                 incremental_update: bool = False):
         from .gradient_gp import gradConstMean
-        super().__init__(kernel, noise_var, mean=None, devices=devices, jitter=jitter, chunk=chunk, n_max=n_max)
+        super().__init__(kernel, noise_var, mean=None, devices=devices, jitter=jitter, chunk=chunk, n_max=n_max,
+                         incremental_update=incremental_update)
         self.p = int(p)
         self.mean = gradConstMean(np.zeros(self.p)) if mean is None else mean
         if len(self.mean.c) != self.p:
@@ -143,16 +147,23 @@ def update(model: HipShardedGP, xs, ys) -> HipShardedGP:
     prm = model._params()
     devs = (C.c_int32 * len(model.devices))(*model.devices)
     gp = C.c_void_p()
+    info = C.c_int64(0)
+    from .surrogate import _with_path
+    if getattr(model, "incremental_update", False) and model._g is not None:
+        path = C.c_int32(_lib.UPDATE_REFIT)
+        mean = np.ascontiguousarray(model.mean.c, dtype=np.float64) if grad else None
+        _lib.check(L.abo_mgpu_update(model._g.ptr, C.byref(prm), mean.ctypes.data if grad else None, xp, n, d, ya.ctypes.data,
+                                     C.byref(info), C.byref(path), C.byref(gp)), info.value)
+        return _with_path(model._clone_group(_GroupHandle(gp.value)), path.value)
     if grad:
         mean = np.ascontiguousarray(model.mean.c)
         _lib.check(L.abo_mgpu_create_grad(C.byref(prm), model.p, mean.ctypes.data, len(model.devices), devs, C.byref(gp)))
     else:
         _lib.check(L.abo_mgpu_create(C.byref(prm), len(model.devices), devs, C.byref(gp)))
     h = _GroupHandle(gp.value)
-    info = C.c_int64(0)
     st = L.abo_mgpu_fit(h.ptr, xp, n, d, ya.ctypes.data, C.byref(info))
     _lib.check(st, info.value)
-    return model._clone_group(h)
+    return _with_path(model._clone_group(h), _lib.UPDATE_REFIT)
 
 
 def copy(model: HipShardedGP) -> HipShardedGP:

@@ -76,7 +76,7 @@ class HipStandardGP(AbstractSurrogate):
     """StandardGP(kernel, noise_var; mean=nothing) (src/surrogates/StandardGP.jl:41-64)."""
 
     def __init__(self, kernel: Kernel, noise_var: float, mean=None, device: int | None = None, jitter: float = 0.0,
-                 chunk: int = 0, n_max: int = 0, contraction: str | None = None):
+                 chunk: int = 0, n_max: int = 0, contraction: str | None = None, incremental_update: bool = False):
         if mean is None:
             mean = ZeroMean()
         inner, scale, ell = extract_scale_and_lengthscale(kernel)
@@ -90,6 +90,10 @@ class HipStandardGP(AbstractSurrogate):
         # engine of the variance contraction: None = the library default (auto), "fp64", "int8" or "int8:<moduli>"
         self.contraction = contraction
         parse_contraction(contraction)
+        # update(model, xs, ys) on a fitted model: bordered appends when (xs, ys) extends its data (abo_update), else the refit;
+        # off = always the refit, the reference's arithmetic
+        self.incremental_update = bool(incremental_update)
+        self.update_path = None   # what the update that made this model ran: "shared" / "appended" / "refit"
         if device is None:
             device = _current_device()
         self.device = int(device)
@@ -114,6 +118,8 @@ class HipStandardGP(AbstractSurrogate):
         m.kernel, m.noise_var, m.mean, m.jitter, m.chunk, m.device, m.n_max = (self.kernel, self.noise_var, self.mean,
                                                                               self.jitter, self.chunk, self.device, self.n_max)
         m.contraction = getattr(self, "contraction", None)
+        m.incremental_update = getattr(self, "incremental_update", False)
+        m.update_path = getattr(self, "update_path", None)
         m._h = handle
         return m
 
@@ -210,15 +216,29 @@ def update(model: HipStandardGP, xs, ys) -> HipStandardGP:
         raise ValueError("xs and ys must both be host arrays or both be tensors on the model's GPU")
     hp = C.c_void_p()
     prm = model._params()
+    info = C.c_int64(0)
+    if getattr(model, "incremental_update", False) and model._h is not None:
+        path = C.c_int32(_lib.UPDATE_REFIT)
+        st = L.abo_update(model._h.ptr, C.byref(prm), None, xp, n, d, yp, xspace, C.byref(info), C.byref(path), C.byref(hp))
+        _lib.check(st, info.value)
+        h = _Handle(hp.value)
+        if getattr(model, "contraction", None) is not None:
+            _lib.check(L.abo_set_contraction(h.ptr, *parse_contraction(model.contraction)))
+        del xkeep, ykeep
+        return _with_path(model._clone(h), path.value)
     _lib.check(L.abo_create(C.byref(prm), C.byref(hp)))
     h = _Handle(hp.value)
     if getattr(model, "contraction", None) is not None:
         _lib.check(L.abo_set_contraction(h.ptr, *parse_contraction(model.contraction)))
-    info = C.c_int64(0)
     st = L.abo_fit(h.ptr, xp, n, d, yp, xspace, C.byref(info))
     _lib.check(st, info.value)
     del xkeep, ykeep
-    return model._clone(h)
+    return _with_path(model._clone(h), _lib.UPDATE_REFIT)
+
+
+def _with_path(model, path: int):
+    model.update_path = _lib.UPDATE_PATHS[path]
+    return model
 
 
 # ---- posterior -----------------------------------------------------------------------------------
@@ -319,12 +339,14 @@ def rescale_model(model: HipStandardGP, sigma):
     if not isinstance(mean, ZeroMean):
         mean = ConstMean(mean.c / sigma)
     return HipStandardGP(new_kernel, model.noise_var / sigma ** 2, mean=mean, device=model.device,
-                         jitter=model.jitter, chunk=model.chunk, n_max=model.n_max, contraction=model.contraction)
+                         jitter=model.jitter, chunk=model.chunk, n_max=model.n_max, contraction=model.contraction,
+                         incremental_update=getattr(model, "incremental_update", False))
 
 
 def _update_model_parameters(model: HipStandardGP, kernel: Kernel):
     return HipStandardGP(kernel, model.noise_var, mean=model.mean, device=model.device, jitter=model.jitter,
-                         chunk=model.chunk, n_max=model.n_max, contraction=model.contraction)
+                         chunk=model.chunk, n_max=model.n_max, contraction=model.contraction,
+                         incremental_update=getattr(model, "incremental_update", False))
 
 
 def get_lengthscale(model: HipStandardGP):

@@ -41,7 +41,9 @@ extern "C" {
                                   that shard a set themselves agree on before they take the block form); abo_cand_qei keeps its
                                   pick loop on the device (one launch per pick, one read-back per batch); abo_fill_distance;
                                   abo_timings grew (abo_nlml_grad phases, the bordered append's mat-vecs); the abo_test_* building
-                                  blocks left the shipped library (test build only: ABO_TEST_HOOKS) */
+                                  blocks left the shipped library (test build only: ABO_TEST_HOOKS)
+                               added within ABI 7 (backwards-compatible, no struct changed): abo_update, abo_mgpu_update,
+                                  ABO_UPDATE_SHARED / _APPENDED / _REFIT */
 
 /* status codes */
 enum {
@@ -209,6 +211,30 @@ int32_t abo_append(abo_gp* gp, const double* x, int32_t d, double y, int64_t* in
  * *info is the order of the failing leading minor in the library's row order (N·p + q + 1).  abo_cand_* work on such a
  * handle too (function-value grid; a down-date after abo_append_grad is p rank-1 down-dates). */
 int32_t abo_append_grad(abo_gp* gp, const double* x, int32_t d, const double* y, int64_t* info, abo_gp** out);
+
+/* update(model, xs, ys) (src/surrogates/StandardGP.jl:79-83, GradientGP.jl:659-668) that reuses `prev` when (X, y) extends the data
+ * prev is conditioned on — what the BO loop passes every iteration (src/bayesian_opt.jl:119-125: the previous points plus the one just
+ * evaluated, under standardisation constants fixed before the loop).  The bordered appends run when ALL of these hold:
+ *   prev is fitted, d matches, N ≥ Nprev;
+ *   X[0:Nprev], y[0:Nprev] equal prev's points and targets bit for bit (checked on the device by one pass over N·(d + p)·8 bytes;
+ *     −0.0 against 0.0 or another NaN payload is a mismatch; for a gradient-enhanced handle y is by outputs, as abo_fit takes it);
+ *   family, ell, sigma_f2, noise_var, mean_c, jitter (and, for a gradient-enhanced handle, the p values of mean_c) bitwise equal prev's;
+ *   prev's factor was built with noise_var itself (a jittered factor goes back through the refit's jitter ladder);
+ *   the k = N − Nprev new points make k·p ≤ kmax(R) appended rows, R = prev's factor rows (the crossover rule below);
+ *   prev's storage has room for them and no other view appended past prev (else: refit with capacity max(n_max, 2N) points).
+ * Then: k bordered appends (abo_append / abo_append_grad semantics, agreeing with the refit to rounding), or for k = 0 a new
+ * reference to prev.  Anything else: the same refit abo_create(_grad) + abo_fit would do, with a handle of prev's kind.
+ * Crossover rule: kmax(R) = clamp(R / 128, 4, 64) rows.  Measured (profiles/update_latency.txt, k sequential appends against one
+ * refit, d = 8, Matérn-5/2): they cost as much as the refit at k ≈ 10 for N = 1024 (rule: 8) and beyond k = 64 for N = 8192 (ratio
+ * 0.84 at 64; rule: 64); the floor of 4 rows (one point of a d = 3 gradient-enhanced model) is not measured.
+ * `prev` stays valid and unchanged.  *path (may be NULL): ABO_UPDATE_SHARED / _APPENDED / _REFIT = what ran.  space: ABO_HOST /
+ * ABO_DEVICE as abo_fit.  A failed append with jitter = 0: ABO_ENOTPD with *info = the order of the failing leading minor, as a
+ * refit's potrf reports it (Nprev + j + 1; gradient-enhanced: the library's row order, abo_append_grad); with jitter > 0 the refit
+ * runs instead (its jitter ladder applies exactly as in abo_fit).  The intermediate views of a failed sequence are destroyed and give
+ * their rows back, so prev stays appendable.  mean_c: p values for a gradient-enhanced prev (NULL = 0), ignored otherwise. */
+enum { ABO_UPDATE_SHARED = 0, ABO_UPDATE_APPENDED = 1, ABO_UPDATE_REFIT = 2 };
+int32_t abo_update(abo_gp* prev, const abo_params* params, const double* mean_c, const double* X, int64_t N, int32_t d,
+                   const double* y, int32_t space, int64_t* info, int32_t* path, abo_gp** out);
 
 /* --- posterior ------------------------------------------------------------------------------
  * posterior_mean / posterior_var (src/surrogates/StandardGP.jl:361-363, :377-379), fused as in
@@ -502,6 +528,11 @@ int32_t abo_mgpu_acq_lhs(abo_mgpu* mg, int64_t n, int32_t d, const double* lower
  * idx_out / ei_out q.  distinct != 0 excludes every picked candidate for the rest of the call. */
 int32_t abo_mgpu_append(abo_mgpu* mg, const double* x, int32_t d, double y, int64_t* info, abo_mcand* cands);
 int32_t abo_mgpu_append_grad(abo_mgpu* mg, const double* x, int32_t d, const double* y, int64_t* info, abo_mcand* cands);
+/* abo_update for a group: the same rule, the prefix compared on the group's first device (the data is replicated); then a clone of
+ * `prev` moves through the k appends (abo_mgpu_append / _append_grad), or a new group on prev's device list is created and fitted
+ * (abo_mgpu_create(_grad) + abo_mgpu_fit; params->device is ignored).  `prev` is never mutated.  Host buffers only. */
+int32_t abo_mgpu_update(abo_mgpu* prev, const abo_params* params, const double* mean_c, const double* X, int64_t N, int32_t d,
+                        const double* y, int64_t* info, int32_t* path, abo_mgpu** out);
 /* abo_optimize_acquisition across the group's devices: the grid stage as abo_mgpu_acq_lhs (shards generated, scored and reduced
  * on their devices, ONE all-gather of the selections), then the selected starts are dealt out contiguously and every device
  * refines its share with abo_refine's launch; a start's refinement does not depend on which device runs it, so the result equals

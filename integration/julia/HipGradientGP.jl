@@ -30,14 +30,16 @@ struct HipGradientGP{T,G<:AbstractGPs.GP} <: AbstractSurrogate
     gpx::Union{Nothing,AboHandle}
     device::Int32; jitter::Float64; n_max::Int64
     devices::Vector{Int32}               # more than one entry: abo_mgpu_create_grad (the model replicated, candidates sharded)
+    incremental::Bool                    # update(m, xs, ys) through abo_update (bordered appends when the data extends m's)
 end
 
-function HipGradientGP(kernel::Kernel, p::Int, noise_var; mean=gradConstMean(zeros(p)), device=0, devices=[device], jitter=0.0, n_max=0)
+function HipGradientGP(kernel::Kernel, p::Int, noise_var; mean=gradConstMean(zeros(p)), device=0, devices=[device], jitter=0.0, n_max=0,
+                       incremental_update=false)
     s = GradientGP(kernel, p, noise_var; mean=mean)           # reuse the normal-form + gradKernel logic (:622-643)
-    HipGradientGP(s.gp, noise_var, p, nothing, Int32(devices[1]), Float64(jitter), Int64(n_max), Int32.(devices))
+    HipGradientGP(s.gp, noise_var, p, nothing, Int32(devices[1]), Float64(jitter), Int64(n_max), Int32.(devices), Bool(incremental_update))
 end
-HipGradientGP(gp, noise_var, p, gpx, device, jitter, n_max) = HipGradientGP(gp, noise_var, p, gpx, device, jitter, n_max, Int32[device])
-_with(m::HipGradientGP, gpx) = HipGradientGP(m.gp, m.noise_var, m.p, gpx, m.device, m.jitter, m.n_max, m.devices)
+HipGradientGP(gp, noise_var, p, gpx, device, jitter, n_max) = HipGradientGP(gp, noise_var, p, gpx, device, jitter, n_max, Int32[device], false)
+_with(m::HipGradientGP, gpx) = HipGradientGP(m.gp, m.noise_var, m.p, gpx, m.device, m.jitter, m.n_max, m.devices, m.incremental)
 _multi(m::HipGradientGP) = length(m.devices) > 1
 
 get_lengthscale(m::HipGradientGP) = 1 ./ m.gp.kernel.base_kernel.kernel.transform.s
@@ -48,7 +50,7 @@ prep_input(m::HipGradientGP, xs) = xs                          # the library add
 prep_output(::HipGradientGP, y::Vector) = vec(permutedims(reduce(hcat, y)))      # by outputs, :919
 _get_minimum(::HipGradientGP, ys::Vector) = minimum(y[1] for y in ys)            # function values only, :1044
 _update_model_parameters(m::HipGradientGP, k::Kernel) =
-    HipGradientGP(k, m.p, m.noise_var; mean=m.gp.mean, devices=m.devices, jitter=m.jitter, n_max=m.n_max)
+    HipGradientGP(k, m.p, m.noise_var; mean=m.gp.mean, devices=m.devices, jitter=m.jitter, n_max=m.n_max, incremental_update=m.incremental)
 
 # standardisation helpers: host arithmetic only — forwarded to the reference's own methods (GradientGP.jl:753-820) on a prior-only
 # GradientGP holding the same gp / noise / p
@@ -57,7 +59,7 @@ get_mean_std(m::HipGradientGP, y_train::AbstractVector, choice::String) = get_me
 std_y(m::HipGradientGP, ys::AbstractVector, μ::AbstractVector, σ::AbstractVector) = std_y(_ref(m), ys, μ, σ)
 function rescale_model(m::HipGradientGP, σ::AbstractVector)
     r = rescale_model(_ref(m), σ)
-    HipGradientGP(r.gp, r.noise_var, m.p, nothing, m.device, m.jitter, m.n_max, m.devices)
+    HipGradientGP(r.gp, r.noise_var, m.p, nothing, m.device, m.jitter, m.n_max, m.devices, m.incremental)
 end
 
 function Base.copy(m::HipGradientGP)                                              # :32
@@ -85,6 +87,21 @@ function update(m::HipGradientGP, xs::AbstractVector, ys::AbstractVector)       
     length(ys) == N || throw(DimensionMismatch("xs has $N points, ys $(length(ys)) observations"))
     all(y -> length(y) == m.p, ys) || throw(DimensionMismatch("each observation must hold p = $(m.p) values"))
     y = collect(Float64, prep_output(m, ys)); info = Ref{Int64}(0)
+    if m.incremental && m.gpx !== nothing                  # abo_update / abo_mgpu_update (HipStandardGP.jl: update)
+        prm = Ref(AboParams(_family(get_kernel_constructor(m)), m.device, get_lengthscale(m)[1], get_scale(m)[1], m.noise_var,
+                            _mean_vec(m)[1], m.jitter, m.n_max, 0))
+        h = Ref{Ptr{Cvoid}}(); mv = _mean_vec(m); path = Ref{Int32}(0)
+        if m.gpx.multi
+            GC.@preserve mv X y _check(@abocall(LIBABO.abo_mgpu_update(m.gpx.ptr::Ptr{Cvoid}, prm::Ptr{AboParams}, mv::Ptr{Float64},
+                X::Ptr{Float64}, N::Int64, d::Int32, y::Ptr{Float64}, info::Ptr{Int64}, path::Ptr{Int32},
+                h::Ptr{Ptr{Cvoid}})::Int32), info[])
+            return _with(m, AboHandle(h[], true))
+        end
+        GC.@preserve mv X y _check(@abocall(LIBABO.abo_update(m.gpx.ptr::Ptr{Cvoid}, prm::Ptr{AboParams}, mv::Ptr{Float64},
+            X::Ptr{Float64}, N::Int64, d::Int32, y::Ptr{Float64}, 0::Int32, info::Ptr{Int64}, path::Ptr{Int32},
+            h::Ptr{Ptr{Cvoid}})::Int32), info[])
+        return _with(m, AboHandle(h[]))
+    end
     if _multi(m)                                           # replicated on every listed device (abo_mgpu_create_grad + abo_mgpu_fit)
         prm = Ref(AboParams(_family(get_kernel_constructor(m)), m.device, get_lengthscale(m)[1], get_scale(m)[1], m.noise_var,
                             _mean_vec(m)[1], m.jitter, m.n_max, 0))

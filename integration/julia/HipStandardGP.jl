@@ -67,15 +67,16 @@ struct HipStandardGP{T} <: AbstractSurrogate
     devices::Vector{Int32}               # one entry: single-device handle; several: abo_mgpu (sharding inside the library)
     jitter::Float64
     n_max::Int64                         # capacity for `append` (0 = size to the fit)
+    incremental::Bool                    # update(m, xs, ys) through abo_update (bordered appends when the data extends m's)
 end
 
 _family(::SqExponentialKernel) = Int32(0); _family(::Matern52Kernel) = Int32(1)
 _family(::ApproxMatern52Kernel) = Int32(1); _family(::ApproxMatern72Kernel) = Int32(2)
 _family(::Matern32Kernel) = Int32(3)
 
-function HipStandardGP(kernel::Kernel, noise_var; mean=nothing, devices=[0], jitter=0.0, n_max=0)
+function HipStandardGP(kernel::Kernel, noise_var; mean=nothing, devices=[0], jitter=0.0, n_max=0, incremental_update=false)
     s = StandardGP(kernel, noise_var; mean=mean)           # reuse the normal-form logic (StandardGP.jl:41-64)
-    HipStandardGP(s.gp, noise_var, nothing, Int32.(devices), Float64(jitter), Int64(n_max))
+    HipStandardGP(s.gp, noise_var, nothing, Int32.(devices), Float64(jitter), Int64(n_max), Bool(incremental_update))
 end
 # Engine of the N²·M variance contraction behind posterior_var (include/abo_hip.h: abo_set_contraction), process-wide for the
 # handles created from now on — :auto (int8-residue engine from 1536 factor rows, fp64 MFMA below), :fp64 or :int8;
@@ -85,7 +86,7 @@ function set_contraction!(engine::Symbol=:auto; moduli::Integer=0)
     _check(@ccall LIBABO.abo_set_contraction(C_NULL::Ptr{Cvoid}, e::Int32, Int32(moduli)::Int32)::Int32)
 end
 
-_with(m::HipStandardGP, gpx) = HipStandardGP(m.gp, m.noise_var, gpx, m.devices, m.jitter, m.n_max)
+_with(m::HipStandardGP, gpx) = HipStandardGP(m.gp, m.noise_var, gpx, m.devices, m.jitter, m.n_max, m.incremental)
 _multi(m::HipStandardGP) = length(m.devices) > 1
 
 function _check(st::Int32, info::Int64=0)
@@ -118,7 +119,7 @@ _get_minimum(::HipStandardGP, ys::Vector) = minimum(ys)                         
 
 # a new un-conditioned model with another kernel, everything else kept (StandardGP.jl:246-248)
 _update_model_parameters(m::HipStandardGP, k::Kernel) =
-    HipStandardGP(k, m.noise_var; mean=m.gp.mean, devices=m.devices, jitter=m.jitter, n_max=m.n_max)
+    HipStandardGP(k, m.noise_var; mean=m.gp.mean, devices=m.devices, jitter=m.jitter, n_max=m.n_max, incremental_update=m.incremental)
 
 # ---- standardisation helpers: host scalars only, so they FORWARD to the reference's own methods (StandardGP.jl:164-232) on a
 # prior-only StandardGP holding the same gp / noise — nothing of their arithmetic is restated here -----------------------
@@ -127,7 +128,7 @@ get_mean_std(m::HipStandardGP, y_train::Vector, choice::String) = get_mean_std(_
 std_y(m::HipStandardGP, ys::Vector, μ, σ) = std_y(_ref(m), ys, μ, σ)
 function rescale_model(m::HipStandardGP, σ)
     r = rescale_model(_ref(m), σ)                            # kernel scale / σ², noise / σ², a ConstMean moves with the data
-    HipStandardGP(r.gp, r.noise_var, nothing, m.devices, m.jitter, m.n_max)
+    HipStandardGP(r.gp, r.noise_var, nothing, m.devices, m.jitter, m.n_max, m.incremental)
 end
 function unstandardized_mean_and_var(m::HipStandardGP, xs::AbstractVector, params::Tuple)   # StandardGP.jl:395-404
     μ, σ = params[1], params[2]
@@ -154,6 +155,21 @@ function update(m::HipStandardGP, xs::AbstractVector, ys::AbstractVector)       
     _ensure_abi()
     X = _pack(xs); d, N = size(X); length(ys) == N || throw(DimensionMismatch("xs has $N points, ys $(length(ys)) values"))
     p = Ref(_params(m)); h = Ref{Ptr{Cvoid}}(); info = Ref{Int64}(0); y = collect(Float64, ys)
+    if m.incremental && m.gpx !== nothing
+        # abo_update / abo_mgpu_update: bordered appends when (xs, ys) extends the data m is conditioned on (the driver's
+        # update(BO.model, BO.xs, BO.ys), bayesian_opt.jl:119-125), otherwise the same refit as below; m itself stays valid
+        path = Ref{Int32}(0)
+        if m.gpx.multi
+            GC.@preserve X y _check(@abocall(LIBABO.abo_mgpu_update(m.gpx.ptr::Ptr{Cvoid}, p::Ptr{AboParams}, C_NULL::Ptr{Float64},
+                X::Ptr{Float64}, N::Int64, d::Int32, y::Ptr{Float64}, info::Ptr{Int64}, path::Ptr{Int32},
+                h::Ptr{Ptr{Cvoid}})::Int32), info[])
+            return _with(m, AboHandle(h[], true))
+        end
+        GC.@preserve X y _check(@abocall(LIBABO.abo_update(m.gpx.ptr::Ptr{Cvoid}, p::Ptr{AboParams}, C_NULL::Ptr{Float64},
+            X::Ptr{Float64}, N::Int64, d::Int32, y::Ptr{Float64}, 0::Int32, info::Ptr{Int64}, path::Ptr{Int32},
+            h::Ptr{Ptr{Cvoid}})::Int32), info[])
+        return _with(m, AboHandle(h[]))
+    end
     if _multi(m)
         devs = m.devices
         GC.@preserve devs _check(@ccall LIBABO.abo_mgpu_create(p::Ptr{AboParams}, length(devs)::Int32, devs::Ptr{Int32},
@@ -359,8 +375,9 @@ function append(m::HipStandardGP, x::AbstractVector{Float64}, y::Float64)       
                                                      info::Ptr{Int64}, h::Ptr{Ptr{Cvoid}})::Int32), info[])
     _with(m, AboHandle(h[]))
 end
-# update(BO, x, y, i) (bayesian_opt.jl:113-150) can call `append(BO.model, x, y)` instead of
-# `update(BO.model, BO.xs, BO.ys)`; `prev_gp = copy(BO.model)` stays valid because rows ≤ N are never touched.
+# The driver needs no edit to reach this path: a model built with `incremental_update=true` answers its
+# `update(BO.model, BO.xs, BO.ys)` (bayesian_opt.jl:119-125) with these appends (abo_update).  `prev_gp = copy(BO.model)`
+# (Base.copy: abo_retain / abo_mgpu_clone) is an independent view that stays valid, because rows ≤ N are never touched.
 
 # ---- resident candidate grid + greedy q-EI (BASELINE config 5; no reference counterpart) ------------------------------
 # The grid's points, posterior (μ, σ²) and K_ZX stay on the device(s); an `append` is followed by an O(N·M) down-date instead
