@@ -1,7 +1,7 @@
 """abstractbayesopt.jl_amd — MI355X-native GP surrogate backend behind AbstractBayesOpt.jl's
 AbstractSurrogate / AbstractAcquisition interface (hot path only: update → posterior → EI/UCB →
 top-k).  Import as ``import abstractbayesopt.jl_amd as abo``."""
-from . import _lib, acquisition, distributed, incremental, multigpu, synth
+from . import _lib, acquisition, distributed, incremental, multigpu, synth, thompson
 from ._lib import AboError, DimensionMismatch, PosDefException
 from .acquisition import (AbstractAcquisition, EnsembleAcquisition, ExpectedImprovement, ProbabilityImprovement,
                           UpperConfidenceBound, device_latin_hypercube, evaluate, latin_hypercube,
@@ -17,6 +17,7 @@ from .multigpu import HipShardedGP, HipShardedGradientGP, ShardedCandidates
 from .kernels import (ApproxMatern52Kernel, ApproxMatern72Kernel, ConstMean, Kernel, Matern32Kernel, Matern52Kernel,
                       ScaledKernel, SqExponentialKernel, ZeroMean, with_lengthscale)
 from . import surrogate as _s
+from .thompson import SamplePaths, sample_paths, spectral_frequencies, thompson_batch
 from .surrogate import (AbstractSurrogate, HipStandardGP, _get_minimum, _update_model_parameters,
                         get_factor, get_kernel_constructor, get_lengthscale, get_mean_std, get_scale, mean_and_var,
                         nlml, nlml_fitted, nlml_ls, posterior_mean, posterior_var, prep_input, prep_output,

@@ -22,7 +22,8 @@ EXPORTS = ["abo_create", "abo_set_contraction", "abo_create_grad", "abo_predict_
            "abo_optimize_acquisition_terms", "abo_mgpu_optimize_acquisition_terms",
            "abo_set_qei_block", "abo_cand_qei", "abo_cand_qei_begin", "abo_cand_qei_top", "abo_cand_qei_block", "abo_cand_qei_pick",
            "abo_cand_qei_end", "abo_cand_qei_has", "abo_cand_qei_stats", "abo_mgpu_cand_qei_stats", "abo_cand_qei_eligible", "abo_fill_distance",
-           "abo_update", "abo_mgpu_update", "abo_cand_qei_mc"]
+           "abo_update", "abo_mgpu_update", "abo_cand_qei_mc",
+           "abo_paths_create", "abo_paths_destroy", "abo_paths_eval", "abo_paths_eval_cand", "abo_paths_stats_get"]
 TEST_EXPORTS = ["abo_test_gemm_nt", "abo_test_kappa", "abo_test_oz_plan", "abo_test_oz_contract", "abo_test_acq_grad",
                 "abo_test_acq_grad_terms"]
 ABI_VERSION = 7
@@ -58,6 +59,15 @@ class AboQeiStats(C.Structure):
     _fields_ = [("picks", C.c_int32), ("block", C.c_int32), ("block_builds", C.c_int32), ("block_hits", C.c_int32),
                 ("total_ms", C.c_double), ("block_ms", C.c_double), ("pass_ms", C.c_double), ("pass_bytes", C.c_double),
                 ("pass_flop", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class AboPathsStats(C.Structure):
+    """times and sizes of a sample-path object's last create / eval (include/abo_hip.h: abo_paths_stats)"""
+    _fields_ = [("create_ms", C.c_double), ("eval_ms", C.c_double), ("eval_flop", C.c_double), ("S", C.c_int64), ("R", C.c_int64),
+                ("N", C.c_int64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -187,6 +197,11 @@ def lib():
     L.abo_cand_qei_has.argtypes = [vp, vp, i64, C.POINTER(i32), C.POINTER(i32)]
     L.abo_cand_qei_stats.argtypes = [vp, vp, C.POINTER(AboQeiStats)]
     L.abo_cand_qei_mc.argtypes = [vp, vp, i32, f64, f64, vp, i32, i32, i64, i32, vp, vp, vp, C.POINTER(AboQeiStats)]
+    L.abo_paths_create.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, C.POINTER(vp)]
+    L.abo_paths_destroy.argtypes = [vp]
+    L.abo_paths_eval.argtypes = [vp, vp, i64, i32, i32, i64, vp, i32, vp, vp, i32]
+    L.abo_paths_eval_cand.argtypes = [vp, vp, i64, vp, i32, vp, vp, i32]
+    L.abo_paths_stats_get.argtypes = [vp, C.POINTER(AboPathsStats)]
     L.abo_refine.argtypes = [vp, i32, f64, f64, vp, vp, i32, vp, i32, C.POINTER(AboRefineOpts), vp, vp, vp]
     L.abo_optimize_acquisition.argtypes = [vp, i32, f64, f64, vp, vp, i32, i64, i32, C.c_uint64, C.POINTER(AboRefineOpts),
                                            vp, C.POINTER(f64), vp, vp, vp, vp]

@@ -83,6 +83,8 @@ int gp_dim(const abo_gp* g);
 const double* cand_points(const abo_cand* c);      // device, [M][d]
 const double* cand_mu(const abo_cand* c);          // device, [M]
 int64_t cand_size(const abo_cand* c);
+int cand_dim(const abo_cand* c);
+int cand_device(const abo_cand* c);
 
 // ---- abo_update / abo_mgpu_update (update.hip): what they read of a handle, and the append / pool / wait machinery of api.hip
 struct GpState {
@@ -102,6 +104,10 @@ bool gp_state(abo_gp* g, GpState* out);   // false: not fitted (device, p_out an
 // a full refit with doubled capacity when the storage is full or claimed by a larger view)
 int32_t gp_append_into(abo_gp* g, abo_gp* n, const double* x, const double* yv, int64_t* info);
 const void* gp_storage(const abo_gp* g);
+// what the sample paths (paths.hip) read of a fitted model's factor: scaled points [≥ rows][dp], L⁻¹ (lower) and its transpose with
+// leading dimension ld, and the process-wide id of the factor storage (never reused, unlike its address)
+struct FactorView { const double* Xs; const double* W; const double* WT; int64_t ld; int dp; uint64_t gen; };
+bool gp_factor_view(abo_gp* g, FactorView* out);   // false: not fitted
 char* gp_pin(abo_gp* g, size_t* bytes);   // the handle's page-locked staging block past the fit scalars (null if it has none)
 hipError_t stream_wait(hipStream_t s);     // the polled wait every call ends with
 hipError_t scratch_alloc(int dev, size_t bytes, void** p, size_t* cap);   // the device-memory pool

@@ -3116,6 +3116,8 @@ int abo::gp_dim(const abo_gp* g) { return g->fitted ? g->d : 0; }
 const double* abo::cand_points(const abo_cand* c) { return c->Z.as<double>(); }
 const double* abo::cand_mu(const abo_cand* c) { return c->mu.as<double>(); }
 int64_t abo::cand_size(const abo_cand* c) { return c->M; }
+int abo::cand_dim(const abo_cand* c) { return c->d; }
+int abo::cand_device(const abo_cand* c) { return c->device; }
 int32_t abo::set_error(int32_t code, const char* text) { return fail(code, "%s", text); }
 const char* abo::last_error_text() { return g_err; }
 
@@ -3140,6 +3142,12 @@ int32_t abo::gp_append_into(abo_gp* g, abo_gp* n, const double* x, const double*
     return g->p_out > 1 ? append_grad_impl(g, n, x, yv, info) : append_impl(g, n, x, yv[0], info);
 }
 const void* abo::gp_storage(const abo_gp* g) { return g->fitted ? g->st : nullptr; }
+bool abo::gp_factor_view(abo_gp* g, FactorView* o) {
+    if (!g->fitted || !g->st) return false;
+    Storage* st = g->st;
+    *o = FactorView{st->Xs.as<double>(), st->W.as<double>(), st->WT.as<double>(), st->cap, st->dp, st->gen};
+    return true;
+}
 char* abo::gp_pin(abo_gp* g, size_t* bytes) {
     if (!g->ctx || !g->ctx->pin) { *bytes = 0; return nullptr; }
     *bytes = PIN_BYTES - PIN_OUT;                    // [0, PIN_OUT) holds a fit's scalars

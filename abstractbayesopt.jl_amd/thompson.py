@@ -1,0 +1,180 @@
+"""Thompson sampling: pathwise posterior sample paths (include/abo_hip.h: abo_paths_*).  No reference counterpart — the
+reference's acquisitions are EI, UCB, PI, GradientNormUCB and ensembles of them.
+
+A posterior sample is g_s(z) = f_s(z) + k(z, X)·v_s with a prior draw f_s in R random Fourier features and the exact kernel row
+(Matheron's rule; Wilson et al. 2020).  The base randomness (frequencies, phases, feature weights, noise draws) is drawn HERE, on the
+host, and handed to the library: the paths are a deterministic function of it, and a `SamplePaths` keeps the four arrays so that
+anyone can restate its values.  The reference minimises, so a Thompson pick is the arg-min of a path."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import DEVICE, HOST
+from .kernels import MATERN32, MATERN52, MATERN72, SE
+from .surrogate import HipStandardGP, _is_torch, as_points
+
+_NU = {MATERN32: 1.5, MATERN52: 2.5, MATERN72: 3.5}
+
+
+def _rng(rng):
+    return rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)
+
+
+def spectral_frequencies(kernel, R: int, d: int, rng=None) -> np.ndarray:
+    """R frequencies (R × d) of the UNIT-lengthscale kernel of `kernel`'s family, i.e. draws from its spectral density:
+    SE → N(0, I); Matérn-ν (ν = 3/2, 5/2, 7/2) → N(0, I) / sqrt(χ²_{2ν} / 2ν), the multivariate Student-t with 2ν degrees of
+    freedom.  With phases uniform in [0, 2π), E[2·cos(ω·x + b)·cos(ω·z + b)] = κ(‖x − z‖)."""
+    family = getattr(kernel, "family", kernel)
+    rng = _rng(rng)
+    R, d = int(R), int(d)
+    if R < 1 or d < 1:
+        raise ValueError(f"spectral_frequencies: R = {R}, d = {d}")
+    z = rng.standard_normal((R, d))
+    if family == SE:
+        return z
+    if family not in _NU:
+        raise ValueError(f"spectral_frequencies: unknown kernel family {family!r}")
+    dof = 2.0 * _NU[family]
+    return z / np.sqrt(rng.chisquare(dof, size=(R, 1)) / dof)
+
+
+class _PathsHandle:
+    def __init__(self, ptr):
+        self.ptr = ptr
+
+    def __del__(self):
+        try:
+            if self.ptr:
+                _lib.lib().abo_paths_destroy(self.ptr)
+                self.ptr = None
+        except Exception:
+            pass
+
+
+def _is_resident(x):
+    from .incremental import ResidentCandidates
+    return isinstance(x, ResidentCandidates)
+
+
+class SamplePaths:
+    """S sample paths of one conditioned model.  Attributes omega (R × d), phase (R), w (S × R), eps (S × N): the base draws."""
+
+    def __init__(self, model, omega, phase, w, eps):
+        if hasattr(model, "devices"):
+            raise TypeError("sample paths of a sharded model (HipShardedGP) are not implemented: draw them from a single-device "
+                            "HipStandardGP conditioned on the same data")
+        if not isinstance(model, HipStandardGP):
+            raise TypeError(f"sample paths need a HipStandardGP, not {type(model).__name__}")
+        self.omega = np.ascontiguousarray(omega, dtype=np.float64)
+        self.phase = np.ascontiguousarray(phase, dtype=np.float64)
+        self.w = np.ascontiguousarray(w, dtype=np.float64)
+        self.eps = np.ascontiguousarray(eps, dtype=np.float64)
+        if self.w.ndim != 2:
+            raise ValueError(f"SamplePaths: w must be (S, R), not {self.w.shape}")
+        self.S, self.R = self.w.shape
+        N, d = _model_shape(model)                      # (raises when the model is not conditioned on data)
+        for name, a, want in (("omega", self.omega, (self.R, d)), ("phase", self.phase, (self.R,)), ("eps", self.eps, (self.S, N))):
+            if a.shape != want:
+                raise ValueError(f"SamplePaths: {name} has shape {a.shape}, the model (N = {N}, d = {d}) and w {self.w.shape} need {want}")
+        self.model = model
+        hp = C.c_void_p()
+        _lib.check(_lib.lib().abo_paths_create(model._require(), self.S, self.R, self.omega.ctypes.data, self.phase.ctypes.data,
+                                               self.w.ctypes.data, self.eps.ctypes.data, HOST, C.byref(hp)))
+        self._h = _PathsHandle(hp.value)
+
+    def _eval(self, Z, want_values, k, idx_base=0):
+        L, S, k = _lib.lib(), self.S, int(k)
+        if _is_resident(Z):
+            m, space, dev = Z.M, HOST, None
+        else:
+            zp, m, d, space, keep = as_points(Z)
+            dev = keep.device if space == DEVICE else None
+        if space == DEVICE:
+            import torch
+            values = torch.empty((S, m), dtype=torch.float64, device=dev) if want_values else None
+            tv = torch.empty((S, k), dtype=torch.float64, device=dev) if k else None
+            ti = torch.empty((S, k), dtype=torch.int64, device=dev) if k else None
+            ptr = lambda a: a.data_ptr() if a is not None else None
+        else:
+            values = np.empty((S, m)) if want_values else None
+            tv = np.empty((S, k)) if k else None
+            ti = np.empty((S, k), dtype=np.int64) if k else None
+            ptr = lambda a: a.ctypes.data if a is not None else None
+        if _is_resident(Z):
+            st = L.abo_paths_eval_cand(self._h.ptr, Z._h.ptr, int(idx_base), ptr(values), k, ptr(tv), ptr(ti), HOST)
+        else:
+            st = L.abo_paths_eval(self._h.ptr, zp, m, d, space, int(idx_base), ptr(values), k, ptr(tv), ptr(ti), space)
+        _lib.check(st)
+        return values, tv, ti
+
+    def __call__(self, Z):
+        """g_s(z_j) as an (S, M) array (NumPy for host inputs and resident sets, a torch tensor on the GPU for device inputs)"""
+        return self._eval(Z, True, 0)[0]
+
+    def argmin(self, Z, k: int = 1, idx_base: int = 0):
+        """per path the k candidates with the smallest g_s: (values (S, k), indices (S, k)) in abo_acq's order on −g_s"""
+        if k < 1:
+            raise ValueError(f"argmin: k = {k}")
+        _, tv, ti = self._eval(Z, False, k, idx_base)
+        return tv, ti
+
+    def stats(self) -> dict:
+        st = _lib.AboPathsStats()
+        _lib.check(_lib.lib().abo_paths_stats_get(self._h.ptr, C.byref(st)))
+        return st.as_dict()
+
+
+def draw_base(kernel, S: int, R: int, N: int, d: int, rng=None):
+    """the four base arrays of S paths in R features for a model of N points in d dimensions: (omega, phase, w, eps)"""
+    rng = _rng(rng)
+    omega = spectral_frequencies(kernel, R, d, rng)
+    phase = rng.uniform(0.0, 2.0 * np.pi, size=R)
+    w = rng.standard_normal((S, R))
+    eps = rng.standard_normal((S, N))
+    return omega, phase, w, eps
+
+
+def _model_shape(model):
+    n, d = C.c_int64(), C.c_int32()
+    _lib.check(_lib.lib().abo_get_n(model._require(), C.byref(n), C.byref(d)))
+    return n.value, d.value
+
+
+def sample_paths(model, S: int, R: int = 1024, rng=None) -> SamplePaths:
+    """S posterior sample paths of `model` in R random Fourier features; the base draws come from `rng` (a seed or a Generator)"""
+    if hasattr(model, "devices"):
+        raise TypeError("sample_paths: a sharded model (HipShardedGP) is not supported: draw the paths from a single-device "
+                        "HipStandardGP conditioned on the same data")
+    if not isinstance(model, HipStandardGP):
+        raise TypeError(f"sample_paths needs a HipStandardGP, not {type(model).__name__}")
+    N, d = _model_shape(model)
+    return SamplePaths(model, *draw_base(model.kernel, int(S), int(R), N, d, rng))
+
+
+def distinct_picks(top_idx) -> np.ndarray:
+    """path s takes its best index not taken by paths 0 … s − 1; top_idx: (q, k ≥ q) per-path orderings (−1: no candidate)"""
+    taken, picks = set(), []
+    for row in np.asarray(top_idx):
+        for j in row:
+            j = int(j)
+            if j >= 0 and j not in taken:
+                taken.add(j)
+                picks.append(j)
+                break
+        else:
+            raise ValueError(f"thompson_batch: path {len(picks)} has no candidate left that earlier paths did not take")
+    return np.asarray(picks, dtype=np.int64)
+
+
+def thompson_batch(model, Z, q: int, R: int = 1024, rng=None) -> np.ndarray:
+    """q DISTINCT candidate indices (into Z, or into a ResidentCandidates set): the arg-mins of q independent sample paths, path s
+    taking its best candidate not taken by paths 0 … s − 1"""
+    q = int(q)
+    if q < 1:
+        raise ValueError(f"thompson_batch: q = {q}")
+    paths = sample_paths(model, q, R, rng)
+    _, ti = paths.argmin(Z, k=q)
+    if _is_torch(ti):
+        ti = ti.cpu().numpy()
+    return distinct_picks(ti)

@@ -43,7 +43,8 @@ extern "C" {
                                   abo_timings grew (abo_nlml_grad phases, the bordered append's mat-vecs); the abo_test_* building
                                   blocks left the shipped library (test build only: ABO_TEST_HOOKS)
                                added within ABI 7 (backwards-compatible, no struct changed): abo_update, abo_mgpu_update,
-                                  ABO_UPDATE_SHARED / _APPENDED / _REFIT; abo_cand_qei_mc */
+                                  ABO_UPDATE_SHARED / _APPENDED / _REFIT; abo_cand_qei_mc; abo_paths_create, abo_paths_destroy,
+                                  abo_paths_eval, abo_paths_eval_cand, abo_paths_stats_get (struct abo_paths_stats is new) */
 
 /* status codes */
 enum {
@@ -448,6 +449,52 @@ int32_t abo_cand_qei_stats(abo_gp* gp, abo_cand* c, abo_qei_stats* out);
 int32_t abo_cand_qei_mc(abo_gp* gp, abo_cand* c, int32_t q, double xi, double best_y, const double* base, int32_t S,
                         int32_t base_space, int64_t idx_base, int32_t block, double* x_out, int64_t* idx_out,
                         double* qei_out, abo_qei_stats* stats);
+
+/* --- Thompson sampling: pathwise posterior sample paths (added within ABI 7) --------------------------------------------------
+ * No reference counterpart (its acquisitions are EI, UCB, PI, GradientNormUCB and ensembles of them, src/acquisition_functions/): a
+ * draw of a FUNCTION from the posterior, by pathwise conditioning (Matheron's rule; Wilson et al. 2020).  The reference minimises
+ * (EI's best_y is minimum(ys), ExpectedImprovement.jl:81-83), so a Thompson pick is the arg-min of a path; a batch of q picks is q
+ * arg-mins of independent paths and never touches σ².
+ * Model: a fitted STANDARD GP handle — family, ℓ, σ_f², σ²_n = noise_var, mean c, points X (N × d), targets y and the factor of
+ * K̃ = k(X,X) + σ²_n·I exactly as abo_fit / abo_append left it (a jittered factor is used as it is).  A gradient-enhanced handle:
+ * ABO_EINVAL.  d ≤ 32 (the register-resident generator; beyond: ABO_EINVAL).
+ * Base quantities, all fp64, supplied by the caller in `space` (ABO_HOST / ABO_DEVICE) — the result is a deterministic function of them:
+ *     omega  R × d, point-major   frequencies of the UNIT-lengthscale kernel (the library divides by ℓ)
+ *     phase  R                    in [0, 2π)
+ *     w      S × R                N(0,1) feature weights
+ *     eps    S × N                N(0,1) observation-noise draws
+ *     φ_r(x) = sqrt(2σ_f²/R)·cos(ω_r·x/ℓ + phase_r)
+ *     f_s(x) = c + Σ_r w[s, r]·φ_r(x)                                          (a prior draw in R random Fourier features)
+ *     v_s    = K̃⁻¹(y − f_s(X) − sqrt(σ²_n)·eps[s, :])                         (N values per path)
+ *     g_s(z) = f_s(z) + Σ_i k(z, x_i)·v_s[i]                                   (k = σ_f²·κ(‖z − x_i‖/ℓ), the library's own κ: the EXACT kernel row)
+ * 1 ≤ S ≤ 256, 1 ≤ R ≤ 65536.  Arguments (null pointers, values out of range) are checked before the handle is looked at and before
+ * any device work.
+ *   abo_paths_create   conditions S paths: f_s(X) by the evaluation pass over the features alone, v_s = L⁻ᵀ(L⁻¹·) from the explicit
+ *                      inverse factor the handle holds, O(N²·S).  The object RETAINS the model (abo_retain): it outlives abo_destroy of the
+ *                      caller's own reference.  It describes the model it was created from: after gp2 = abo_append(gp, …) the paths of gp
+ *                      are still paths of gp, the OLD model (make new ones from gp2); after abo_fit on the very handle `gp` — which replaces
+ *                      that handle's model — abo_paths_eval returns ABO_EINVAL.
+ *   abo_paths_eval     g_s over M candidates (Z point-major, d = the model's: else ABO_EDIM), one generated-operand product on the fp64
+ *                      matrix pipe per chunk of candidates, O((N + R)·M·S); two calls with the same inputs return the same bits.
+ *                      values (S × M, path-major: values[s·M + j]) is optional.  k ≥ 0 (free, as abo_acq's): per path the k candidates
+ *                      with the SMALLEST g_s — abo_acq's ordering applied to score = −g_s (descending score, ties → lowest index, NaN
+ *                      first, tail (NaN, −1) when M < k); top_val (S × k) holds g_s ITSELF (bit for bit values[s·M + top_idx − idx_base]; a NaN comes back as the quiet NaN 0x7ff8…),
+ *                      top_idx (S × k) = idx_base + j.  values / top_* live in out_space.
+ *   abo_paths_eval_cand  the same over a resident set's own coordinates; a candidate taken out by abo_cand_exclude (stored μ = +Inf) gets
+ *                      g_s = +Inf.  The set need not be in sync with the model: only its coordinates and exclusions are read, nothing of it
+ *                      is written.
+ *   abo_paths_stats_get  HIP-event times of the last create / eval on the object, and the algorithmic flop 2·(N + R)·M·S of that eval. */
+/* The paths object — S sample paths of ONE conditioned model, holding a reference to it — crosses the ABI as an untyped handle
+ * (void*), which is what a host without the C type system binds anyway (Julia: Ptr{Cvoid}); only abo_paths_create makes one. */
+typedef struct abo_paths_stats { double create_ms, eval_ms, eval_flop; int64_t S, R, N; } abo_paths_stats;
+int32_t abo_paths_create(abo_gp* gp, int32_t S, int32_t R, const double* omega, const double* phase, const double* w,
+                         const double* eps, int32_t space, void** out);
+int32_t abo_paths_destroy(void* paths);
+int32_t abo_paths_eval(void* paths, const double* Z, int64_t M, int32_t d, int32_t z_space, int64_t idx_base,
+                       double* values, int32_t k, double* top_val, int64_t* top_idx, int32_t out_space);
+int32_t abo_paths_eval_cand(void* paths, abo_cand* c, int64_t idx_base, double* values, int32_t k, double* top_val,
+                            int64_t* top_idx, int32_t out_space);
+int32_t abo_paths_stats_get(void* paths, abo_paths_stats* out);
 
 /* --- grid generation and stand-alone epilogue (DEVICE buffers) --------------------------------------
  * abo_lhs: points j0 .. j0+count−1 of an n-point Latin-hypercube design in the box [lower, upper]

@@ -1,4 +1,4 @@
-# HipStandardGP.jl — binding of libabo_hip.so (include/abo_hip.h, ABI version 5) for AbstractBayesOpt.jl.
+# HipStandardGP.jl — binding of libabo_hip.so (include/abo_hip.h, ABI version 7) for AbstractBayesOpt.jl.
 #
 # Drop next to src/surrogates/StandardGP.jl, `include("surrogates/HipStandardGP.jl")` from src/AbstractBayesOpt.jl
 # (after StandardGP.jl and the acquisition functions) and export HipStandardGP.  Every method the BO driver calls on
@@ -484,4 +484,97 @@ function mc_qei(c::HipCandidates, q::Int; ξ::Float64=0.01, best_y::Float64, sam
                                                                    0::Int64, block::Int32, X::Ptr{Float64}, idx::Ptr{Int64},
                                                                    v::Ptr{Float64}, st::Ptr{AboQeiStats})::Int32)
     X, idx .+ 1, v
+end
+
+# ---- Thompson sampling: pathwise posterior sample paths (include/abo_hip.h: abo_paths_*) -------------------------------------------
+# No reference counterpart (its acquisitions are EI, UCB, PI, GradientNormUCB and ensembles).  A posterior sample is
+# g_s(z) = f_s(z) + k(z, X)·v_s with f_s a prior draw in R random Fourier features (Matheron's rule); the four base arrays are drawn
+# HERE from `rng` and kept with the object, so the paths are a deterministic function of them.  The reference minimises: a Thompson
+# pick is the arg-min of a path.  One device only: a sharded model raises.
+# frequencies of the UNIT-lengthscale kernel (d × R, column r is ω_r): SE → N(0, I); Matérn-ν → N(0, I)/sqrt(χ²_{2ν}/2ν)
+_spectral_dof(::SqExponentialKernel) = 0
+_spectral_dof(::Matern32Kernel) = 3
+_spectral_dof(::Union{Matern52Kernel,ApproxMatern52Kernel}) = 5
+_spectral_dof(::ApproxMatern72Kernel) = 7
+function spectral_frequencies(k::Kernel, R::Int, d::Int, rng=Random.default_rng())
+    ω = randn(rng, d, R)
+    dof = _spectral_dof(k)
+    dof == 0 && return ω
+    for r in 1:R
+        ω[:, r] ./= sqrt(sum(abs2, randn(rng, dof)) / dof)       # χ²_dof as a sum of squares: integer degrees of freedom
+    end
+    ω
+end
+
+mutable struct HipSamplePaths
+    ptr::Ptr{Cvoid}
+    model::HipStandardGP          # the model the paths were conditioned on (the library retains it as well)
+    S::Int
+    R::Int
+    omega::Matrix{Float64}        # d × R
+    phase::Vector{Float64}        # R, in [0, 2π)
+    w::Matrix{Float64}            # R × S  (w[s·R + r] of the C-ABI)
+    eps::Matrix{Float64}          # N × S  (eps[s·N + i])
+end
+
+function sample_paths(m::HipStandardGP, S::Int; R::Int=1024, rng=Random.default_rng())
+    m.gpx === nothing && error("sample_paths: the model has not been fitted (call update first)")
+    m.gpx.multi && error("sample_paths: a sharded model is not supported; draw the paths from a single-device HipStandardGP on the same data")
+    n = Ref{Int64}(0); d = Ref{Int32}(0)
+    _check(@ccall LIBABO.abo_get_n(m.gpx.ptr::Ptr{Cvoid}, n::Ptr{Int64}, d::Ptr{Int32})::Int32)
+    ω = spectral_frequencies(get_kernel_constructor(m), R, Int(d[]), rng)
+    b = 2π .* rand(rng, R); w = randn(rng, R, S); ε = randn(rng, Int(n[]), S)
+    h = Ref{Ptr{Cvoid}}()
+    GC.@preserve ω b w ε _check(@abocall LIBABO.abo_paths_create(m.gpx.ptr::Ptr{Cvoid}, Int32(S)::Int32, Int32(R)::Int32, ω::Ptr{Float64},
+                                                                  b::Ptr{Float64}, w::Ptr{Float64}, ε::Ptr{Float64}, 0::Int32,
+                                                                  h::Ptr{Ptr{Cvoid}})::Int32)
+    p = HipSamplePaths(h[], m, S, R, ω, b, w, ε)
+    finalizer(p) do x
+        @ccall LIBABO.abo_paths_destroy(x.ptr::Ptr{Cvoid})::Int32
+    end
+    p
+end
+
+# g_s(z_j) as an M × S matrix (column s is path s)
+function (p::HipSamplePaths)(zs::AbstractVector)
+    Z = _pack(zs); d, M = size(Z); G = Matrix{Float64}(undef, M, p.S)
+    GC.@preserve Z G _check(@abocall LIBABO.abo_paths_eval(p.ptr::Ptr{Cvoid}, Z::Ptr{Float64}, M::Int64, d::Int32, 0::Int32, 0::Int64,
+                                                            G::Ptr{Float64}, 0::Int32, C_NULL::Ptr{Float64}, C_NULL::Ptr{Int64},
+                                                            0::Int32)::Int32)
+    G
+end
+
+# per path the k candidates with the smallest g_s, in the acquisition stage's order on −g_s: (values k × S, 1-based indices k × S;
+# 0 where the set holds fewer than k candidates).  A candidate excluded from a resident grid is never returned before the others.
+function path_argmin(p::HipSamplePaths, zs::AbstractVector; k::Int=1)
+    Z = _pack(zs); d, M = size(Z); v = Matrix{Float64}(undef, k, p.S); idx = Matrix{Int64}(undef, k, p.S)
+    GC.@preserve Z v idx _check(@abocall LIBABO.abo_paths_eval(p.ptr::Ptr{Cvoid}, Z::Ptr{Float64}, M::Int64, d::Int32, 0::Int32, 0::Int64,
+                                                                C_NULL::Ptr{Float64}, Int32(k)::Int32, v::Ptr{Float64}, idx::Ptr{Int64},
+                                                                0::Int32)::Int32)
+    v, idx .+ 1
+end
+function path_argmin(p::HipSamplePaths, c::HipCandidates; k::Int=1)
+    c.multi && error("path_argmin: sample paths run on one device (abo_paths_eval_cand); this grid is sharded")
+    v = Matrix{Float64}(undef, k, p.S); idx = Matrix{Int64}(undef, k, p.S)
+    GC.@preserve v idx _check(@abocall LIBABO.abo_paths_eval_cand(p.ptr::Ptr{Cvoid}, c.ptr::Ptr{Cvoid}, 0::Int64, C_NULL::Ptr{Float64},
+                                                                   Int32(k)::Int32, v::Ptr{Float64}, idx::Ptr{Int64}, 0::Int32)::Int32)
+    v, idx .+ 1
+end
+
+# path s takes its best index not taken by paths 1 … s − 1 (idx: k × q orderings, 0 = no candidate)
+function _distinct_picks(idx::AbstractMatrix{Int64})
+    picks = Int64[]
+    for s in axes(idx, 2)
+        j = findfirst(i -> i > 0 && !(i in picks), view(idx, :, s))
+        j === nothing && error("thompson_batch: path $s has no candidate left that earlier paths did not take")
+        push!(picks, idx[j, s])
+    end
+    picks
+end
+
+# q DISTINCT candidates (1-based indices into zs, or into the resident grid): the arg-mins of q independent sample paths
+function thompson_batch(m::HipStandardGP, zs_or_cands, q::Int; R::Int=1024, rng=Random.default_rng())
+    p = sample_paths(m, q; R=R, rng=rng)
+    _, idx = path_argmin(p, zs_or_cands; k=q)
+    _distinct_picks(idx)
 end
