@@ -17,7 +17,7 @@ from .multigpu import HipShardedGP, HipShardedGradientGP, ShardedCandidates
 from .kernels import (ApproxMatern52Kernel, ApproxMatern72Kernel, ConstMean, Kernel, Matern32Kernel, Matern52Kernel,
                       ScaledKernel, SqExponentialKernel, ZeroMean, with_lengthscale)
 from . import surrogate as _s
-from .thompson import SamplePaths, sample_paths, spectral_frequencies, thompson_batch
+from .thompson import SamplePaths, sample_paths, spectral_frequencies, thompson_batch, thompson_step
 from .surrogate import (AbstractSurrogate, HipStandardGP, _get_minimum, _update_model_parameters,
                         get_factor, get_kernel_constructor, get_lengthscale, get_mean_std, get_scale, mean_and_var,
                         nlml, nlml_fitted, nlml_ls, posterior_mean, posterior_var, prep_input, prep_output,

@@ -23,7 +23,8 @@ EXPORTS = ["abo_create", "abo_set_contraction", "abo_create_grad", "abo_predict_
            "abo_set_qei_block", "abo_cand_qei", "abo_cand_qei_begin", "abo_cand_qei_top", "abo_cand_qei_block", "abo_cand_qei_pick",
            "abo_cand_qei_end", "abo_cand_qei_has", "abo_cand_qei_stats", "abo_mgpu_cand_qei_stats", "abo_cand_qei_eligible", "abo_fill_distance",
            "abo_update", "abo_mgpu_update", "abo_cand_qei_mc",
-           "abo_paths_create", "abo_paths_destroy", "abo_paths_eval", "abo_paths_eval_cand", "abo_paths_stats_get"]
+           "abo_paths_create", "abo_paths_destroy", "abo_paths_eval", "abo_paths_eval_cand", "abo_paths_stats_get",
+           "abo_paths_append", "abo_paths_attach", "abo_paths_detach", "abo_paths_top", "abo_paths_values", "abo_paths_append_stats_get"]
 TEST_EXPORTS = ["abo_test_gemm_nt", "abo_test_kappa", "abo_test_oz_plan", "abo_test_oz_contract", "abo_test_acq_grad",
                 "abo_test_acq_grad_terms"]
 ABI_VERSION = 7
@@ -68,6 +69,15 @@ class AboPathsStats(C.Structure):
     """times and sizes of a sample-path object's last create / eval (include/abo_hip.h: abo_paths_stats)"""
     _fields_ = [("create_ms", C.c_double), ("eval_ms", C.c_double), ("eval_flop", C.c_double), ("S", C.c_int64), ("R", C.c_int64),
                 ("N", C.c_int64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class AboPathsAppendStats(C.Structure):
+    """the last abo_paths_append of a sample-path object (include/abo_hip.h: abo_paths_append_stats)"""
+    _fields_ = [("model_ms", C.c_double), ("resident_ms", C.c_double), ("resident_bytes", C.c_double), ("column_from_chain", C.c_int64),
+                ("appends", C.c_int64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -202,6 +212,12 @@ def lib():
     L.abo_paths_eval.argtypes = [vp, vp, i64, i32, i32, i64, vp, i32, vp, vp, i32]
     L.abo_paths_eval_cand.argtypes = [vp, vp, i64, vp, i32, vp, vp, i32]
     L.abo_paths_stats_get.argtypes = [vp, C.POINTER(AboPathsStats)]
+    L.abo_paths_append.argtypes = [vp, vp, vp, i32]
+    L.abo_paths_attach.argtypes = [vp, vp]
+    L.abo_paths_detach.argtypes = [vp]
+    L.abo_paths_top.argtypes = [vp, i64, i32, vp, vp, i32]
+    L.abo_paths_values.argtypes = [vp, vp, i32]
+    L.abo_paths_append_stats_get.argtypes = [vp, C.POINTER(AboPathsAppendStats)]
     L.abo_refine.argtypes = [vp, i32, f64, f64, vp, vp, i32, vp, i32, C.POINTER(AboRefineOpts), vp, vp, vp]
     L.abo_optimize_acquisition.argtypes = [vp, i32, f64, f64, vp, vp, i32, i64, i32, C.c_uint64, C.POINTER(AboRefineOpts),
                                            vp, C.POINTER(f64), vp, vp, vp, vp]

@@ -85,6 +85,16 @@ const double* cand_mu(const abo_cand* c);          // device, [M]
 int64_t cand_size(const abo_cand* c);
 int cand_dim(const abo_cand* c);
 int cand_device(const abo_cand* c);
+// ---- what the advancing sample paths (paths.hip: abo_paths_append) read of an appended model and of a down-dated set
+struct CandSync { uint64_t gen; int64_t N; uint64_t mu_epoch; };   // the factor (id, rows) the set is in sync with; mu_epoch grows
+void cand_sync(const abo_cand* c, CandSync* out);                  // whenever the set's exclusions may have changed
+// the bordered append that made g (false: g is not a one-row abo_append of a standard GP): vext = [−u; 1; 0 …] with
+// u = K̃⁻¹k(X, x*) (device, ≥ N entries), s2 = the pivot l_nn², serial = process-wide id of that append
+struct AppendView { const double* vext; double s2; uint64_t serial; };
+bool gp_append_view(abo_gp* g, AppendView* out);
+// the down-date column c(z) over the set, which must be in sync with g: *route 0 = left in place by abo_cand_downdate's pass,
+// 1 = the set's chain entry, 2 = recomputed into tmp (device, pad_up(M, 16) doubles)
+int32_t cand_downdate_column(abo_gp* g, abo_cand* c, double* tmp, const double** col, int* route);
 
 // ---- abo_update / abo_mgpu_update (update.hip): what they read of a handle, and the append / pool / wait machinery of api.hip
 struct GpState {

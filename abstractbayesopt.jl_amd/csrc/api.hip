@@ -262,6 +262,7 @@ struct ScratchBuf {
 };
 
 std::atomic<uint64_t> g_storage_gen{1};
+std::atomic<uint64_t> g_append_serial{1};
 
 // contraction engine of the posterior variance: process default (ABO_CONTRACTION = auto | fp64 | int8 | int8:<moduli>),
 // overridable per handle (abo_set_contraction)
@@ -351,6 +352,7 @@ struct abo_gp {
     // bordered-append bookkeeping (valid when this view was produced by abo_append)
     bool from_append = false;
     double ap_s2 = 0.0, ap_beta = 0.0; // Schur complement l_nn² and (y* − μ(x*))/l_nn²
+    uint64_t ap_serial = 0;            // process-wide id of the append that made this view (never reused): what a down-date column is tagged with
     std::vector<double> ap_x;          // the point a one-row append added, as the host handed it over (abo_cand_downdate matches it against the q-EI chain)
     double ap_s2v[MAX_P] = {0}, ap_betav[MAX_P] = {0};   // gradient-enhanced append: the same per appended row (p_out of them)
     DevBuf alpha, vext, tvec, T, info, scal;
@@ -423,6 +425,11 @@ struct abo_cand {
     int64_t synced_N = -1;
     uint64_t bak_gen = 0;                 // abo_cand_save snapshot
     int64_t bak_N = -1;
+    // the last one-row abo_cand_downdate: the append it served (abo_gp::ap_serial) and where it left the column c(z) — 0: cdot (which
+    // nothing else writes), 1: entry dd_chain of the chain.  The resident sample-path values (paths.hip) read the column there.
+    uint64_t dd_serial = 0;
+    int dd_src = -1, dd_chain = -1;
+    uint64_t mu_epoch = 1;                // grows whenever the stored μ — and with it the exclusions — may have changed other than by a down-date
     DevBuf Z, mu, var, score, cdot, tk_keys0, tk_keys1, tk_idx0, tk_idx1, top_val, top_idx, mu_bak, var_bak;
     // resident K_ZX (candidate-major, kzx_ld doubles per candidate, column k = training row k of synced_st): kept when
     // it fits the budget (ABO_CAND_KZX_GIB, default 64), so that a down-date streams it once instead of re-evaluating
@@ -1270,6 +1277,7 @@ int32_t append_impl(abo_gp* g, abo_gp* n, const double* x, double y, int64_t* in
     n->tm.append_trmv_ms = timed ? ev_ms(n->evs()[EV_BASE], n->evs()[EV_BASE + 1]) : 0.0;
     n->tm.append_trmv_bytes = 8.0 * (double)N * (double)N;
     n->ap_s2 = sc[0]; n->ap_beta = sc[1];
+    n->ap_serial = g_append_serial.fetch_add(1);
     n->ap_x.assign(x, x + d);
     n->logdet = g->logdet + 2.0 * std::log(sc[2]);
     n->quad = g->quad + sc[1] * sc[1] * sc[0];
@@ -1988,6 +1996,7 @@ static int32_t cand_topk(abo_gp* g, abo_cand* c, const double* sc_d, int32_t k, 
 }
 
 int32_t abo_cand_refresh(abo_gp* g, abo_cand* c) {
+    if (c) ++c->mu_epoch;                                  // (the resident sample-path selection re-reads the exclusions)
     if (!c) return fail(ABO_EINVAL, "abo_cand_refresh: null candidate set");
     int32_t rc = check_fitted(g, c->d);
     if (rc) return rc;
@@ -2153,6 +2162,9 @@ int32_t abo_cand_downdate(abo_gp* g, abo_cand* c) {
         pass_ms = ev_ms(g->evs()[5], g->evs()[6]);
         g->tm.downdate_ms = pass_ms;
         g->tm.downdate_bytes = (resident && chain_i < 0) ? 8.0 * (double)g->N * (double)c->M * P : 0.0;
+        c->dd_serial = P == 1 ? g->ap_serial : 0;
+        c->dd_src = chain_i >= 0 ? 1 : 0;
+        c->dd_chain = chain_i;
     }
     c->synced_N = g->N;
     return ABO_OK;
@@ -2444,6 +2456,7 @@ int32_t abo::qei_has(const abo_cand* c, int64_t gidx) { return c && qei_find_slo
 // s = var_x + σ²_n (var_x: the stored σ² at the pick, from the winner's record), γ_i = cx[i]/s_i (cx: c_1(x) … c_n(x) from the same
 // record).  s ≤ 0 is what the plain loop's bordered append reports as a failed pivot: ABO_ENOTPD, *info = N + n + 1.
 int32_t abo::qei_pick(abo_gp* g, abo_cand* c, int64_t gidx, double var_x, const double* cx, int n, int64_t excl, int64_t* info) {
+    if (c) ++c->mu_epoch;                                  // (the resident sample-path selection re-reads the exclusions)
     if (info) *info = 0;
     if (!g || !c || (n > 0 && !cx)) return fail(ABO_EINVAL, "abo_cand_qei_pick: null argument");
     abo_cand::Qei& Q = c->qei;
@@ -2483,6 +2496,7 @@ int32_t abo::qei_pick(abo_gp* g, abo_cand* c, int64_t gidx, double var_x, const 
 }
 
 int32_t abo::qei_end(abo_gp* g, abo_cand* c) {
+    if (c) ++c->mu_epoch;                                  // (the resident sample-path selection re-reads the exclusions)
     if (!g || !c) return fail(ABO_EINVAL, "abo_cand_qei_end: null argument");
     if (!c->qei.open) return ABO_OK;
     HIPCHK(hipSetDevice(g->prm.device));
@@ -2541,6 +2555,7 @@ static int32_t qei_build_block(const abo::QeiShards& S, double xi, double best_y
 // abstractbayesopt.jl_amd/incremental.py drives — are compared with this in tests/test_gpu_incremental.py).
 static int32_t qei_drive_device(abo_gp* g, abo_cand* c, int q, double xi, double best_y, int distinct, int T, int64_t idx_base,
                                 double* x_out, int64_t* idx_out, double* ei_out, int64_t* info) {
+    if (c) ++c->mu_epoch;                                  // (the resident sample-path selection re-reads the exclusions)
     if (T <= 0) T = qei_default_block();
     if (T > QEI_MAXT) T = QEI_MAXT;
     const int d = c->d;
@@ -2699,6 +2714,7 @@ int32_t abo::qei_drive(const QeiShards& S, int q, double xi, double best_y, int 
 // The Monte-Carlo joint q-EI (qei_mc.hip) on the set's block state: the continuation rule of qei_begin, but the chain (real entries and
 // the last batch's fantasies) is only read, and another block size re-keys the ring instead of dropping the chain.
 int32_t abo::qei_mc_open(abo_gp* g, abo_cand* c, int q, int T, int64_t idx_base, QeiMcStats* keep) {
+    if (c) ++c->mu_epoch;                                  // (the resident sample-path selection re-reads the exclusions)
     int32_t rc = check_fitted(g, c->d);
     if (rc) return rc;
     if (g->p_out > 1) return fail(ABO_EINVAL, "abo_cand_qei_mc: gradient-enhanced models are not supported (a standard GP only)");
@@ -2733,6 +2749,7 @@ void abo::qei_mc_view(abo_cand* c, QeiMcView* v) {
 }
 
 void abo::qei_mc_close(abo_cand* c, const QeiMcStats& keep) {
+    if (c) ++c->mu_epoch;                                  // (the resident sample-path selection re-reads the exclusions)
     abo_cand::Qei& Q = c->qei;
     Q.open = false;
     Q.builds = keep.builds; Q.block_ms = keep.block_ms; Q.pass_ms = keep.pass_ms; Q.pass_bytes = keep.pass_bytes; Q.pass_flop = keep.pass_flop;
@@ -3118,6 +3135,46 @@ const double* abo::cand_mu(const abo_cand* c) { return c->mu.as<double>(); }
 int64_t abo::cand_size(const abo_cand* c) { return c->M; }
 int abo::cand_dim(const abo_cand* c) { return c->d; }
 int abo::cand_device(const abo_cand* c) { return c->device; }
+void abo::cand_sync(const abo_cand* c, CandSync* o) { *o = CandSync{c->synced_gen, c->synced_N, c->mu_epoch}; }
+bool abo::gp_append_view(abo_gp* g, AppendView* o) {
+    if (!g->fitted || !g->st || !g->from_append || g->p_out != 1 || !g->vext.p) return false;
+    *o = AppendView{g->vext.as<double>(), g->ap_s2, g->ap_serial};
+    return true;
+}
+// c(z) = k(z, x*) − k(z, X)·u of the one-row append that made `g`, over the set (in sync with g): where the down-date left it when that
+// can be said with certainty, else recomputed into tmp [pad_up(M, 16)] with the down-date's own kernels.  Queued on g's stream.
+int32_t abo::cand_downdate_column(abo_gp* g, abo_cand* c, double* tmp, const double** col, int* route) {
+    const abo_cand::Qei& Q = c->qei;
+    if (c->dd_serial != 0 && c->dd_serial == g->ap_serial) {
+        if (c->dd_src == 0 && c->cdot.p) { *col = c->cdot.as<double>(); *route = 0; return ABO_OK; }
+        const int i = c->dd_chain;
+        if (c->dd_src == 1 && i >= 0 && i < Q.nreal && Q.gen == g->st->gen && Q.N + i == g->N - 1 && c->qchain.p && (int)g->ap_x.size() == g->d &&
+            (size_t)(i + 1) * g->d <= Q.chain_x.size() && !memcmp(g->ap_x.data(), &Q.chain_x[(size_t)i * g->d], sizeof(double) * g->d)) {
+            *col = c->qchain.as<double>() + (size_t)i * Q.Mp; *route = 1;
+            return ABO_OK;
+        }
+    }
+    hipStream_t s = g->stream;
+    const int64_t Rq = g->N - 1;
+    const double* vext = g->vext.as<double>();
+    if (c->kzx_ld > 0 && c->kzx_ld == g->st->cap) {
+        // (the set is in sync with g: column Rq of the resident K_ZX is the appended row's)
+        HIPCHK(launch_cand_gemv(c->Kzx.as<double>(), c->kzx_ld, vext, (int)(Rq + 1), c->M, tmp, s));
+    } else {
+        const int64_t step = 65536;
+        for (int64_t j0 = 0; j0 < c->M; j0 += step) {
+            const int64_t m = (c->M - j0) < step ? (c->M - j0) : step;
+            KgenArgs ka{};
+            ka.Xs = g->st->Xs.as<double>(); ka.Z = c->Z.as<double>(); ka.alpha = vext; ka.Kout = nullptr;
+            ka.mu = tmp + j0; ka.ldk = 0; ka.M = c->M; ka.j0 = j0; ka.Mc = (int)pad_up(m, 16);
+            ka.N = (int)(Rq + 1); ka.Np = (int)pad_up(Rq + 1, TB); ka.d = g->d; ka.dp = g->dp; ka.family = g->prm.family;
+            ka.s = 1.0 / g->prm.ell; ka.sigma_f2 = g->prm.sigma_f2; ka.mean_c = 0.0;
+            HIPCHK(launch_kgen(ka, s));
+        }
+    }
+    *col = tmp; *route = 2;
+    return ABO_OK;
+}
 int32_t abo::set_error(int32_t code, const char* text) { return fail(code, "%s", text); }
 const char* abo::last_error_text() { return g_err; }
 
@@ -3173,6 +3230,7 @@ int32_t abo_cand_save(abo_gp* g, abo_cand* c) {
 }
 
 int32_t abo_cand_restore(abo_gp* g, abo_cand* c) {
+    if (c) ++c->mu_epoch;                                  // (the resident sample-path selection re-reads the exclusions)
     if (!g || !c) return fail(ABO_EINVAL, "abo_cand_restore: null argument");
     if (c->bak_N < 0) return fail(ABO_EINVAL, "abo_cand_restore: nothing saved");
     HIPCHK(hipSetDevice(g->prm.device));
@@ -3207,6 +3265,7 @@ int32_t abo_cand_point(abo_gp* g, abo_cand* c, int64_t idx, double* x, double* m
 }
 
 int32_t abo_cand_exclude(abo_gp* g, abo_cand* c, int64_t idx) {
+    if (c) ++c->mu_epoch;                                  // (the resident sample-path selection re-reads the exclusions)
     if (!g || !c) return fail(ABO_EINVAL, "abo_cand_exclude: null argument");
     if (idx < 0 || idx >= c->M) return fail(ABO_EINVAL, "abo_cand_exclude: index %lld outside 0..%lld", (long long)idx, (long long)c->M - 1);
     HIPCHK(hipSetDevice(g->prm.device));
@@ -3279,6 +3338,7 @@ int32_t abo_cand_qei_stats(abo_gp* g, abo_cand* c, abo_qei_stats* out) {
 // loop does per device)
 static int32_t qei_plain(abo_gp* g, abo_cand* c, int q, double xi, double best_y, int distinct, int64_t idx_base, double* x_out,
                          int64_t* idx_out, double* ei_out, int64_t* info) {
+    if (c) ++c->mu_epoch;                                  // (the resident sample-path selection re-reads the exclusions)
     int32_t rc = check_fitted(g, c->d);
     if (rc) return rc;
     if (g->st->gen != c->synced_gen || g->N != c->synced_N)

@@ -82,6 +82,7 @@ class SamplePaths:
         _lib.check(_lib.lib().abo_paths_create(model._require(), self.S, self.R, self.omega.ctypes.data, self.phase.ctypes.data,
                                                self.w.ctypes.data, self.eps.ctypes.data, HOST, C.byref(hp)))
         self._h = _PathsHandle(hp.value)
+        self._set = None
 
     def _eval(self, Z, want_values, k, idx_base=0):
         L, S, k = _lib.lib(), self.S, int(k)
@@ -124,6 +125,70 @@ class SamplePaths:
         _lib.check(_lib.lib().abo_paths_stats_get(self._h.ptr, C.byref(st)))
         return st.as_dict()
 
+    # ---- following the model through appends (include/abo_hip.h: abo_paths_append …) ----
+    def append(self, model2, eps_new=None, rng=None):
+        """Advance the paths IN PLACE to `model2`, the one-point append of the model they describe (incremental.append): one fresh
+        N(0,1) draw per path (`eps_new`, S values; drawn from `rng` when not given) joins `eps` as its last column, so that
+        SamplePaths(model2, omega, phase, w, eps) restates the advanced paths.  With a set attached, the set must have been
+        down-dated to `model2` first.  The advanced paths share their prior draw with the paths before: successive steps' paths are not
+        independent draws.  Returns self."""
+        if hasattr(model2, "devices") or not isinstance(model2, HipStandardGP):
+            raise TypeError(f"SamplePaths.append needs the appended HipStandardGP, not {type(model2).__name__}")
+        if eps_new is None:
+            eps_new = _rng(rng).standard_normal(self.S)
+        e = np.ascontiguousarray(eps_new, dtype=np.float64).reshape(-1)
+        if e.shape != (self.S,):
+            raise ValueError(f"SamplePaths.append: eps_new holds {e.shape[0]} values, the object has S = {self.S} paths")
+        if not np.all(np.isfinite(e)):
+            raise ValueError("SamplePaths.append: eps_new is not finite")
+        _lib.check(_lib.lib().abo_paths_append(self._h.ptr, model2._require(), e.ctypes.data, HOST))
+        self.eps = np.ascontiguousarray(np.concatenate([self.eps, e[:, None]], axis=1))     # (only after the library accepted the step)
+        self.model = model2
+        return self
+
+    def attach(self, cand_set):
+        """keep g_s(z_j) of every candidate of a ResidentCandidates set on the device (S × M doubles); the caller keeps the set alive
+        while it is attached (the object holds a Python reference as well).  One set per object."""
+        if not _is_resident(cand_set):
+            raise TypeError(f"SamplePaths.attach needs a ResidentCandidates set, not {type(cand_set).__name__}")
+        if getattr(self, "_set", None) is not None:
+            raise ValueError("SamplePaths.attach: a set is attached already (detach() first)")
+        _lib.check(_lib.lib().abo_paths_attach(self._h.ptr, cand_set._h.ptr))
+        self._set = cand_set
+        return self
+
+    def detach(self):
+        _lib.check(_lib.lib().abo_paths_detach(self._h.ptr))
+        self._set = None
+
+    def _attached(self, what):
+        cs = getattr(self, "_set", None)
+        if cs is None:
+            raise ValueError(f"SamplePaths.{what}: no candidate set is attached (attach() first)")
+        return cs
+
+    def top(self, k: int = 1, idx_base: int = 0):
+        """per path the k attached candidates with the smallest resident g_s: (values (S, k), indices (S, k)); k = 1 costs no pass"""
+        k = int(k)
+        if k < 1:
+            raise ValueError(f"top: k = {k}")
+        self._attached("top")
+        tv, ti = np.empty((self.S, k)), np.empty((self.S, k), dtype=np.int64)
+        _lib.check(_lib.lib().abo_paths_top(self._h.ptr, int(idx_base), k, tv.ctypes.data, ti.ctypes.data, HOST))
+        return tv, ti
+
+    def values(self) -> np.ndarray:
+        """the resident values (S, M); +Inf at excluded candidates"""
+        cs = self._attached("values")
+        out = np.empty((self.S, cs.M))
+        _lib.check(_lib.lib().abo_paths_values(self._h.ptr, out.ctypes.data, HOST))
+        return out
+
+    def append_stats(self) -> dict:
+        st = _lib.AboPathsAppendStats()
+        _lib.check(_lib.lib().abo_paths_append_stats_get(self._h.ptr, C.byref(st)))
+        return st.as_dict()
+
 
 def draw_base(kernel, S: int, R: int, N: int, d: int, rng=None):
     """the four base arrays of S paths in R features for a model of N points in d dimensions: (omega, phase, w, eps)"""
@@ -150,6 +215,21 @@ def sample_paths(model, S: int, R: int = 1024, rng=None) -> SamplePaths:
         raise TypeError(f"sample_paths needs a HipStandardGP, not {type(model).__name__}")
     N, d = _model_shape(model)
     return SamplePaths(model, *draw_base(model.kernel, int(S), int(R), N, d, rng))
+
+
+def thompson_step(paths: SamplePaths, model2, cand_set, eps_new=None, rng=None, idx_base: int = 0):
+    """One incremental Thompson step after `model2 = append(model, x, y)`: down-date the resident set to model2 (unless it is there
+    already), advance the paths and their resident values, and return each path's arg-min (values (S,), indices (S,)).  The set is
+    attached on first use."""
+    if getattr(paths, "_set", None) is None:
+        paths.attach(cand_set)
+    elif paths._set is not cand_set:
+        raise ValueError("thompson_step: the paths are attached to another candidate set")
+    if cand_set.model is not model2:
+        cand_set.downdate(model2)
+    paths.append(model2, eps_new, rng)
+    tv, ti = paths.top(1, idx_base)
+    return tv[:, 0], ti[:, 0]
 
 
 def distinct_picks(top_idx) -> np.ndarray:

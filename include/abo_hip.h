@@ -44,7 +44,9 @@ extern "C" {
                                   blocks left the shipped library (test build only: ABO_TEST_HOOKS)
                                added within ABI 7 (backwards-compatible, no struct changed): abo_update, abo_mgpu_update,
                                   ABO_UPDATE_SHARED / _APPENDED / _REFIT; abo_cand_qei_mc; abo_paths_create, abo_paths_destroy,
-                                  abo_paths_eval, abo_paths_eval_cand, abo_paths_stats_get (struct abo_paths_stats is new) */
+                                  abo_paths_eval, abo_paths_eval_cand, abo_paths_stats_get (struct abo_paths_stats is new); abo_paths_append,
+                                  abo_paths_attach, abo_paths_detach, abo_paths_top, abo_paths_values, abo_paths_append_stats_get
+                                  (struct abo_paths_append_stats is new) */
 
 /* status codes */
 enum {
@@ -495,6 +497,56 @@ int32_t abo_paths_eval(void* paths, const double* Z, int64_t M, int32_t d, int32
 int32_t abo_paths_eval_cand(void* paths, abo_cand* c, int64_t idx_base, double* values, int32_t k, double* top_val,
                             int64_t* top_idx, int32_t out_space);
 int32_t abo_paths_stats_get(void* paths, abo_paths_stats* out);
+
+/* --- sample paths that FOLLOW the model through appends (added within ABI 7) ---------------------------------------------------
+ * Pathwise conditioning has the structure of the bordered append.  With the new observation (x*, y*), u = K̃⁻¹k(X, x*),
+ * s² = k(x*,x*) + σ²_n − k(X,x*)ᵀu (the append's pivot l_nn²) and ONE fresh N(0,1) draw ε*_s per path:
+ *     a_s     = (y* − sqrt(σ²_n)·ε*_s − g_s(x*)) / s²          g_s(x*): the path BEFORE the append, at the new point
+ *     v'_s    = [ v_s − a_s·u ;  a_s ]                          (N + 1 values per path)
+ *     g'_s(z) = g_s(z) + a_s·c(z),   c(z) = k(z, x*) − k(z, X)·u
+ * g'_s is the path abo_paths_create would build on the appended model from the same (omega, phase, w) and eps extended by the column
+ * ε* — the block-inverse identity, nothing approximate.  u and s² are what abo_append left with the new handle, c(z) over a resident
+ * set is the column abo_cand_downdate used: an append costs O((N + R)·S) for the object and O(M·S) for S resident values per
+ * candidate, with no triangular mat-vec and no pass over the factor.
+ * The advanced paths are exact posterior draws under the appended model, but they share their prior draw (omega, phase, w) with the
+ * paths before the append — successive BO steps' paths are not independent of each other; a caller who wants fresh draws calls
+ * abo_paths_create at its own cadence.
+ *   abo_paths_append   advances the object IN PLACE from its model to gp2, which must be the ONE-point append of that model made by
+ *                      abo_append: same factor storage, N(gp2) = N(paths) + 1.  A refit in disguise (the append fell back to a refit —
+ *                      storage full or copy-on-write —, abo_fit), a handle more than one append ahead, another lineage, a
+ *                      gradient-enhanced handle: ABO_EINVAL with the reason in abo_last_error, the object untouched.  k appends are k
+ *                      calls, in append order.  eps_new: S doubles in `space` (a non-finite host value: ABO_EINVAL).  Every check comes
+ *                      before any device work.  On success the object describes gp2: it retains gp2 and releases the old model (the
+ *                      caller may abo_destroy its references to both), and abo_paths_eval / _eval_cand evaluate paths of the
+ *                      appended model.  g_s(x*) is summed in a fixed order (no atomics): the same inputs give the same bits.
+ *                      With a set attached (below) the set must be in sync with gp2 — abo_cand_downdate(gp2, c) has run; else
+ *                      ABO_EINVAL, nothing changed — and the resident values follow: G[s][j] += a_s·c(z_j), in one launch that also
+ *                      leaves each path's arg-min.  c(z) is read where the down-date left it (its pass's result, or the entry of the
+ *                      set's q-EI chain it was served from) when that is certain, and recomputed with the down-date's own kernels
+ *                      otherwise; a stale column is never used.
+ *   abo_paths_attach   evaluates G[s][j] = g_s(z_j) over the set's candidates (the pass of abo_paths_eval_cand) and KEEPS it with the
+ *                      object: S × M doubles of device memory (M rounded up to 1024); ABO_ENOMEM leaves the object unattached.  One
+ *                      set per object (a second attach: ABO_EINVAL).  The object remembers the set but does not own it: the CALLER
+ *                      keeps the set alive while it is attached; abo_paths_detach / abo_paths_destroy drop the values.
+ *   abo_paths_top      selection over the resident values, the output contract of abo_paths_eval: top_val / top_idx are S × k in
+ *                      out_space, per path the k candidates with the smallest g_s in abo_acq's order on −g_s (ties → lowest index,
+ *                      NaN first, tail (NaN, −1) when M < k), top_idx = idx_base + j, top_val the bits of abo_paths_values at that
+ *                      index.  A candidate taken out by abo_cand_exclude (stored μ = +Inf) counts as g = +Inf; exclusions are read
+ *                      when the selection runs, not at attach time.  k = 1 returns what the fused reduction left after the last
+ *                      attach / append without a further pass, unless the set's exclusions may have changed since (then the selection
+ *                      alone is re-run); k > 1 is one abo_acq selection per path.
+ *   abo_paths_values   the resident values, S × M path-major (values[s·M + j]), +Inf at excluded candidates.
+ *   abo_paths_append_stats_get  the last abo_paths_append: HIP-event ms of (path values at x* + update of v) and of (column look-up or
+ *                      recomputation + resident update + selection; 0 without a set), the algorithmic bytes 16·S·M + 8·M of the
+ *                      latter, where the column came from (0: the down-date's pass, 1: the q-EI chain, 2: recomputed, −1: no set
+ *                      or an empty one) and the number of appends the object has followed. */
+typedef struct abo_paths_append_stats { double model_ms, resident_ms, resident_bytes; int64_t column_from_chain, appends; } abo_paths_append_stats;
+int32_t abo_paths_append(void* paths, abo_gp* gp2, const double* eps_new, int32_t space);
+int32_t abo_paths_attach(void* paths, abo_cand* c);
+int32_t abo_paths_detach(void* paths);
+int32_t abo_paths_top(void* paths, int64_t idx_base, int32_t k, double* top_val, int64_t* top_idx, int32_t out_space);
+int32_t abo_paths_values(void* paths, double* values, int32_t out_space);
+int32_t abo_paths_append_stats_get(void* paths, abo_paths_append_stats* out);
 
 /* --- grid generation and stand-alone epilogue (DEVICE buffers) --------------------------------------
  * abo_lhs: points j0 .. j0+count−1 of an n-point Latin-hypercube design in the box [lower, upper]

@@ -561,6 +561,9 @@ function path_argmin(p::HipSamplePaths, c::HipCandidates; k::Int=1)
     v, idx .+ 1
 end
 
+# the paths that follow the model through appends (abo_paths_append …) live in a file of their own
+include("ThompsonAppend.jl")
+
 # path s takes its best index not taken by paths 1 … s − 1 (idx: k × q orderings, 0 = no candidate)
 function _distinct_picks(idx::AbstractMatrix{Int64})
     picks = Int64[]
