@@ -14,7 +14,7 @@ HOST, DEVICE = 0, 1
 
 EXPORTS = ["abo_create", "abo_set_contraction", "abo_create_grad", "abo_predict_grad", "abo_predict_grad_cov", "abo_retain", "abo_destroy", "abo_fit", "abo_append", "abo_append_grad", "abo_cand_create", "abo_cand_destroy",
            "abo_cand_refresh", "abo_cand_downdate", "abo_cand_save", "abo_cand_restore", "abo_cand_acq", "abo_cand_get", "abo_cand_point", "abo_cand_exclude", "abo_predict", "abo_acq", "abo_nlml", "abo_nlml_grad", "abo_lhs", "abo_score",
-           "abo_get_factor", "abo_get_n", "abo_get_data", "abo_get_timings", "abo_last_error", "abo_abi_version", "abo_pool_trim",
+           "abo_get_factor", "abo_get_n", "abo_get_data", "abo_get_timings", "abo_get_prune_stats", "abo_last_error", "abo_abi_version", "abo_pool_trim",
            "abo_mgpu_create", "abo_mgpu_clone", "abo_mgpu_destroy", "abo_mgpu_info", "abo_mgpu_get", "abo_mgpu_fit",
            "abo_mgpu_predict", "abo_mgpu_acq", "abo_mgpu_acq_lhs", "abo_mgpu_append", "abo_mgpu_cand_create",
            "abo_mgpu_cand_create_lhs", "abo_mgpu_cand_refresh", "abo_mgpu_cand_destroy", "abo_mgpu_cand_acq",
@@ -26,7 +26,7 @@ EXPORTS = ["abo_create", "abo_set_contraction", "abo_create_grad", "abo_predict_
            "abo_paths_create", "abo_paths_destroy", "abo_paths_eval", "abo_paths_eval_cand", "abo_paths_stats_get",
            "abo_paths_append", "abo_paths_attach", "abo_paths_detach", "abo_paths_top", "abo_paths_values", "abo_paths_append_stats_get"]
 TEST_EXPORTS = ["abo_test_gemm_nt", "abo_test_kappa", "abo_test_oz_plan", "abo_test_oz_contract", "abo_test_acq_grad",
-                "abo_test_acq_grad_terms"]
+                "abo_test_acq_grad_terms", "abo_test_prune_plan", "abo_test_prune_force", "abo_test_prune_bounds"]
 ABI_VERSION = 7
 CONTRACT_AUTO, CONTRACT_FP64, CONTRACT_INT8 = 0, 1, 2
 # what abo_update / abo_mgpu_update ran (include/abo_hip.h)
@@ -50,6 +50,15 @@ class AboTimings(C.Structure):
                [("refine_starts", C.c_int64), ("refine_evals", C.c_int64), ("downdate_from_chain", C.c_int64),
                 ("nlml_kinv_ms", C.c_double), ("nlml_trace_ms", C.c_double), ("append_trmv_ms", C.c_double),
                 ("append_trmv_bytes", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class AboPruneStats(C.Structure):
+    """the pruned top-k selection of the last abo_acq on a handle (include/abo_hip.h: abo_prune_stats)"""
+    _fields_ = [(n, C.c_int64) for n in ("pruned", "fallback", "bound_rows", "k0", "survivors")] + \
+               [(n, C.c_double) for n in ("bound_ms", "threshold_ms", "survivor_ms")]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -165,6 +174,11 @@ def lib():
     L.abo_get_n.argtypes = [vp, C.POINTER(i64), C.POINTER(i32)]
     L.abo_get_data.argtypes = [vp, vp, vp]
     L.abo_get_timings.argtypes = [vp, C.POINTER(AboTimings)]
+    L.abo_get_prune_stats.argtypes = [vp, C.POINTER(AboPruneStats)]
+    if hooks:
+        L.abo_test_prune_plan.argtypes = [i64, i64, i32, i32, i32, f64, i32, i32, i32, vp]
+        L.abo_test_prune_force.argtypes = [i32, i32]
+        L.abo_test_prune_bounds.argtypes = [vp, vp, i64]
     L.abo_last_error.argtypes = [C.c_char_p, C.c_size_t]
     L.abo_abi_version.argtypes = []
     L.abo_pool_trim.argtypes = [i32]

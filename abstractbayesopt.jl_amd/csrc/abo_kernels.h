@@ -99,6 +99,9 @@ struct OzVarArgs {
     // image as well, and their column sums by 2^(2 ktg) on the way out.  rmode 0: every row is a function value.
     int rmode = 0, rper = 1;
     int64_t r0 = 0, rpts = 1;
+    // > 0: only the first rblocks 256-row blocks of W are contracted — partial[tb] for tb < 2·rblocks, the sum of squares over the
+    // first min(nvalid, 256·rblocks) rows of V, bit for bit what the full call writes there (the buffers keep their full layout)
+    int rblocks = 0;
     double* Vout = nullptr;     // when given: V = W.K_XZ itself, [Mc][ldv] fp64 (candidate-major), instead of the column sums of squares
     int64_t ldv = 0;
     hipEvent_t ev_quant = nullptr, ev_gemm = nullptr;   // optional: recorded after the quantisation / after the GEMM
@@ -136,6 +139,8 @@ struct KgenArgs {
     int* res_bad = nullptr;
     int res_n = 0, res_sK = 0;
     int res_ktg = 0;      // gradient-enhanced GP: derivative training rows and derivative candidate outputs each carry 2^-res_ktg on top
+    int res_kmax = 0;     // StandardGP: > 0 (a multiple of 128) = planes only for the training columns k < res_kmax (the rest is never read
+                          // by a contraction limited to the first res_kmax rows of the triangular W); 0 = all columns
 };
 // true when launch_kgen honours KgenArgs::res for this shape and n moduli (the fused output is instantiated for the default plan)
 inline bool kgen_writes_residues(const KgenArgs& a, int n) { return a.dp <= 32 && n == 14 && !a.dlogell; }
@@ -426,6 +431,18 @@ hipError_t launch_refine_lockstep_grad(const RefineArgs& a, int S, const double*
 hipError_t launch_acq_grad_via_eval(const RefineArgs& a, int S, const double* mean_g, void* work, const GradEval& ev, hipStream_t s);
 // out[j][0..d) = Z[idx[j] − idx_base][0..d) for j < k (zeros for idx[j] < 0): the coordinates of selected candidates
 hipError_t launch_gather_points(const double* Z, const int64_t* idx, int64_t idx_base, int k, int d, double* out, hipStream_t s);
+
+// ---- pruned top-k selection (misc.hip): candidates whose guarded upper bound reaches the threshold, compacted in index order ----------
+// Margins of the guard ub + |ub|·PRUNE_REL + PRUNE_ABS (derivation: misc.hip, prune_keep)
+constexpr double PRUNE_REL = 0x1p-30;
+constexpr double PRUNE_ABS = 0x1p-1022;
+constexpr int PRUNE_SCAN_E = 1024;       // candidates per workgroup of the compaction
+// sel[0 … *count) = the indices j < M, ascending, with !(guard(ub[j]) < *tau) — a NaN on either side keeps the candidate, as the
+// selection's order ranks NaN first; *count = their number.  blk: ⌈M / PRUNE_SCAN_E⌉ ints of scratch; sel: room for M entries.
+// Stream-ordered, no atomics: the same list on every run.
+hipError_t launch_prune_compact(const double* ub, int64_t M, const double* tau, int* blk, int64_t* sel, int64_t* count, hipStream_t s);
+// top_idx[e] = sel[top_idx[e]] + idx_base for e < k (−1 stays): positions in a compacted list back to candidate indices
+hipError_t launch_prune_map(int64_t* top_idx, int k, const int64_t* sel, int64_t idx_base, hipStream_t s);
 
 struct TopkWork {            // scratch sized by topk_workspace_entries()
     uint64_t* keys[2];

@@ -376,7 +376,12 @@ struct abo_gp {
     bool oz_prepare_pending = false;  // events 8/9 of the current call bracket a rebuild of the residue planes of W (read with its timings)
     uint64_t oz_gen = 0;
     int64_t oz_N = -1;
-    int64_t last_chunk = 0;          // candidates per chunk of the last posterior call (its events are read back with it)
+    // the posterior passes of the current call, in launch order (their per-chunk events are read back with them): the pruned top-k
+    // selection of abo_acq runs up to three, everything else one
+    struct PostPass { int64_t chunk0, nchunk, M, rows; };     // first chunk's event slot, chunks, candidate rows, rows of W contracted
+    std::vector<PostPass> passes;
+    DevBuf pr_ub, pr_z, pr_sc, pr_sel, pr_blk, pr_tv, pr_ti;   // pruned selection: bounds, gathered points, their scores, survivor list, scan scratch, threshold pairs
+    abo_prune_stats pst{};
     DevBuf oz_WR, oz_sexp, oz_badr, oz_KR, oz_U, oz_badc;
     abo_timings tm{};
 
@@ -386,14 +391,14 @@ struct abo_gp {
     void set_device(int dev) {
         DevBuf* all[] = {&alpha, &vext, &tvec, &T, &info, &scal, &Zdev, &Kxz, &partial, &mu_c, &mu_all, &var_all,
                          &score_all, &tk_keys0, &tk_keys1, &tk_idx0, &tk_idx1, &top_val, &top_idx,
-                         &oz_WR, &oz_sexp, &oz_badr, &oz_KR, &oz_U, &oz_badc};
+                         &oz_WR, &oz_sexp, &oz_badr, &oz_KR, &oz_U, &oz_badc, &pr_ub, &pr_z, &pr_sc, &pr_sel, &pr_blk, &pr_tv, &pr_ti};
         for (DevBuf* b : all) b->dev = dev;
     }
 
     void free_all() {
         DevBuf* all[] = {&alpha, &vext, &tvec, &T, &info, &scal, &Zdev, &Kxz, &partial, &mu_c, &mu_all, &var_all,
                          &score_all, &tk_keys0, &tk_keys1, &tk_idx0, &tk_idx1, &top_val, &top_idx,
-                         &oz_WR, &oz_sexp, &oz_badr, &oz_KR, &oz_U, &oz_badc};
+                         &oz_WR, &oz_sexp, &oz_badr, &oz_KR, &oz_U, &oz_badc, &pr_ub, &pr_z, &pr_sc, &pr_sel, &pr_blk, &pr_tv, &pr_ti};
         for (DevBuf* b : all) b->release();
         oz_N = -1;
         oz_ctr_clean = nullptr;
@@ -536,7 +541,7 @@ void fit_collect(abo_gp* g) {
     g->tm.fit_total_ms = ev_ms(g->evs()[0], g->evs()[4]);
 }
 
-constexpr size_t EV_BASE = 10;        // 0-4 fit phases, 5-7 acquisition call, 8-9 residue planes of W; from EV_BASE: per-chunk events of a
+constexpr size_t EV_BASE = 14;        // 0-4 fit phases, 5-7 acquisition call, 8-9 residue planes of W, 10-13 passes of the pruned selection; from EV_BASE: per-chunk events of a
                                       // posterior call, or (inside a fit) the strip events of the factorisation's look-ahead
 constexpr size_t EV_PER_CHUNK = 8;   // kgen 0-1, contraction 2-3, epilogue 4-5, int8 pipeline: end of quantisation 6, end of GEMM 7
 
@@ -843,9 +848,13 @@ int32_t oz_planes_of_w(abo_gp* g) {
 // unless point_major; mu/var/score arrays then have pc·M entries.
 // kstore / ldstore: write K_XZ into a caller-owned candidate-major matrix (pad_up(M,128) rows of ldstore ≥ Np doubles)
 // instead of the per-chunk scratch — the resident K_ZX of a candidate set.
+// rblocks > 0 (the bound pass of the pruned selection; int8 engine with generator-written planes only, else PRUNE_UNAVAILABLE):
+// the contraction covers the first rblocks 256-row blocks of W — var / score then come from σ²_R ≥ σ², μ from the full pass's code.
+// more: a further pass of the same call — its events and counts are kept next to those of the passes before it.
+constexpr int32_t PRUNE_UNAVAILABLE = -100;
 int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0, double best_y, double* mu_out,
                   double* var_out, double* score_out, int pc = 1, int point_major = 0, double* kstore = nullptr,
-                  int64_t ldstore = 0) {
+                  int64_t ldstore = 0, int rblocks = 0, bool more = false) {
     const int64_t M = Mpts * pc;                         // candidate rows
     hipStream_t s = g->stream;
     const int64_t Np = g->Np;
@@ -855,20 +864,25 @@ int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0
     bool oz = wants_int8(g, want_var, pc, &nm);
     int64_t Mc = pick_chunk(g, M, oz);
     { int32_t rc = oz_acquire(g, nm, M, &Mc, &oz); if (rc) return rc; }
-    g->last_chunk = Mc;
     {
         KgenArgs probe{};
         probe.pt = g->p_out; probe.dp = g->dp;
+        if (rblocks > 0 && !(oz && kgen_writes_residues(probe, nm) && !kstore && pc == 1)) return PRUNE_UNAVAILABLE;
         // the fp64 chunk of K_XZ is not materialised when the generator writes the residue planes itself
         if (!kstore && !(oz && kgen_writes_residues(probe, nm))) HIPCHK(g->Kxz.ensure(sizeof(double) * Mc * Np));
     }
     HIPCHK(g->partial.ensure(sizeof(double) * T * Mc));
     HIPCHK(g->mu_c.ensure(sizeof(double) * Mc));
     const int64_t nchunk = (M + Mc - 1) / Mc;
-    HIPCHK(g->events(EV_BASE + EV_PER_CHUNK * (size_t)nchunk));
-    g->tm.var_gemm_launches = 0;
-    g->oz_prepare_pending = false;
-    g->tm.oz_prepare_ms = 0.0;                                      // planes cached from an earlier call: nothing spent in this one
+    if (!more) {
+        g->passes.clear();
+        g->tm.var_gemm_launches = 0;
+        g->oz_prepare_pending = false;
+        g->tm.oz_prepare_ms = 0.0;                                  // planes cached from an earlier call: nothing spent in this one
+    }
+    const int64_t chunk0 = g->passes.empty() ? 0 : g->passes.back().chunk0 + g->passes.back().nchunk;
+    HIPCHK(g->events(EV_BASE + EV_PER_CHUNK * (size_t)(chunk0 + nchunk)));
+    g->passes.push_back({chunk0, nchunk, M, rblocks > 0 && (int64_t)256 * rblocks < g->N ? (int64_t)256 * rblocks : g->N});
     if (oz) { int32_t rc = oz_planes_of_w(g); if (rc) return rc; }
     g->tm.contraction_engine = want_var ? (oz ? ABO_CONTRACT_INT8 : ABO_CONTRACT_FP64) : 0;
     g->tm.oz_nmod = oz ? g->oz_plan.n : 0;
@@ -876,7 +890,7 @@ int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0
         const int64_t j0 = c * Mc;
         const int64_t m = (M - j0) < Mc ? (M - j0) : Mc;
         const int mcp = (int)pad_up(m, TB);
-        hipEvent_t* e = &g->evs()[EV_BASE + EV_PER_CHUNK * c];
+        hipEvent_t* e = &g->evs()[EV_BASE + EV_PER_CHUNK * (chunk0 + c)];
         KgenArgs ka{};
         double* kchunk = kstore ? kstore + j0 * ldstore : g->Kxz.as<double>();
         const int64_t ldk = kstore ? ldstore : Np;
@@ -897,6 +911,7 @@ int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0
             ka.res_bad = g->oz_badc.as<int>(); ka.res_n = g->oz_plan.n;
             ka.res_sK = oz_k_scale(g->p_out > 1 ? (pc > 1 ? 2.0 : 1.5) * g->prm.sigma_f2 : g->prm.sigma_f2);
             ka.res_ktg = oz_grad_exp(g);
+            ka.res_kmax = 256 * rblocks;
             if (!kstore) ka.Kout = nullptr;
         }
         PHASE_EVENT(e[0], s);
@@ -913,6 +928,7 @@ int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0
             oa.kper = g->p_out; oa.ktg = oz_grad_exp(g);
             if (pc > 1) { oa.rmode = point_major ? 1 : 2; oa.rper = pc; oa.r0 = j0; oa.rpts = Mpts; }
             oa.ev_quant = phase_events() ? e[6] : nullptr; oa.ev_gemm = phase_events() ? e[7] : nullptr; oa.planes_ready = fused ? 1 : 0;
+            oa.rblocks = rblocks;
             PHASE_EVENT(e[2], s);
             HIPCHK(launch_var_ozaki(oa, s));
             PHASE_EVENT(e[3], s);
@@ -929,7 +945,7 @@ int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0
         FinalizeArgs fa{};
         fa.partial = g->partial.as<double>(); fa.mu_in = g->mu_c.as<double>(); fa.mu_out = mu_out;
         fa.var_out = var_out; fa.score_out = score_out; fa.ldp = Mc; fa.j0 = j0; fa.M = M;
-        fa.T = (var_out || score_out) ? T : 0; fa.Mc = mcp; fa.kind = kind; fa.sigma_f2 = g->prm.sigma_f2;
+        fa.T = (var_out || score_out) ? (rblocks > 0 && 2 * rblocks < T ? 2 * rblocks : T) : 0; fa.Mc = mcp; fa.kind = kind; fa.sigma_f2 = g->prm.sigma_f2;
         fa.p0 = p0; fa.best_y = best_y;
         fa.prior_grad = grad_prior_var(g); fa.pc = pc; fa.point_major = point_major; fa.Mpts = Mpts;
         PHASE_EVENT(e[4], s);
@@ -1020,29 +1036,33 @@ int32_t grad_eval_device(abo_gp* g, const double* Zd, int64_t M, double beta, do
     return ABO_OK;
 }
 
-void collect_posterior_timings(abo_gp* g, int64_t M, bool with_var) {
-    const int64_t Mc = g->last_chunk;
-    const int64_t nchunk = (M + Mc - 1) / Mc;
-    double kx = 0, vg = 0, fi = 0, oq = 0, og = 0, oc = 0;
+// phase times and algorithmic work of the call's posterior passes (what was launched: a bound pass counts its R rows, a survivor pass
+// its survivors)
+void collect_posterior_timings(abo_gp* g, bool with_var) {
+    double kx = 0, vg = 0, fi = 0, oq = 0, og = 0, oc = 0, work = 0;
     const bool oz = with_var && g->tm.contraction_engine == ABO_CONTRACT_INT8;
-    for (int64_t c = 0; phase_events() && c < nchunk; ++c) {
-        hipEvent_t* e = &g->evs()[EV_BASE + EV_PER_CHUNK * c];
-        kx += ev_ms(e[0], e[1]);
-        if (with_var) vg += ev_ms(e[2], e[3]);
-        if (oz) { oq += ev_ms(e[2], e[6]); og += ev_ms(e[6], e[7]); oc += ev_ms(e[7], e[3]); }
-        fi += ev_ms(e[4], e[5]);
+    for (const abo_gp::PostPass& ps : g->passes) {
+        for (int64_t c = 0; phase_events() && c < ps.nchunk; ++c) {
+            hipEvent_t* e = &g->evs()[EV_BASE + EV_PER_CHUNK * (ps.chunk0 + c)];
+            kx += ev_ms(e[0], e[1]);
+            if (with_var) vg += ev_ms(e[2], e[3]);
+            if (oz) { oq += ev_ms(e[2], e[6]); og += ev_ms(e[6], e[7]); oc += ev_ms(e[7], e[3]); }
+            fi += ev_ms(e[4], e[5]);
+        }
+        work += (double)ps.rows * (double)ps.rows * (double)ps.M;
     }
     g->tm.acq_kxz_ms = kx;
     g->tm.acq_var_gemm_ms = vg;
     g->tm.acq_finalize_ms = fi;
     g->tm.oz_quant_ms = oq; g->tm.oz_gemm_ms = og; g->tm.oz_crt_ms = oc;
     if (g->oz_prepare_pending) { g->tm.oz_prepare_ms = phase_events() ? ev_ms(g->evs()[8], g->evs()[9]) : 0.0; g->oz_prepare_pending = false; }
-    // ALGORITHMIC int8 operations of the residue GEMMs: n moduli × the triangular product N²·M (N(N+1)/2 multiply-adds per
-    // candidate, 2 operations each ≈ N²).  What the kernel issues beyond that — the upper halves of its 256-wide diagonal blocks
-    // (of which it skips 6 of 16 units), padding of N and M to 256 — is not credited.
-    g->tm.oz_gemm_ops = oz ? (double)g->tm.oz_nmod * (double)g->N * (double)g->N * (double)M : 0.0;
-    // algorithmic (triangular) flop of the contraction: N²·M, N = true training size
-    g->tm.var_gemm_flop = with_var ? (double)g->N * (double)g->N * (double)M : 0.0;
+    // ALGORITHMIC int8 operations of the residue GEMMs: n moduli × the triangular product R²·M per pass (R(R+1)/2 multiply-adds per
+    // candidate over the R rows of W the pass contracts — R = N but for a bound pass —, 2 operations each ≈ R²).  What the kernel issues
+    // beyond that — the upper halves of its 256-wide diagonal blocks (of which it skips 6 of 16 units), padding of N and M to 256 — is
+    // not credited.
+    g->tm.oz_gemm_ops = oz ? (double)g->tm.oz_nmod * work : 0.0;
+    // algorithmic (triangular) flop of the contraction: R²·M per pass
+    g->tm.var_gemm_flop = with_var ? work : 0.0;
 }
 
 int32_t check_fitted(abo_gp* g, int32_t d) {
@@ -1565,7 +1585,7 @@ int32_t abo_predict(abo_gp* g, const double* Z, int64_t M, int32_t d, int32_t z_
     if (mu && out_space == ABO_HOST) { rc = copy_out(mu, mu_d, sizeof(double) * M, ABO_HOST, s); if (rc) return rc; }
     if (var && out_space == ABO_HOST) { rc = copy_out(var, var_d, sizeof(double) * M, ABO_HOST, s); if (rc) return rc; }
     HIPCHK(wait_stream(s));
-    collect_posterior_timings(g, M, var != nullptr);
+    collect_posterior_timings(g, var != nullptr);
     g->tm.acq_topk_ms = 0.0;
     g->tm.acq_total_ms = ev_ms(g->evs()[5], g->evs()[6]);
     return ABO_OK;
@@ -1658,10 +1678,12 @@ AcqTerms one_term(int32_t kind, double p0, double best_y) {
 //   one plain term            the fused posterior + epilogue pass (what abo_acq has always run: same bits)
 //   function-value terms      ONE posterior pass, then every member's epilogue on that μ, σ² (EnsembleAcq.jl:53-55)
 //   a GRADNORM_UCB term       the all-output posterior per point (mean[p], covariance block) in slabs, epilogue on those
-int32_t score_terms_device(abo_gp* g, const double* Zd, int64_t M, const AcqTerms& t, double* sc_d) {
+//   more: the call already ran posterior passes (a pruned selection that fell back): this one is counted next to them
+int32_t score_terms_device(abo_gp* g, const double* Zd, int64_t M, const AcqTerms& t, double* sc_d, bool more = false) {
     hipStream_t s = g->stream;
     if (terms_plain(t)) {
-        if (t.kind[0] != ABO_ACQ_MEAN) return posterior(g, Zd, M, t.kind[0], t.p0[0], t.best_y[0], nullptr, nullptr, sc_d);
+        if (t.kind[0] != ABO_ACQ_MEAN)
+            return posterior(g, Zd, M, t.kind[0], t.p0[0], t.best_y[0], nullptr, nullptr, sc_d, 1, 0, nullptr, 0, 0, more);
         // −mu only: skip the contraction (scores come from the mean pass)
         HIPCHK(g->mu_all.ensure(sizeof(double) * M));
         int32_t rc = posterior(g, Zd, M, -1, 0.0, 0.0, g->mu_all.as<double>(), nullptr, nullptr);
@@ -1695,6 +1717,122 @@ int32_t score_terms_device(abo_gp* g, const double* Zd, int64_t M, const AcqTerm
     return ABO_OK;
 }
 
+// ---- exact top-k without the full variance contraction (DESIGN.md "Pruned top-k selection") -------------------------------------------
+// The sum of squares over the first R rows of V = L⁻¹K_XZ is the variance reduction from the first R training points alone, so
+// σ²_R = k_zz − Σ_{i<R} V_ij² ≥ σ², and EI and UCB (β ≥ 0) do not decrease with σ: the score of (μ, σ²_R) bounds the score from above.
+// W = L⁻¹ being triangular, its first R rows cost (R/N)² of the contraction.
+struct PrunePlan {
+    bool eligible;
+    int rblocks;            // 256-row blocks of W in the bound pass
+    int64_t k0;             // candidates whose exact scores set the threshold
+    int64_t max_survivors;  // more than this: the ordinary full pass runs instead of the survivor pass
+};
+
+#ifdef ABO_TEST_HOOKS
+std::atomic<int> g_prune_force_rblocks{0};      // abo_test_prune_force: row blocks of the bound pass (0 = the rule); mode 1 = a threshold
+std::atomic<int> g_prune_force_mode{0};         // of −Inf (every candidate survives: the worst case, on any data), 2 = as ABO_ACQ_PRUNE=0
+#endif
+
+bool prune_enabled() {
+    static const bool on = [] { const char* e = getenv("ABO_ACQ_PRUNE"); return !(e && e[0] == '0'); }();
+#ifdef ABO_TEST_HOOKS
+    if (g_prune_force_mode.load() == 2) return false;
+#endif
+    return on;
+}
+
+// rows: factor rows N of the model; int8_fused: the int8-residue engine would run this call's contraction with generator-written planes
+PrunePlan prune_plan(int64_t rows, int64_t M, int k, bool want_scores, int kind, double p0, int p_out, bool int8_fused, int d) {
+    PrunePlan pp{false, 0, 0, 0};
+    const int64_t tblocks = (rows + 255) / 256;
+    // R = N/8, rounded to whole 256-row blocks: the bound pass then costs 1/64 of the contraction.  On the synthetic problem of the
+    // benchmark R = N/8, N/4, N/2 left 4 %, 2 %, 1 % of the candidates: R = N/4 would halve a survivor pass that costs 0.04 of the
+    // full one at four times a bound pass that costs 0.016 of it.
+    int rb = (int)((rows / 8 + 128) / 256);
+    if (rb < 1) rb = 1;
+#ifdef ABO_TEST_HOOKS
+    if (g_prune_force_rblocks.load() > 0) rb = g_prune_force_rblocks.load();
+#endif
+    pp.rblocks = rb;
+    pp.k0 = k > 0 ? ((int64_t)4 * k > 1024 ? (int64_t)4 * k : 1024) : 0;
+    // the survivor pass costs S/M of the full pass it replaces (plus a gather of S points): it is the cheaper of the two for any
+    // S < M, and is taken while it saves at least an eighth of the pass — far more than the extra launches cost
+    pp.max_survivors = M - M / 8;
+    const bool monotone = kind == ABO_ACQ_EI || (kind == ABO_ACQ_UCB && p0 >= 0.0);
+    // two passes pay from a few times the K0 exactly evaluated candidates on (M ≥ 4·K0: the threshold pass is at most a quarter of
+    // what the selection can save); the compaction counts in ints and gathers with 32-bit element indices
+    pp.eligible = prune_enabled() && k > 0 && !want_scores && monotone && p_out == 1 && int8_fused && rb < tblocks &&
+                  M >= 4 * pp.k0 && M * (int64_t)d < ((int64_t)1 << 31);
+    return pp;
+}
+
+// The pruned selection on device candidates Zd.  *done = false: nothing selected (the engine was not available after all, or too many
+// candidates survived) — the caller runs the ordinary pass, with more = true when passes were launched here.
+int32_t prune_select(abo_gp* g, const double* Zd, int64_t M, const AcqTerms& t, const PrunePlan& pp, int64_t idx_base, int32_t k,
+                     TopkWork w, double* tv, int64_t* ti, bool* done) {
+    hipStream_t s = g->stream;
+    const int d = g->d;
+    const int kind = t.kind[0];
+    const double p0 = t.p0[0], best_y = t.best_y[0];
+    const int64_t K0 = pp.k0;
+    *done = false;
+    const int64_t nb = (M + PRUNE_SCAN_E - 1) / PRUNE_SCAN_E;
+    HIPCHK(g->pr_ub.ensure(sizeof(double) * M));
+    HIPCHK(g->pr_z.ensure(sizeof(double) * K0 * d));
+    HIPCHK(g->pr_sc.ensure(sizeof(double) * K0));
+    HIPCHK(g->pr_sel.ensure(sizeof(int64_t) * M));
+    HIPCHK(g->pr_blk.ensure(sizeof(int) * nb + 16));
+    HIPCHK(g->pr_tv.ensure(sizeof(double) * (K0 + 2)));          // K0 values, then {survivor count, −Inf (test hook)}
+    HIPCHK(g->pr_ti.ensure(sizeof(int64_t) * K0));
+    double* ub = g->pr_ub.as<double>();
+    int64_t* count_d = reinterpret_cast<int64_t*>(g->pr_tv.as<double>() + K0);
+    HIPCHK(g->events(EV_BASE));
+    constexpr size_t PE = 10;          // events 10-13, by index: the passes below may grow (and move) the context's event list
+    // 1. bound pass: the chunk pipeline on the first row blocks of W
+    HIPCHK(hipEventRecord(g->evs()[PE], s));
+    int32_t rc = posterior(g, Zd, M, kind, p0, best_y, nullptr, nullptr, ub, 1, 0, nullptr, 0, pp.rblocks, false);
+    if (rc == PRUNE_UNAVAILABLE) return ABO_OK;
+    if (rc) return rc;
+    g->pst.bound_rows = g->passes.back().rows;
+    g->pst.k0 = K0;
+    HIPCHK(hipEventRecord(g->evs()[PE + 1], s));
+    // 2. threshold: exact scores of the K0 best by bound (NaN bounds first, as everywhere), τ = the k-th best of them
+    HIPCHK(launch_topk(ub, M, (int)K0, 0, w, g->pr_tv.as<double>(), g->pr_ti.as<int64_t>(), s));
+    HIPCHK(launch_gather_points(Zd, g->pr_ti.as<int64_t>(), 0, (int)K0, d, g->pr_z.as<double>(), s));
+    rc = posterior(g, g->pr_z.as<double>(), K0, kind, p0, best_y, nullptr, nullptr, g->pr_sc.as<double>(), 1, 0, nullptr, 0, 0, true);
+    if (rc) return rc;
+    HIPCHK(launch_topk(g->pr_sc.as<double>(), K0, k, 0, w, g->pr_tv.as<double>(), g->pr_ti.as<int64_t>(), s));
+    const double* tau = g->pr_tv.as<double>() + (k - 1);
+#ifdef ABO_TEST_HOOKS
+    if (g_prune_force_mode.load() == 1) {
+        static const double ninf = -HUGE_VAL;
+        HIPCHK(hipMemcpyAsync(count_d + 1, &ninf, sizeof(double), hipMemcpyHostToDevice, s));
+        tau = reinterpret_cast<const double*>(count_d + 1);
+    }
+#endif
+    // 3. survivors: every candidate whose guarded bound reaches τ (the k that set τ among them), in index order
+    HIPCHK(launch_prune_compact(ub, M, tau, g->pr_blk.as<int>(), g->pr_sel.as<int64_t>(), count_d, s));
+    HIPCHK(hipEventRecord(g->evs()[PE + 2], s));
+    int64_t S = 0;
+    HIPCHK(hipMemcpyAsync(&S, count_d, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(wait_stream(s));
+    g->pst.survivors = S;
+    if (S < k || S > pp.max_survivors) { g->pst.fallback = 1; return ABO_OK; }
+    HIPCHK(g->pr_z.ensure(sizeof(double) * S * d));
+    HIPCHK(g->pr_sc.ensure(sizeof(double) * S));
+    HIPCHK(launch_gather_points(Zd, g->pr_sel.as<int64_t>(), 0, (int)S, d, g->pr_z.as<double>(), s));
+    rc = posterior(g, g->pr_z.as<double>(), S, kind, p0, best_y, nullptr, nullptr, g->pr_sc.as<double>(), 1, 0, nullptr, 0, 0, true);
+    if (rc) return rc;
+    PHASE_EVENT(g->evs()[6], s);
+    // 4. the selection among the exactly evaluated: list positions are in index order, so ties fall as they do over all M
+    HIPCHK(launch_topk(g->pr_sc.as<double>(), S, k, 0, w, tv, ti, s));
+    HIPCHK(launch_prune_map(ti, k, g->pr_sel.as<int64_t>(), idx_base, s));
+    HIPCHK(hipEventRecord(g->evs()[PE + 3], s));
+    g->pst.pruned = 1;
+    *done = true;
+    return ABO_OK;
+}
+
 // scores + selection for host or device candidates; separate memory spaces for the M scores and for the k selected pairs
 int32_t acq_terms_impl(abo_gp* g, const double* Z, int64_t M, int32_t d, int32_t z_space, const AcqTerms& t, int64_t idx_base,
                        double* scores, int32_t out_space, int32_t k, double* top_val, int64_t* top_idx, int32_t top_space) {
@@ -1707,36 +1845,55 @@ int32_t acq_terms_impl(abo_gp* g, const double* Z, int64_t M, int32_t d, int32_t
     PinStage pin(g->ctx);
     const bool with_var = !(terms_plain(t) && t.kind[0] == ABO_ACQ_MEAN);
     const bool fused_timings = !terms_have_gradnorm(t);           // the slab path does not keep per-chunk events
-    if (M > 0) {
-        const double* Zd = nullptr;
-        int32_t rc = stage_candidates(g, Z, M, z_space, &Zd);
-        if (rc) return rc;
-        if (scores && out_space == ABO_DEVICE) sc_d = scores;
-        else { HIPCHK(g->score_all.ensure(sizeof(double) * M)); sc_d = g->score_all.as<double>(); }
-        HIPCHK(hipEventRecord(g->evs()[5], s));
-        rc = score_terms_device(g, Zd, M, t, sc_d);
-        if (rc) return rc;
-        PHASE_EVENT(g->evs()[6], s);
-    } else {
-        HIPCHK(hipEventRecord(g->evs()[5], s));
-        PHASE_EVENT(g->evs()[6], s);
+    g->pst = abo_prune_stats{};
+    PrunePlan pp{false, 0, 0, 0};
+    if (M > 0 && terms_plain(t)) {
+        int nm = 0;
+        KgenArgs probe{};
+        probe.pt = g->p_out; probe.dp = g->dp;
+        const bool int8_fused = wants_int8(g, true, 1, &nm) && kgen_writes_residues(probe, nm);
+        pp = prune_plan(g->N, M, k, scores != nullptr, t.kind[0], t.p0[0], g->p_out, int8_fused, g->d);
     }
+    TopkWork w{};
+    double* tv = top_val;
+    int64_t* ti = top_idx;
     if (k > 0) {
-        const int64_t we = topk_workspace_entries(M, k);
+        const int64_t we = topk_workspace_entries(M, pp.eligible && pp.k0 > k ? (int)pp.k0 : k);
         HIPCHK(g->tk_keys0.ensure(sizeof(uint64_t) * we));
         HIPCHK(g->tk_keys1.ensure(sizeof(uint64_t) * we));
         HIPCHK(g->tk_idx0.ensure(sizeof(int64_t) * we));
         HIPCHK(g->tk_idx1.ensure(sizeof(int64_t) * we));
-        TopkWork w{{g->tk_keys0.as<uint64_t>(), g->tk_keys1.as<uint64_t>()}, {g->tk_idx0.as<int64_t>(), g->tk_idx1.as<int64_t>()}};
-        double* tv = top_val;
-        int64_t* ti = top_idx;
+        w = TopkWork{{g->tk_keys0.as<uint64_t>(), g->tk_keys1.as<uint64_t>()}, {g->tk_idx0.as<int64_t>(), g->tk_idx1.as<int64_t>()}};
         if (top_space == ABO_HOST) {
             HIPCHK(g->top_val.ensure(sizeof(double) * k));
             HIPCHK(g->top_idx.ensure(sizeof(int64_t) * k));
             tv = g->top_val.as<double>();
             ti = g->top_idx.as<int64_t>();
         }
-        HIPCHK(launch_topk(sc_d, M, k, idx_base, w, tv, ti, s));
+    }
+    bool selected = false;
+    if (M > 0) {
+        const double* Zd = nullptr;
+        int32_t rc = stage_candidates(g, Z, M, z_space, &Zd);
+        if (rc) return rc;
+        HIPCHK(hipEventRecord(g->evs()[5], s));
+        if (pp.eligible) {
+            rc = prune_select(g, Zd, M, t, pp, idx_base, k, w, tv, ti, &selected);
+            if (rc) return rc;
+        }
+        if (!selected) {
+            if (scores && out_space == ABO_DEVICE) sc_d = scores;
+            else { HIPCHK(g->score_all.ensure(sizeof(double) * M)); sc_d = g->score_all.as<double>(); }
+            rc = score_terms_device(g, Zd, M, t, sc_d, /*more=*/g->pst.bound_rows > 0);
+            if (rc) return rc;
+            PHASE_EVENT(g->evs()[6], s);
+        }
+    } else {
+        HIPCHK(hipEventRecord(g->evs()[5], s));
+        PHASE_EVENT(g->evs()[6], s);
+    }
+    if (k > 0) {
+        if (!selected) HIPCHK(launch_topk(sc_d, M, k, idx_base, w, tv, ti, s));
         if (top_space == ABO_HOST) {
             HIPCHK(pin.d2h(top_val, tv, sizeof(double) * k, s));             // through the pinned block, copied on after the sync
             HIPCHK(pin.d2h(top_idx, ti, sizeof(int64_t) * k, s));
@@ -1749,9 +1906,15 @@ int32_t acq_terms_impl(abo_gp* g, const double* Z, int64_t M, int32_t d, int32_t
     }
     HIPCHK(wait_stream(s));
     pin.flush();
-    if (M > 0 && fused_timings) collect_posterior_timings(g, M, with_var);
+    if (M > 0 && fused_timings) collect_posterior_timings(g, with_var);
     g->tm.acq_topk_ms = phase_events() ? ev_ms(g->evs()[6], g->evs()[7]) : 0.0;
     g->tm.acq_total_ms = ev_ms(g->evs()[5], g->evs()[7]);
+    if (g->pst.bound_rows > 0) {
+        hipEvent_t* pe = &g->evs()[10];
+        g->pst.bound_ms = ev_ms(pe[0], pe[1]);
+        g->pst.threshold_ms = ev_ms(pe[1], pe[2]);
+        g->pst.survivor_ms = g->pst.pruned ? ev_ms(pe[2], pe[3]) : 0.0;
+    }
     return ABO_OK;
 }
 
@@ -1901,6 +2064,12 @@ int32_t abo_get_n(abo_gp* g, int64_t* N, int32_t* d) {
     return ABO_OK;
 }
 
+int32_t abo_get_prune_stats(abo_gp* g, abo_prune_stats* out) {
+    if (!g || !out) return fail(ABO_EINVAL, "abo_get_prune_stats: null argument");
+    *out = g->pst;
+    return ABO_OK;
+}
+
 int32_t abo_get_timings(abo_gp* g, abo_timings* out) {
     if (!g || !out) return fail(ABO_EINVAL, "abo_get_timings: null argument");
     *out = g->tm;
@@ -2028,7 +2197,7 @@ int32_t abo_cand_refresh(abo_gp* g, abo_cand* c) {
         if (rc) return rc;
         HIPCHK(hipEventRecord(g->evs()[6], g->stream));
         HIPCHK(wait_stream(g->stream));
-        collect_posterior_timings(g, c->M, true);
+        collect_posterior_timings(g, true);
         g->tm.acq_topk_ms = 0.0;
         g->tm.acq_total_ms = ev_ms(g->evs()[5], g->evs()[6]);
     }
@@ -3490,6 +3659,30 @@ int32_t abo_score(int32_t device, const double* mu, const double* var, int64_t M
 }
 
 #ifdef ABO_TEST_HOOKS
+int32_t abo_test_prune_plan(int64_t rows, int64_t M, int32_t k, int32_t want_scores, int32_t kind, double p0, int32_t p_out, int32_t int8_fused,
+                            int32_t d, int64_t* out) {
+    if (!out) return fail(ABO_EINVAL, "abo_test_prune_plan: null argument");
+    const PrunePlan pp = prune_plan(rows, M, k, want_scores != 0, kind, p0, p_out, int8_fused != 0, d);
+    out[0] = pp.eligible; out[1] = pp.rblocks; out[2] = pp.k0; out[3] = pp.max_survivors;
+    return ABO_OK;
+}
+
+int32_t abo_test_prune_force(int32_t rblocks, int32_t mode) {
+    if (rblocks < 0 || mode < 0 || mode > 2) return fail(ABO_EINVAL, "abo_test_prune_force: rblocks = %d, mode = %d", rblocks, mode);
+    g_prune_force_rblocks.store(rblocks);
+    g_prune_force_mode.store(mode);
+    return ABO_OK;
+}
+
+int32_t abo_test_prune_bounds(abo_gp* g, double* out, int64_t M) {
+    if (!g || !out || M < 0) return fail(ABO_EINVAL, "abo_test_prune_bounds: bad argument");
+    if (!g->pst.bound_rows || g->pr_ub.cap < sizeof(double) * (size_t)M) return fail(ABO_EINVAL, "abo_test_prune_bounds: the last abo_acq on this handle ran no bound pass over %lld candidates", (long long)M);
+    HIPCHK(hipSetDevice(g->prm.device));
+    HIPCHK(hipMemcpyAsync(out, g->pr_ub.p, sizeof(double) * M, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(wait_stream(g->stream));
+    return ABO_OK;
+}
+
 int32_t abo_test_oz_plan(int32_t n, int32_t* p, double* tables, double* scal, int32_t* eP) {
     if (!p || !tables || !scal || !eP) return fail(ABO_EINVAL, "abo_test_oz_plan: null argument");
     OzPlan pl;

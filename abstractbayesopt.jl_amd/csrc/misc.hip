@@ -682,4 +682,94 @@ hipError_t launch_gather_points(const double* Z, const int64_t* idx, int64_t idx
     return hipGetLastError();
 }
 
+// ---- pruned top-k selection: which candidates still need the full variance ---------------------------------------------------------------
+// ub[j] is the score computed from the exact μ_j and σ²_R(j) = k_zz − Σ_{i<R} V_ij² + 1e-18 ≥ σ²(j): finalize_kernel adds the row
+// blocks' sums in order, so the R-row sum is a prefix of the full one and, the later terms being ≥ 0 and fp64 addition monotone, the
+// COMPUTED σ²_R is ≥ the computed σ² as well.  What remains is whether acq_score, as computed, is non-decreasing in var at fixed μ:
+//   UCB  −μ + β·sqrt(max(var, 0)), β ≥ 0: sqrt, the product and the sum are each correctly rounded, hence monotone — no margin needed.
+//   EI   var ≤ 1e-12 gives max(Δ, 0) ≤ the exact EI of any larger var; otherwise Δ·Φ(z) + σ·φ(z), z = Δ/σ.  Relative error of a term, in
+//        units of 2⁻⁵³: a few from erfc / exp / sqrt and the products; z² ≤ 1416 from the rounding of z in each of Φ(z) (d ln Φ/dz ≤
+//        |z| + 1) and φ(z); 708 from the rounding of the argument −z²/2 of exp (beyond z² = 1416 φ leaves the normal range) — below
+//        2200 together.  For Δ < 0 the two terms cancel: Δ·Φ + σ·φ = σ·φ·(1 − |z|·Φ(−|z|)/φ) and, by the Mills-ratio bound
+//        Φ(−x)/φ(x) ≤ (x² + 2)/(x³ + 3x), 1 − |z|Φ/φ ≥ 1/(z² + 3): the sum's relative error is at most z² + 3 ≤ 1500 times a term's.
+//        1500·2200·2⁻⁵³ < 3.7·10⁻¹⁰ < 2⁻³⁰ = PRUNE_REL (10⁻⁹ of the score: no effect on how much is pruned).  Where Φ or φ leave the
+//        normal range both terms are below 2⁻¹⁰²² in magnitude and so is any error of their sum: PRUNE_ABS = 2⁻¹⁰²², the smallest normal.
+// A NaN bound, score or threshold keeps the candidate (NaN ranks first in the selection's order).
+__device__ __forceinline__ bool prune_keep(double ub, double tau) {
+    return !(ub + fabs(ub) * PRUNE_REL + PRUNE_ABS < tau);
+}
+
+// workgroup b owns candidates [b·1024, (b+1)·1024), thread t four consecutive ones: SCATTER = false counts the kept ones into blk[b];
+// SCATTER = true (blk now holds the exclusive offsets) writes their indices at blk[b] + rank inside the workgroup — index order
+template <bool SCATTER>
+__global__ void __launch_bounds__(256) prune_compact_kernel(const double* __restrict__ ub, int64_t M, const double* __restrict__ tau,
+                                                            int* __restrict__ blk, int64_t* __restrict__ sel) {
+    __shared__ int wsum[4];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int64_t j0 = (int64_t)blockIdx.x * PRUNE_SCAN_E + 4 * t;
+    const double th = tau[0];
+    bool keep[4];
+    int mine = 0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) { keep[u] = j0 + u < M && prune_keep(ub[j0 + u], th); mine += keep[u]; }
+    int incl = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int v = __shfl_up(incl, o); if (lane >= o) incl += v; }
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    int before_me = incl - mine;
+    for (int w = 0; w < wave; ++w) before_me += wsum[w];
+    if constexpr (!SCATTER) {
+        if (t == 255) blk[blockIdx.x] = before_me + mine;
+    } else {
+        int64_t pos = (int64_t)blk[blockIdx.x] + before_me;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) if (keep[u]) sel[pos++] = j0 + u;
+    }
+}
+
+// blk[0 … nb) → its exclusive prefix sums, in place; *count = the total.  One workgroup, 1024 entries per trip.
+__global__ void __launch_bounds__(1024) prune_scan_kernel(int* __restrict__ blk, int nb, int64_t* __restrict__ count) {
+    __shared__ int wsum[16];
+    __shared__ int carry;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    if (t == 0) carry = 0;
+    __syncthreads();
+    for (int b0 = 0; b0 < nb; b0 += 1024) {
+        const int v = b0 + t < nb ? blk[b0 + t] : 0;
+        int incl = v;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(incl, o); if (lane >= o) incl += u; }
+        if (lane == 63) wsum[wave] = incl;
+        __syncthreads();
+        int base = carry;
+        for (int w = 0; w < wave; ++w) base += wsum[w];
+        if (b0 + t < nb) blk[b0 + t] = base + incl - v;
+        __syncthreads();
+        if (t == 1023) carry = base + incl;
+        __syncthreads();
+    }
+    if (t == 0) count[0] = carry;
+}
+
+hipError_t launch_prune_compact(const double* ub, int64_t M, const double* tau, int* blk, int64_t* sel, int64_t* count, hipStream_t s) {
+    if (M <= 0 || M >= (int64_t)1 << 31) return hipErrorInvalidValue;      // (the counts are ints)
+    const int nb = (int)((M + PRUNE_SCAN_E - 1) / PRUNE_SCAN_E);
+    hipLaunchKernelGGL(prune_compact_kernel<false>, dim3(nb), dim3(256), 0, s, ub, M, tau, blk, sel);
+    hipLaunchKernelGGL(prune_scan_kernel, dim3(1), dim3(1024), 0, s, blk, nb, count);
+    hipLaunchKernelGGL(prune_compact_kernel<true>, dim3(nb), dim3(256), 0, s, ub, M, tau, blk, sel);
+    return hipGetLastError();
+}
+
+__global__ void prune_map_kernel(int64_t* top_idx, int k, const int64_t* sel, int64_t idx_base) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < k && top_idx[e] >= 0) top_idx[e] = sel[top_idx[e]] + idx_base;
+}
+
+hipError_t launch_prune_map(int64_t* top_idx, int k, const int64_t* sel, int64_t idx_base, hipStream_t s) {
+    if (k <= 0) return hipSuccess;
+    hipLaunchKernelGGL(prune_map_kernel, dim3((k + 255) / 256), dim3(256), 0, s, top_idx, k, sel, idx_base);
+    return hipGetLastError();
+}
+
 }  // namespace abo

@@ -862,7 +862,9 @@ hipError_t launch_var_ozaki(const OzVarArgs& v, hipStream_t s) {
     g.KR = v.KR; g.WR = v.WR; g.U = v.U;
     g.nhs = Np256 / 64;
     g.sK = (int64_t)Mc256 * Np256; g.sW = (int64_t)Np256 * Np256;
-    g.Ti = Np256 / OZ_T; g.Tj = Mc256 / OZ_T; g.n = pl.n;
+    // (rblocks: the tile list, the layout of U and the reconstruction cover the first row blocks only; nhs, the stride between the
+    // row blocks of a plane, stays that of the buffers)
+    g.Ti = v.rblocks > 0 && v.rblocks < Np256 / OZ_T ? v.rblocks : Np256 / OZ_T; g.Tj = Mc256 / OZ_T; g.n = pl.n;
     g.tjg = g.Tj >= 64 ? 64 : (int)pad_up(g.Tj, 8);
     for (int l = 0; l < pl.n; ++l) {
         g.invp[l] = pl.invp[l]; g.p[l] = pl.p[l];
@@ -893,11 +895,12 @@ hipError_t launch_var_ozaki(const OzVarArgs& v, hipStream_t s) {
     }
     OzCrtArgs c{};
     c.U = v.U; c.Ti = g.Ti; c.sexp = v.sexp; c.sK = v.sK; c.bad_row = v.bad_row; c.bad_col = v.bad_col;
-    c.partial = v.partial; c.ldp = v.ldp; c.Mc = v.Mc; c.nvalid = v.nvalid; c.pl = pl;
+    c.partial = v.partial; c.ldp = v.ldp; c.Mc = v.Mc; c.nvalid = v.nvalid < g.Ti * OZ_T ? v.nvalid : g.Ti * OZ_T; c.pl = pl;
     c.rmode = v.rmode; c.rper = v.rper; c.rtg = v.ktg; c.r0 = v.r0; c.rpts = v.rpts;
     c.ctr_reset = v.ctr_clean ? v.bad_col + Mc256 : nullptr;
-    if (pl.n == 14) hipLaunchKernelGGL(oz_crt_kernel<14>, dim3((v.Mc + 255) / 256, v.Np / 128), dim3(256), 0, s, c);
-    else hipLaunchKernelGGL(oz_crt_kernel<0>, dim3((v.Mc + 255) / 256, v.Np / 128), dim3(256), 0, s, c);
+    const int tbs = 2 * g.Ti < v.Np / 128 ? 2 * g.Ti : v.Np / 128;      // 128-row blocks of partial
+    if (pl.n == 14) hipLaunchKernelGGL(oz_crt_kernel<14>, dim3((v.Mc + 255) / 256, tbs), dim3(256), 0, s, c);
+    else hipLaunchKernelGGL(oz_crt_kernel<0>, dim3((v.Mc + 255) / 256, tbs), dim3(256), 0, s, c);
     e = hipGetLastError();
     if (e == hipSuccess && v.ctr_clean) *v.ctr_clean = v.bad_col + Mc256;
     return e;

@@ -133,6 +133,12 @@ class HipStandardGP(AbstractSurrogate):
         _lib.check(_lib.lib().abo_get_timings(self._require(), C.byref(t)))
         return t.as_dict()
 
+    def prune_stats(self) -> dict:
+        """the pruned top-k selection of the last evaluate() on this model (include/abo_hip.h: abo_prune_stats)"""
+        t = _lib.AboPruneStats()
+        _lib.check(_lib.lib().abo_get_prune_stats(self._require(), C.byref(t)))
+        return t.as_dict()
+
     # Checkpoint / resume: the reference has no serialisation code, a BOStruct is rebuilt from (xs, ys, hyper-
     # parameters) (bayesian_opt.jl:81).  A pickled model is exactly that — hyper-parameters plus the training data
     # read back from the device — and unpickling refits on the current device.

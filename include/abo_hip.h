@@ -151,6 +151,21 @@ typedef struct abo_timings {
     double append_trmv_ms, append_trmv_bytes;
 } abo_timings;
 
+/* The pruned top-k selection of the last abo_acq / abo_fit_acq on a handle (abo_get_prune_stats).  A call that asks for the top k
+ * only (k > 0, scores == NULL) with EI, or UCB with β ≥ 0, on a StandardGP whose contraction runs on the int8-residue engine, over at
+ * least 4·K₀ candidates, does not compute σ² of every candidate: a bound pass over the first bound_rows rows of L⁻¹ gives σ²_R ≥ σ²
+ * and so an upper bound of every score; the exact scores of the K₀ = max(4k, 1024) best-by-bound candidates set a threshold; only the
+ * candidates whose bound reaches it (the survivors) go through the full contraction.  The k pairs returned are bit for bit those of
+ * the full evaluation.  ABO_ACQ_PRUNE=0 in the environment turns the path off.  All zeros: the call was not eligible. */
+typedef struct abo_prune_stats {
+    int64_t pruned;        /* 1: the k pairs came from the survivor pass */
+    int64_t fallback;      /* 1: more than 7/8 of the candidates survived — the ordinary full pass ran behind the two passes below */
+    int64_t bound_rows;    /* rows of L⁻¹ the bound pass contracted (0: no bound pass ran) */
+    int64_t k0;            /* candidates evaluated exactly for the threshold */
+    int64_t survivors;     /* candidates whose bound reached the threshold (the k0 that set it are re-evaluated among them) */
+    double bound_ms, threshold_ms, survivor_ms;      /* HIP events on the handle's stream around the three passes */
+} abo_prune_stats;
+
 /* --- lifetime -------------------------------------------------------------------------------
  * StandardGP(kernel, noise_var; mean) (src/surrogates/StandardGP.jl:41-64).  The handle starts
  * un-conditioned (gpx === nothing). */
@@ -591,6 +606,7 @@ int32_t abo_get_n(abo_gp* gp, int64_t* N, int32_t* d);
  * this is the device-side half of that: checkpoint = hyper-parameters + these arrays, resume = abo_fit. */
 int32_t abo_get_data(abo_gp* gp, double* X, double* y);
 int32_t abo_get_timings(abo_gp* gp, abo_timings* out);
+int32_t abo_get_prune_stats(abo_gp* gp, abo_prune_stats* out);
 
 /* --- multi-device handles (BASELINE configs 4 and 5: candidates sharded over the GPUs of one node) -----------------
  * One host process drives all devices: the Julia host has no process launcher, so the sharding of
@@ -705,6 +721,16 @@ int32_t abo_abi_version(void);
  * NOT part of the shipped ABI: compiled only into the test build of the library (-DABO_TEST_HOOKS:
  * abstractbayesopt.jl_amd/lib/libabo_hip_test.so, what the GPU suite loads); libabo_hip.so exports none of them. */
 #ifdef ABO_TEST_HOOKS
+/* The host-side decisions of the pruned top-k selection (no GPU needed) for a model of `rows` factor rows and p_out outputs per
+ * point: out[4] = {eligible, 256-row blocks of the bound pass, K₀, largest survivor count that still takes the survivor pass}. */
+int32_t abo_test_prune_plan(int64_t rows, int64_t M, int32_t k, int32_t want_scores, int32_t kind, double p0, int32_t p_out,
+                            int32_t int8_fused, int32_t d, int64_t* out);
+/* Process-wide overrides for tests and measurements: rblocks > 0 = that many row blocks in the bound pass instead of the rule's;
+ * mode 1 = a threshold of −Inf (every candidate survives: the selection's worst case on any data), mode 2 = the path is off, as under
+ * ABO_ACQ_PRUNE=0.  (0, 0) restores the defaults. */
+int32_t abo_test_prune_force(int32_t rblocks, int32_t mode);
+/* out[0..M) (host) = the upper bounds the last abo_acq on this handle computed in its bound pass */
+int32_t abo_test_prune_bounds(abo_gp* gp, double* out, int64_t M);
 /* The int8-residue engine's host constants for n moduli (no GPU needed): p[16] moduli, tables[4][16] = {1/p, 2^26 mod p
  * (symmetric), head and tail of (P/p)·((P/p)⁻¹ mod p)}, scal[3] = {head of P, tail of P, 1/P}, *eP with 2^eP ≤ P/4. */
 int32_t abo_test_oz_plan(int32_t n, int32_t* p, double* tables, double* scal, int32_t* eP);
