@@ -26,7 +26,8 @@ EXPORTS = ["abo_create", "abo_set_contraction", "abo_create_grad", "abo_predict_
            "abo_paths_create", "abo_paths_destroy", "abo_paths_eval", "abo_paths_eval_cand", "abo_paths_stats_get",
            "abo_paths_append", "abo_paths_attach", "abo_paths_detach", "abo_paths_top", "abo_paths_values", "abo_paths_append_stats_get"]
 TEST_EXPORTS = ["abo_test_gemm_nt", "abo_test_kappa", "abo_test_oz_plan", "abo_test_oz_contract", "abo_test_acq_grad",
-                "abo_test_acq_grad_terms", "abo_test_prune_plan", "abo_test_prune_force", "abo_test_prune_bounds"]
+                "abo_test_acq_grad_terms", "abo_test_prune_plan", "abo_test_prune_force", "abo_test_prune_bounds", "abo_test_prune_mean",
+                "abo_test_kappa_tail"]
 ABI_VERSION = 7
 CONTRACT_AUTO, CONTRACT_FP64, CONTRACT_INT8 = 0, 1, 2
 # what abo_update / abo_mgpu_update ran (include/abo_hip.h)
@@ -179,6 +180,8 @@ def lib():
         L.abo_test_prune_plan.argtypes = [i64, i64, i32, i32, i32, f64, i32, i32, i32, vp]
         L.abo_test_prune_force.argtypes = [i32, i32]
         L.abo_test_prune_bounds.argtypes = [vp, vp, i64]
+        L.abo_test_prune_mean.argtypes = [vp, vp, vp, i64]
+        L.abo_test_kappa_tail.argtypes = [i32, i32, vp, vp, i64]
     L.abo_last_error.argtypes = [C.c_char_p, C.c_size_t]
     L.abo_abi_version.argtypes = []
     L.abo_pool_trim.argtypes = [i32]

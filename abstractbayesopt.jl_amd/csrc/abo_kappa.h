@@ -50,6 +50,80 @@ __device__ __forceinline__ double sqrt_pos(double x) {
     return x > 1e-290 ? g : 0.0;
 }
 
+// ---- the μ-only tail of the pruned selection's bound pass (kgen_tail.hip) ----------------------------------------------------------
+// Shorter sequences whose result only has to stay within a PROVEN distance of kappa_eval (the bound pass subtracts that distance from
+// its mean); nothing that is returned to a caller is computed with them.
+//
+// TAIL_ETA_EVAL bounds |kappa_tail(r²) − κ(r²)| for one finite r² ≥ TAIL_R2_MIN handed to both, in units of κ(0) = 1, u = 2⁻⁵³:
+//   sqrt   g̃ = √r²·(1 + δ_s): v_rsq_f64 is specified to 2²⁹ ulp (2⁻²³ relative); a seed error e, |e| ≤ 2⁻²², leaves 1.5e² ≤ 1.5·2⁻⁴⁴
+//          after the one coupled step, plus 4u of rounding.  Only the odd powers of the Matérn polynomial and the exponent are built
+//          from g̃, the even powers from r² itself, so κ moves by the PARTIAL derivative at fixed r²: with a = c·√r²,
+//          |a·∂κ/∂a|·δ_s = a²e⁻ᵃ ≤ 0.55 (ν = 3/2), (a² + a³/3)e⁻ᵃ ≤ 0.94 (ν = 5/2), (a³/3 + a⁴/15)e⁻ᵃ ≤ 0.74 (ν = 7/2), none for
+//          SE: below 0.94·(1.5·2⁻⁴⁴ + 4u) < 1.42·2⁻⁴⁴ = 8.1·10⁻¹⁴.
+//   exp    the argument t = −c·g̃ is rounded (|t|·u·eᵗ ≤ 0.37u), clamped at −800 (e⁻⁸⁰⁰ < 2⁻¹⁰⁷⁴: both sides of the clamp give 0), the
+//          reduction r = t − n·ln2 is exact to 2u (|n| ≤ 1155),
+//          the degree-10 Taylor polynomial on |r| ≤ ln2/2 leaves |r|¹¹/11!·e^{|r|} ≤ 2.17·10⁻¹³·1.4143 < 3.1·10⁻¹³ relative, Horner adds
+//          10u: the factor eᵗ carries at most 3.2·10⁻¹³ < 2⁻⁴¹·⁵ relative, and q·eᵗ = κ ≤ 1.
+//   rest   the Matérn polynomial q and the product: below 6u.
+// Together below 3.2·10⁻¹³ + 8.1·10⁻¹⁴ + 6u < 4.02·10⁻¹³ < 2⁻⁴¹ = 4.55·10⁻¹³.
+// TAIL_LIP: κ is Lipschitz in r² — |dκ/dr²| ≤ 1/2 (SE), 3/2 (ν = 3/2), 5/6 (ν = 5/2), 7/10 (ν = 7/2), each attained at r² = 0 — so an
+// absolute error δ of the squared distance (the expansion's cancellation, the clamp at TAIL_R2_MIN) costs at most 1.5·δ.
+constexpr double TAIL_ETA_EVAL = 0x1p-41;
+constexpr double TAIL_LIP = 1.5;
+constexpr double TAIL_R2_MIN = 0x1p-200;       // clamp of the expanded squared distance: no negative argument, no 0·∞ from the rsq seed
+constexpr double TAIL_W_MAX = 0x1p40;          // |x|² + |z|² (scaled) up to which the guard is stated: r² ≤ 2·TAIL_W_MAX stays far inside the
+                                               // range of the rsq seed and of the distance's error term
+
+// exp(x) for any x ≤ 0 (NaN is taken for −800: the caller answers for non-finite input): exp_nonpos with the polynomial cut at degree
+// 10 and the argument clamped where the result is 0 anyway, which keeps n inside the int range
+__device__ __forceinline__ double exp_nonpos_tail(double x) {
+    x = __builtin_fmax(x, -800.0);
+    const double n = rint(x * 1.4426950408889634074);
+    double r = fma(n, -6.93147180369123816490e-01, x);
+    r = fma(n, -1.90821492927058770002e-10, r);
+    double p = 2.75573192239858906526e-07;                 // 1/10!
+    p = fma(p, r, 2.75573192239858906526e-06);
+    p = fma(p, r, 2.48015873015873015873e-05);
+    p = fma(p, r, 1.98412698412698412698e-04);
+    p = fma(p, r, 1.38888888888888888889e-03);
+    p = fma(p, r, 8.33333333333333333333e-03);
+    p = fma(p, r, 4.16666666666666666667e-02);
+    p = fma(p, r, 1.66666666666666666667e-01);
+    p = fma(p, r, 0.5);
+    p = fma(p, r, 1.0);
+    p = fma(p, r, 1.0);
+    return ldexp(p, (int)n);
+}
+
+// sqrt(x) for TAIL_R2_MIN ≤ x < 2⁴²: the seed and ONE coupled step, no residual correction; NaN and +Inf come back as NaN
+__device__ __forceinline__ double sqrt_tail(double x) {
+    const double y = __builtin_amdgcn_rsq(x);
+    const double g = x * y, h = 0.5 * y;
+    const double r = fma(-h, g, 0.5);
+    return fma(g, r, g);
+}
+
+// κ(r²) without σ_f², r² the expanded squared distance before the clamp
+template <int FAM>
+__device__ __forceinline__ double kappa_tail(double d2) {
+    d2 = __builtin_fmax(d2, TAIL_R2_MIN);
+    if constexpr (FAM == ABO_KERNEL_SE) {
+        return exp_nonpos_tail(-0.5 * d2);
+    } else if constexpr (FAM == ABO_KERNEL_MATERN52) {
+        const double s5 = 2.23606797749978969640917366873128;
+        const double d = sqrt_tail(d2);
+        return fma(d2, 5.0 / 3.0, fma(s5, d, 1.0)) * exp_nonpos_tail(-s5 * d);
+    } else if constexpr (FAM == ABO_KERNEL_MATERN72) {
+        const double s7 = 2.64575131106459059050161575363926;
+        const double d = sqrt_tail(d2);
+        return fma(d2 * d, 7.0 * s7 / 15.0, fma(d2, 14.0 / 5.0, fma(s7, d, 1.0))) * exp_nonpos_tail(-s7 * d);
+    } else {
+        const double s3 = 1.73205080756887729352744634150587;
+        const double d = sqrt_tail(d2);
+        return fma(s3, d, 1.0) * exp_nonpos_tail(-s3 * d);
+    }
+}
+
 template <int FAM>
 __device__ __forceinline__ double kappa_eval(double d2) {
     if constexpr (FAM == ABO_KERNEL_SE) {

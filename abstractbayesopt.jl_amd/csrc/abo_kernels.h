@@ -139,12 +139,36 @@ struct KgenArgs {
     int* res_bad = nullptr;
     int res_n = 0, res_sK = 0;
     int res_ktg = 0;      // gradient-enhanced GP: derivative training rows and derivative candidate outputs each carry 2^-res_ktg on top
-    int res_kmax = 0;     // StandardGP: > 0 (a multiple of 128) = planes only for the training columns k < res_kmax (the rest is never read
-                          // by a contraction limited to the first res_kmax rows of the triangular W); 0 = all columns
+    int res_kmax = 0;     // StandardGP: > 0 (a multiple of 128) = the launch covers the training columns k < res_kmax alone (the rest is
+                          // never read by a contraction limited to the first res_kmax rows of the triangular W): planes for them, and
+                          // mu = mean_c + their part of the sum — the other columns' part comes from launch_kgen_tail; 0 = all columns
 };
 // true when launch_kgen honours KgenArgs::res for this shape and n moduli (the fused output is instantiated for the default plan)
 inline bool kgen_writes_residues(const KgenArgs& a, int n) { return a.dp <= 32 && n == 14 && !a.dlogell; }
 hipError_t launch_kgen(const KgenArgs& a, hipStream_t s);
+// ---- the μ-only tail of the pruned selection's bound pass (kgen_tail.hip) ----
+// over the N training points: norms[0] = Σ_{k ≥ k0} |alpha_k|, norms[1] = Σ_k |alpha_k|, norms[2] = max_{k ≥ k0} |Xs_k|² — one
+// workgroup, fixed order
+hipError_t launch_tail_norms(const double* Xs, const double* alpha, int N, int dp, int k0, double* norms, hipStream_t s);
+// For the chunk's candidates j (global index gj = j0 + j < M):
+//   mu_tail[gj] = sigma_f2·Σ_{k0 ≤ k < N} alpha_k·κ̃(r²_jk), κ̃ = kappa_tail of the EXPANDED squared distance |x|² + |z|² − 2x·z
+//   eps[gj]     ≥ |(head + mu_tail) − μ| for the μ of a full launch_kgen and the head of one limited to res_kmax = k0
+// (derivation: kgen_tail.hip).  A candidate with a non-finite coordinate, or |x|² + |z|² ≥ TAIL_W_MAX, gets mu_tail = NaN.
+struct KgenTailArgs {
+    const double* Xs;     // [Np][dp]  only the rows k < N are read
+    const double* Z;      // [M][d]
+    const double* alpha;  // [Np]      only the entries k < N are read
+    const double* norms;  // [3], launch_tail_norms with the same k0
+    double* mu_tail;      // [M]
+    double* eps;          // [M]
+    int64_t M, j0;
+    int Mc;               // padded chunk rows (multiple of 16)
+    int N, Np, k0, d, dp, family;
+    double s, sigma_f2, mean_c;
+};
+hipError_t launch_kgen_tail(const KgenTailArgs& a, hipStream_t s);
+// test hook: out[i] = kappa_tail(family, d2[i]) (abo_kappa.h)
+hipError_t launch_kappa_tail_test(int family, const double* d2, double* out, int64_t n, hipStream_t s);
 // NLML gradient reduction: Σ_ij (Kinv − ααᵀ)_ij ∂K_ij/∂log ℓ over the lower tiles, plus tr(Kinv), αᵀα, αᵀδ
 struct NlmlGradArgs {
     const double* Xs;      // [Np][dp]
@@ -247,6 +271,10 @@ struct FinalizeArgs {
     double prior_grad = 0.0;
     int pc = 1, point_major = 0;
     int64_t Mpts = 0;
+    // bound pass of the pruned selection: mu_in holds the head of the mean; mu_tail [M] (global index) its tail on the way in and
+    // μ̃ = head + tail on the way out, mu_eps [M] the proven |μ̃ − μ| — var / score are taken at μ̃ − ε
+    double* mu_tail = nullptr;
+    const double* mu_eps = nullptr;
 };
 hipError_t launch_finalize(const FinalizeArgs& a, hipStream_t s);
 

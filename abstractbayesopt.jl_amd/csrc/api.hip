@@ -381,6 +381,7 @@ struct abo_gp {
     struct PostPass { int64_t chunk0, nchunk, M, rows; };     // first chunk's event slot, chunks, candidate rows, rows of W contracted
     std::vector<PostPass> passes;
     DevBuf pr_ub, pr_z, pr_sc, pr_sel, pr_blk, pr_tv, pr_ti;   // pruned selection: bounds, gathered points, their scores, survivor list, scan scratch, threshold pairs
+    DevBuf pr_mut, pr_eps, pr_nrm;                             // its bound pass: μ̃ and ε of every candidate, the norms ε is built from (kgen_tail.hip)
     abo_prune_stats pst{};
     DevBuf oz_WR, oz_sexp, oz_badr, oz_KR, oz_U, oz_badc;
     abo_timings tm{};
@@ -391,14 +392,16 @@ struct abo_gp {
     void set_device(int dev) {
         DevBuf* all[] = {&alpha, &vext, &tvec, &T, &info, &scal, &Zdev, &Kxz, &partial, &mu_c, &mu_all, &var_all,
                          &score_all, &tk_keys0, &tk_keys1, &tk_idx0, &tk_idx1, &top_val, &top_idx,
-                         &oz_WR, &oz_sexp, &oz_badr, &oz_KR, &oz_U, &oz_badc, &pr_ub, &pr_z, &pr_sc, &pr_sel, &pr_blk, &pr_tv, &pr_ti};
+                         &oz_WR, &oz_sexp, &oz_badr, &oz_KR, &oz_U, &oz_badc, &pr_ub, &pr_z, &pr_sc, &pr_sel, &pr_blk, &pr_tv, &pr_ti,
+                         &pr_mut, &pr_eps, &pr_nrm};
         for (DevBuf* b : all) b->dev = dev;
     }
 
     void free_all() {
         DevBuf* all[] = {&alpha, &vext, &tvec, &T, &info, &scal, &Zdev, &Kxz, &partial, &mu_c, &mu_all, &var_all,
                          &score_all, &tk_keys0, &tk_keys1, &tk_idx0, &tk_idx1, &top_val, &top_idx,
-                         &oz_WR, &oz_sexp, &oz_badr, &oz_KR, &oz_U, &oz_badc, &pr_ub, &pr_z, &pr_sc, &pr_sel, &pr_blk, &pr_tv, &pr_ti};
+                         &oz_WR, &oz_sexp, &oz_badr, &oz_KR, &oz_U, &oz_badc, &pr_ub, &pr_z, &pr_sc, &pr_sel, &pr_blk, &pr_tv, &pr_ti,
+                         &pr_mut, &pr_eps, &pr_nrm};
         for (DevBuf* b : all) b->release();
         oz_N = -1;
         oz_ctr_clean = nullptr;
@@ -849,7 +852,8 @@ int32_t oz_planes_of_w(abo_gp* g) {
 // kstore / ldstore: write K_XZ into a caller-owned candidate-major matrix (pad_up(M,128) rows of ldstore ≥ Np doubles)
 // instead of the per-chunk scratch — the resident K_ZX of a candidate set.
 // rblocks > 0 (the bound pass of the pruned selection; int8 engine with generator-written planes only, else PRUNE_UNAVAILABLE):
-// the contraction covers the first rblocks 256-row blocks of W — var / score then come from σ²_R ≥ σ², μ from the full pass's code.
+// the contraction covers the first rblocks 256-row blocks of W — var / score then come from σ²_R ≥ σ² and from μ̃ − ε ≤ μ: the mean's
+// columns past those blocks are summed by the cheaper launch_kgen_tail, which also proves ε ≥ |μ̃ − μ| (kgen_tail.hip).
 // more: a further pass of the same call — its events and counts are kept next to those of the passes before it.
 constexpr int32_t PRUNE_UNAVAILABLE = -100;
 int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0, double best_y, double* mu_out,
@@ -873,6 +877,11 @@ int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0
     }
     HIPCHK(g->partial.ensure(sizeof(double) * T * Mc));
     HIPCHK(g->mu_c.ensure(sizeof(double) * Mc));
+    if (rblocks > 0) {
+        HIPCHK(g->pr_mut.ensure(sizeof(double) * M));
+        HIPCHK(g->pr_eps.ensure(sizeof(double) * M));
+        HIPCHK(g->pr_nrm.ensure(sizeof(double) * 4));
+    }
     const int64_t nchunk = (M + Mc - 1) / Mc;
     if (!more) {
         g->passes.clear();
@@ -886,6 +895,8 @@ int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0
     if (oz) { int32_t rc = oz_planes_of_w(g); if (rc) return rc; }
     g->tm.contraction_engine = want_var ? (oz ? ABO_CONTRACT_INT8 : ABO_CONTRACT_FP64) : 0;
     g->tm.oz_nmod = oz ? g->oz_plan.n : 0;
+    // (prune_plan: fewer row blocks than the model has, so the tail is never empty)
+    if (rblocks > 0) HIPCHK(launch_tail_norms(g->st->Xs.as<double>(), g->alpha.as<double>(), (int)g->npts, g->dp, 256 * rblocks, g->pr_nrm.as<double>(), s));
     for (int64_t c = 0; c < nchunk; ++c) {
         const int64_t j0 = c * Mc;
         const int64_t m = (M - j0) < Mc ? (M - j0) : Mc;
@@ -916,6 +927,14 @@ int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0
         }
         PHASE_EVENT(e[0], s);
         HIPCHK(launch_kgen(ka, s));
+        if (rblocks > 0) {
+            KgenTailArgs kt{};
+            kt.Xs = ka.Xs; kt.Z = Zd; kt.alpha = ka.alpha; kt.norms = g->pr_nrm.as<double>();
+            kt.mu_tail = g->pr_mut.as<double>(); kt.eps = g->pr_eps.as<double>();
+            kt.M = Mpts; kt.j0 = j0; kt.Mc = mcp; kt.N = (int)g->npts; kt.Np = (int)Np; kt.k0 = ka.res_kmax; kt.d = g->d; kt.dp = g->dp; kt.family = ka.family;
+            kt.s = ka.s; kt.sigma_f2 = ka.sigma_f2; kt.mean_c = ka.mean_c;
+            HIPCHK(launch_kgen_tail(kt, s));
+        }
         PHASE_EVENT(e[1], s);
         if (oz) {
             OzVarArgs oa{};
@@ -948,6 +967,7 @@ int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0
         fa.T = (var_out || score_out) ? (rblocks > 0 && 2 * rblocks < T ? 2 * rblocks : T) : 0; fa.Mc = mcp; fa.kind = kind; fa.sigma_f2 = g->prm.sigma_f2;
         fa.p0 = p0; fa.best_y = best_y;
         fa.prior_grad = grad_prior_var(g); fa.pc = pc; fa.point_major = point_major; fa.Mpts = Mpts;
+        if (rblocks > 0) { fa.mu_tail = g->pr_mut.as<double>(); fa.mu_eps = g->pr_eps.as<double>(); }
         PHASE_EVENT(e[4], s);
         HIPCHK(launch_finalize(fa, s));
         PHASE_EVENT(e[5], s);
@@ -3680,6 +3700,26 @@ int32_t abo_test_prune_bounds(abo_gp* g, double* out, int64_t M) {
     HIPCHK(hipSetDevice(g->prm.device));
     HIPCHK(hipMemcpyAsync(out, g->pr_ub.p, sizeof(double) * M, hipMemcpyDeviceToHost, g->stream));
     HIPCHK(wait_stream(g->stream));
+    return ABO_OK;
+}
+
+int32_t abo_test_prune_mean(abo_gp* g, double* mu, double* eps, int64_t M) {
+    if (!g || !mu || !eps || M < 0) return fail(ABO_EINVAL, "abo_test_prune_mean: bad argument");
+    if (!g->pst.bound_rows || g->pr_mut.cap < sizeof(double) * (size_t)M || g->pr_eps.cap < sizeof(double) * (size_t)M)
+        return fail(ABO_EINVAL, "abo_test_prune_mean: the last abo_acq on this handle ran no bound pass over %lld candidates", (long long)M);
+    HIPCHK(hipSetDevice(g->prm.device));
+    HIPCHK(hipMemcpyAsync(mu, g->pr_mut.p, sizeof(double) * M, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(eps, g->pr_eps.p, sizeof(double) * M, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(wait_stream(g->stream));
+    return ABO_OK;
+}
+
+int32_t abo_test_kappa_tail(int32_t device, int32_t family, const double* d2, double* out, int64_t n) {
+    if (!d2 || !out || n < 0) return fail(ABO_EINVAL, "abo_test_kappa_tail: bad argument");
+    if (family < ABO_KERNEL_SE || family > ABO_KERNEL_MATERN32) return fail(ABO_EINVAL, "abo_test_kappa_tail: unknown family");
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(launch_kappa_tail_test(family, d2, out, n, nullptr));
+    HIPCHK(wait_stream(nullptr));
     return ABO_OK;
 }
 

@@ -16,8 +16,7 @@ constexpr int KSTEP = 512;    // k per sweep step (256 threads × 2)
 // the 16 candidate rows of a workgroup against this lane's two training points
 // RES: 0 = no residue output; n > 0 = residue planes for exactly n moduli, unrolled over the compile-time tables of abo_oz_dev.h
 // (instantiated for the default plan, n = 14; other moduli counts go through the separate quantiser of ozaki.hip)
-// EMIT = false (RES != 0 only): training columns past KgenArgs::res_kmax — the planes are not written, the non-finite check stays
-template <int FAM, int DP, bool FULL, int RES, bool EMIT = true>
+template <int FAM, int DP, bool FULL, int RES>
 __device__ __forceinline__ void kgen_rows(const KgenArgs& p, const double (*zs)[DP], const double (&x0)[DP], const double (&x1)[DP],
                                           double s0, double s1, double a0, double a1, int jb, int k, double (&mu)[JT], int* lds_bad) {
     const double rsc = RES != 0 ? __builtin_ldexp(1.0, p.res_sK) : 0.0;
@@ -47,7 +46,7 @@ __device__ __forceinline__ void kgen_rows(const KgenArgs& p, const double (*zs)[
             // the int8-residue engine's image of the pair: two bytes per modulus (a wave writes one 128-byte line per row and plane)
             if (!(__builtin_fabs(v0) < 1.0e300) || !(__builtin_fabs(v1) < 1.0e300)) lds_bad[jj] = 1;
         }
-        if constexpr (RES != 0 && EMIT) {
+        if constexpr (RES != 0) {
             // plane offset = (uniform) row part + (per-lane, row-independent) k part: the stores take a scalar base and a 32-bit lane offset
             const unsigned koff = (unsigned)(((k >> 6) << 14) + (k & 63));
             const int64_t rowoff = ((int64_t)((jb + jj) >> 8) * (p.res_ld >> 6)) * 16384 + ((jb + jj) & 255) * 64;
@@ -60,8 +59,9 @@ __device__ __forceinline__ void kgen_rows(const KgenArgs& p, const double (*zs)[
     }
 }
 
-// PART (RES != 0 only): the residue planes are written for the training columns k < p.res_kmax alone (the bound pass of the pruned
-// top-k selection contracts only the first row blocks of W, which read no further); μ walks all N columns in the same order as ever
+// PART (RES != 0 only): the sweep ends at the training column p.res_kmax (the bound pass of the pruned top-k selection contracts only
+// the first row blocks of W, which read no further): planes, non-finite check and μ for the columns k < res_kmax — the same code and
+// bits per pair as the full launch; the other columns' part of μ is the work of kgen_tail.hip
 template <int FAM, int DP, int RES, bool PART = false>
 __global__ void __launch_bounds__(256) kgen_kernel(KgenArgs p) {
     __shared__ double zs[JT][DP];
@@ -82,9 +82,10 @@ __global__ void __launch_bounds__(256) kgen_kernel(KgenArgs p) {
 #pragma unroll
     for (int jj = 0; jj < JT; ++jj) mu[jj] = 0.0;
 
-    for (int k0 = 0; k0 < p.Np; k0 += KSTEP) {
+    const int kend = PART ? p.res_kmax : p.Np;          // (a multiple of 128: whole waves)
+    for (int k0 = 0; k0 < kend; k0 += KSTEP) {
         const int k = k0 + 2 * t;
-        if (k < p.Np) {
+        if (k < kend) {
             double x0[DP], x1[DP];
             const double* xp = p.Xs + (int64_t)k * DP;
             if constexpr (DP >= 2) {
@@ -105,12 +106,7 @@ __global__ void __launch_bounds__(256) kgen_kernel(KgenArgs p) {
             if (p.alpha) { a0 = p.alpha[k]; a1 = p.alpha[k + 1]; }
             // a workgroup whose 16 rows are all real candidates runs the branch-free body; an edge workgroup (the one-row
             // launch of a bordered append above all) skips the kernel evaluations of its padding rows
-            bool emit = true;
-            if constexpr (PART) emit = k0 + 128 * __builtin_amdgcn_readfirstlane(t >> 6) < p.res_kmax;   // wave-uniform: res_kmax is a multiple of 128
-            if (PART && !emit) {
-                if (p.j0 + jb + JT <= p.M) kgen_rows<FAM, DP, true, RES, false>(p, zs, x0, x1, s0, s1, a0, a1, jb, k, mu, bad);
-                else kgen_rows<FAM, DP, false, RES, false>(p, zs, x0, x1, s0, s1, a0, a1, jb, k, mu, bad);
-            } else if (p.j0 + jb + JT <= p.M) kgen_rows<FAM, DP, true, RES>(p, zs, x0, x1, s0, s1, a0, a1, jb, k, mu, bad);
+            if (p.j0 + jb + JT <= p.M) kgen_rows<FAM, DP, true, RES>(p, zs, x0, x1, s0, s1, a0, a1, jb, k, mu, bad);
             else kgen_rows<FAM, DP, false, RES>(p, zs, x0, x1, s0, s1, a0, a1, jb, k, mu, bad);
         }
     }
@@ -139,7 +135,7 @@ static hipError_t launch_kgen_dp(const KgenArgs& a, hipStream_t s) {
     dim3 grid(a.Mc / JT), block(256);
     if constexpr (RES != 0) {
         if (a.res_kmax > 0) {
-            if (a.res_kmax % 128) return hipErrorInvalidValue;
+            if (a.res_kmax % 128 || a.res_kmax > a.Np) return hipErrorInvalidValue;
             switch (a.dp) {
                 case 1: hipLaunchKernelGGL((kgen_kernel<FAM, 1, RES, true>), grid, block, 0, s, a); break;
                 case 2: hipLaunchKernelGGL((kgen_kernel<FAM, 2, RES, true>), grid, block, 0, s, a); break;

@@ -29,7 +29,12 @@ __global__ void __launch_bounds__(256) finalize_kernel(FinalizeArgs p) {
         if (o > 0) prior = p.prior_grad;
     }
     const double var = prior - q + 1e-18;
-    const double mu = p.mu_in[j];
+    double mu = p.mu_in[j];
+    if (p.mu_tail) {
+        mu += p.mu_tail[gj];
+        p.mu_tail[gj] = mu;
+        mu -= p.mu_eps[gj];          // EI and UCB (β ≥ 0) do not increase with μ: the bound is taken at the low end (prune_keep)
+    }
     if (p.mu_out) p.mu_out[gj] = mu;
     if (p.var_out) p.var_out[gj] = var;
     if (p.score_out) p.score_out[gj] = acq_score(p.kind, mu, var, p.p0, p.best_y);
@@ -683,17 +688,25 @@ hipError_t launch_gather_points(const double* Z, const int64_t* idx, int64_t idx
 }
 
 // ---- pruned top-k selection: which candidates still need the full variance ---------------------------------------------------------------
-// ub[j] is the score computed from the exact μ_j and σ²_R(j) = k_zz − Σ_{i<R} V_ij² + 1e-18 ≥ σ²(j): finalize_kernel adds the row
-// blocks' sums in order, so the R-row sum is a prefix of the full one and, the later terms being ≥ 0 and fp64 addition monotone, the
-// COMPUTED σ²_R is ≥ the computed σ² as well.  What remains is whether acq_score, as computed, is non-decreasing in var at fixed μ:
-//   UCB  −μ + β·sqrt(max(var, 0)), β ≥ 0: sqrt, the product and the sum are each correctly rounded, hence monotone — no margin needed.
-//   EI   var ≤ 1e-12 gives max(Δ, 0) ≤ the exact EI of any larger var; otherwise Δ·Φ(z) + σ·φ(z), z = Δ/σ.  Relative error of a term, in
+// ub[j] is the score computed from μ̃_j − ε_j ≤ μ_j (the full pass's computed mean; ε_j from kgen_tail.hip, which sums the columns past
+// the bound's row blocks with shortened arithmetic and proves |μ̃_j − μ_j| ≤ ε_j — the subtraction's own rounding is inside ε_j) and from
+// σ²_R(j) = k_zz − Σ_{i<R} V_ij² + 1e-18 ≥ σ²(j): finalize_kernel adds the row blocks' sums in order, so the R-row sum is a prefix of the
+// full one and, the later terms being ≥ 0 and fp64 addition monotone, the COMPUTED σ²_R is ≥ the computed σ² as well.  The exact EI and
+// the exact UCB (β ≥ 0) do not decrease with var and do not increase with μ (∂EI/∂μ = −Φ ≤ 0), so the exact score at (μ̃ − ε, σ²_R)
+// dominates the exact score at (μ, σ²).  What remains is how far acq_score, as computed, is from monotone in either argument:
+//   UCB  −μ + β·sqrt(max(var, 0)), β ≥ 0: sqrt, the product and the sum are each correctly rounded, hence monotone in var and in −μ — no
+//        margin needed.
+//   EI   var ≤ 1e-12 gives max(Δ, 0), monotone in −μ and ≤ the exact EI of any larger var; otherwise Δ·Φ(z) + σ·φ(z), z = Δ/σ.  Relative error of a term, in
 //        units of 2⁻⁵³: a few from erfc / exp / sqrt and the products; z² ≤ 1416 from the rounding of z in each of Φ(z) (d ln Φ/dz ≤
 //        |z| + 1) and φ(z); 708 from the rounding of the argument −z²/2 of exp (beyond z² = 1416 φ leaves the normal range) — below
 //        2200 together.  For Δ < 0 the two terms cancel: Δ·Φ + σ·φ = σ·φ·(1 − |z|·Φ(−|z|)/φ) and, by the Mills-ratio bound
 //        Φ(−x)/φ(x) ≤ (x² + 2)/(x³ + 3x), 1 − |z|Φ/φ ≥ 1/(z² + 3): the sum's relative error is at most z² + 3 ≤ 1500 times a term's.
 //        1500·2200·2⁻⁵³ < 3.7·10⁻¹⁰ < 2⁻³⁰ = PRUNE_REL (10⁻⁹ of the score: no effect on how much is pruned).  Where Φ or φ leave the
 //        normal range both terms are below 2⁻¹⁰²² in magnitude and so is any error of their sum: PRUNE_ABS = 2⁻¹⁰²², the smallest normal.
+//        The relative error ρ < 3.7·10⁻¹⁰ is that of the COMPUTED EI against the exact EI of its own arguments, whichever argument moved
+//        (Δ = (best − ξ) − μ is one rounding of an exact difference, and its effect is the z-term already counted): computed bound ≥
+//        (1 − ρ)·exact bound ≥ (1 − ρ)·exact score ≥ (1 − ρ)/(1 + ρ)·computed score, and (1 + 2⁻³⁰)(1 − ρ)/(1 + ρ) > 1 needs 2ρ < 2⁻³⁰ =
+//        9.3·10⁻¹⁰: PRUNE_REL stays as it is with the bound taken at μ̃ − ε.
 // A NaN bound, score or threshold keeps the candidate (NaN ranks first in the selection's order).
 __device__ __forceinline__ bool prune_keep(double ub, double tau) {
     return !(ub + fabs(ub) * PRUNE_REL + PRUNE_ABS < tau);

@@ -731,6 +731,12 @@ int32_t abo_test_prune_plan(int64_t rows, int64_t M, int32_t k, int32_t want_sco
 int32_t abo_test_prune_force(int32_t rblocks, int32_t mode);
 /* out[0..M) (host) = the upper bounds the last abo_acq on this handle computed in its bound pass */
 int32_t abo_test_prune_bounds(abo_gp* gp, double* out, int64_t M);
+/* mu[0..M), eps[0..M) (host) = the mean μ̃ the last abo_acq on this handle computed in its bound pass (first row blocks' columns by the
+ * full generator, the others by the shortened sequences of csrc/kgen_tail.hip) and the distance ε it proved to the full pass's mean:
+ * the bounds above are scores at μ̃ − ε */
+int32_t abo_test_prune_mean(abo_gp* gp, double* mu, double* eps, int64_t M);
+/* out[i] = kappa_tail(family, d2[i]): the shortened kernel evaluation of that pass (csrc/abo_kappa.h), without sigma_f2 */
+int32_t abo_test_kappa_tail(int32_t device, int32_t family, const double* d2, double* out, int64_t n);
 /* The int8-residue engine's host constants for n moduli (no GPU needed): p[16] moduli, tables[4][16] = {1/p, 2^26 mod p
  * (symmetric), head and tail of (P/p)·((P/p)⁻¹ mod p)}, scal[3] = {head of P, tail of P, 1/P}, *eP with 2^eP ≤ P/4. */
 int32_t abo_test_oz_plan(int32_t n, int32_t* p, double* tables, double* scal, int32_t* eP);
