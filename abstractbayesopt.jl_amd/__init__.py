@@ -3,8 +3,8 @@ AbstractSurrogate / AbstractAcquisition interface (hot path only: update → pos
 top-k).  Import as ``import abstractbayesopt.jl_amd as abo``."""
 from . import _lib, acquisition, distributed, incremental, multigpu, synth, thompson
 from ._lib import AboError, DimensionMismatch, PosDefException
-from .acquisition import (AbstractAcquisition, EnsembleAcquisition, ExpectedImprovement, ProbabilityImprovement,
-                          UpperConfidenceBound, device_latin_hypercube, evaluate, latin_hypercube,
+from .acquisition import (AbstractAcquisition, EnsembleAcquisition, ExpectedImprovement, LogExpectedImprovement,
+                          ProbabilityImprovement, UpperConfidenceBound, device_latin_hypercube, evaluate, latin_hypercube,
                           optimize_acquisition, optimize_acquisition_device, acquisition_value_and_grad, refine_starts,
                           update_and_evaluate)
 from .domains import ContinuousDomain

@@ -27,7 +27,7 @@ EXPORTS = ["abo_create", "abo_set_contraction", "abo_create_grad", "abo_predict_
            "abo_paths_append", "abo_paths_attach", "abo_paths_detach", "abo_paths_top", "abo_paths_values", "abo_paths_append_stats_get"]
 TEST_EXPORTS = ["abo_test_gemm_nt", "abo_test_kappa", "abo_test_oz_plan", "abo_test_oz_contract", "abo_test_acq_grad",
                 "abo_test_acq_grad_terms", "abo_test_prune_plan", "abo_test_prune_force", "abo_test_prune_bounds", "abo_test_prune_mean",
-                "abo_test_kappa_tail"]
+                "abo_test_kappa_tail", "abo_test_acq_partials"]
 ABI_VERSION = 7
 CONTRACT_AUTO, CONTRACT_FP64, CONTRACT_INT8 = 0, 1, 2
 # what abo_update / abo_mgpu_update ran (include/abo_hip.h)
@@ -241,6 +241,7 @@ def lib():
     L.abo_mgpu_optimize_acquisition.argtypes = L.abo_optimize_acquisition.argtypes
     if hooks:
         L.abo_test_acq_grad.argtypes = [vp, i32, f64, f64, vp, i64, i32, vp, vp]
+        L.abo_test_acq_partials.argtypes = [i32, vp, vp, i64, i32, f64, f64, vp, vp, vp]
     tp = C.POINTER(AboAcqTerm)
     if hooks:
         L.abo_test_acq_grad_terms.argtypes = [vp, tp, i32, vp, i64, i32, vp, vp]

@@ -16,7 +16,7 @@ from . import _lib
 from ._lib import DEVICE, HOST
 from .surrogate import AbstractSurrogate, HipStandardGP, _get_minimum, as_points
 
-ACQ_EI, ACQ_UCB, ACQ_PI, ACQ_MEAN, ACQ_GRADNORM_UCB = 0, 1, 2, 3, 4
+ACQ_EI, ACQ_UCB, ACQ_PI, ACQ_MEAN, ACQ_GRADNORM_UCB, ACQ_LOGEI = 0, 1, 2, 3, 4, 5
 MAX_TERMS = 8
 
 
@@ -45,6 +45,22 @@ class ExpectedImprovement(AbstractAcquisition):
     xi: float
     best_y: float
     kind = ACQ_EI
+
+    def _p0(self):
+        return float(self.xi)
+
+    def _best(self):
+        return float(self.best_y)
+
+
+@dataclass(frozen=True)
+class LogExpectedImprovement(AbstractAcquisition):
+    """LogExpectedImprovement(ξ, best_y): log EI, finite for every finite z = Δ/σ where EI itself underflows to 0 and every
+    candidate ties (no reference counterpart; Ament et al. 2023; include/abo_hip.h: ABO_ACQ_LOGEI).  Same arg-max and order as
+    ExpectedImprovement wherever EI > 0; `update` takes best_y as EI's does."""
+    xi: float
+    best_y: float
+    kind = ACQ_LOGEI
 
     def _p0(self):
         return float(self.xi)
@@ -120,13 +136,16 @@ class EnsembleAcquisition(AbstractAcquisition):
                 and self.acquisitions == other.acquisitions)
 
 
+_TAKES_BEST_Y = (ExpectedImprovement, LogExpectedImprovement, ProbabilityImprovement)
+
+
 def update(acq: AbstractAcquisition, ys, surrogate: AbstractSurrogate):
-    """update(acq, ys, surrogate): EI/PI take best_y = _get_minimum(surrogate, ys)
+    """update(acq, ys, surrogate): EI/LogEI/PI take best_y = _get_minimum(surrogate, ys)
     (ExpectedImprovement.jl:81-83, ProbabilityImprovement.jl:79-82); UCB is unchanged
     (UpperConfidenceBound.jl:60-62)."""
     if isinstance(acq, EnsembleAcquisition):                            # EnsembleAcq.jl:57-62
         return EnsembleAcquisition(acq.weights, [update(a, ys, surrogate) for a in acq.acquisitions])
-    if isinstance(acq, (ExpectedImprovement, ProbabilityImprovement)):
+    if isinstance(acq, _TAKES_BEST_Y):
         return replace(acq, best_y=_get_minimum(surrogate, ys))
     return acq
 
@@ -189,7 +208,7 @@ def update_and_evaluate(acq: AbstractAcquisition, model: HipStandardGP, xs, ys, 
     if _is_torch(ys):
         yt = ys.reshape(-1).contiguous()
         yspace, yp, ny, ykeep = (DEVICE if yt.is_cuda else HOST), yt.data_ptr(), yt.shape[0], yt
-        needs_min = best_y is None and isinstance(acq, (ExpectedImprovement, ProbabilityImprovement))
+        needs_min = best_y is None and isinstance(acq, _TAKES_BEST_Y)
         ymin = float(yt.min().item()) if needs_min else best_y
     else:
         ya = np.ascontiguousarray(np.asarray(ys, dtype=np.float64).reshape(-1))
@@ -199,7 +218,7 @@ def update_and_evaluate(acq: AbstractAcquisition, model: HipStandardGP, xs, ys, 
         raise _lib.DimensionMismatch(f"xs has {n} points but ys has {ny} values")
     if xspace != yspace:
         raise ValueError("xs and ys must both be host arrays or both be tensors on the model's GPU")
-    if isinstance(acq, (ExpectedImprovement, ProbabilityImprovement)):
+    if isinstance(acq, _TAKES_BEST_Y):
         acq = replace(acq, best_y=ymin)
     zp, m, dz, zspace, zkeep = as_points(x)
     if zspace == DEVICE:
@@ -267,7 +286,7 @@ def _walk_terms(a, w, grad_ok, out) -> bool:
     if isinstance(a, EnsembleAcquisition):
         return all(_walk_terms(m, w * float(wi), grad_ok, out) for wi, m in zip(a.weights, a.acquisitions))
     k = getattr(a, "kind", None)
-    if k not in (ACQ_EI, ACQ_UCB, ACQ_PI, ACQ_MEAN, ACQ_GRADNORM_UCB):
+    if k not in (ACQ_EI, ACQ_UCB, ACQ_PI, ACQ_MEAN, ACQ_GRADNORM_UCB, ACQ_LOGEI):
         return False
     if k == ACQ_GRADNORM_UCB and not grad_ok:
         return False

@@ -4,6 +4,7 @@
 //   PI   src/acquisition_functions/ProbabilityImprovement.jl:38-63 (incl. the σ² ≤ 1e-12 → max(Δ,0) quirk)
 //   GradientNormUCB  src/acquisition_functions/gradNormUCB.jl:43-51
 //   EnsembleAcquisition  src/acquisition_functions/EnsembleAcq.jl:53-55  (Σ wᵢ·acqᵢ on one posterior)
+//   LogEI  no reference counterpart: log EI, finite for every finite z (Ament et al. 2023)
 #pragma once
 #include "abo_kernels.h"
 #include "../../include/abo_hip.h"
@@ -30,10 +31,44 @@ __device__ __forceinline__ bool before(uint64_t ka, int64_t ia, uint64_t kb, int
 __device__ __forceinline__ double norm_cdf(double z) { return 0.5 * erfc(-z * 0.70710678118654752440084436210485); }
 __device__ __forceinline__ double norm_pdf(double z) { return exp(-0.5 * z * z) * 0.39894228040143267793994605993438; }
 
+// log h(z), h(z) = φ(z) + z·Φ(z) (EI = σ·h(z)), in three ranges of z; with q = Φ(z)/φ(z) the two ratios the partial derivatives
+// of LogEI need come out of the same quantities, never as a quotient of two underflowed ones:
+//   z > −1        h from norm_pdf / norm_cdf (φ and zΦ cancel by at most a factor 3 here; φ → 0 for large z leaves h = z)
+//   −64 < z ≤ −1  q = √(π/2)·erfcx(|z|/√2), h = φ·(1 + z·q): log h = −z²/2 − ½log 2π + log1p(z·q).  1 + z·q ≈ 1/z² cancels up to
+//                 12 bits at the far end, where −z²/2 ≈ −2048 carries the value: the error stays below an ulp of the sum
+//   z ≤ −64       h = φ·u·S(u), q = T(u)/|z|, u = 1/z²: S = 1 − 3u + 15u² − 105u³ + 945u⁴, T = 1 − u + 3u² − 15u³ + 105u⁴ (the
+//                 asymptotic series of the Mills ratio; first dropped terms 10395u⁵ < 10⁻¹⁴ and 945u⁵ < 10⁻¹⁵)
+// cdf_h = Φ/h, pdf_h = φ/h.  A NaN z fails every comparison and comes out of the last range as NaN; z² overflows beyond
+// |z| ≈ 1.3·10¹⁵⁴, where log h itself is below −DBL_MAX: −Inf.
+constexpr double LOGEI_HALF_LOG_2PI = 0.91893853320467274178032973640562;
+constexpr double LOGEI_SQRT_HALF_PI = 1.2533141373155002512078826424055;
+__device__ __forceinline__ double log_h(double z, double& cdf_h, double& pdf_h) {
+    if (z > -1.0) {
+        const double cdf = norm_cdf(z), pdf = norm_pdf(z), h = pdf + z * cdf;
+        cdf_h = cdf / h; pdf_h = pdf / h;
+        return log(h);
+    }
+    if (z > -64.0) {
+        const double q = LOGEI_SQRT_HALF_PI * erfcx(-z * 0.70710678118654752440084436210485), zq = z * q;
+        pdf_h = 1.0 / (1.0 + zq); cdf_h = q * pdf_h;
+        return -0.5 * z * z - LOGEI_HALF_LOG_2PI + log1p(zq);
+    }
+    const double z2 = z * z, u = 1.0 / z2;
+    const double S = u * (-3.0 + u * (15.0 + u * (-105.0 + u * 945.0)));                  // S − 1
+    const double T = 1.0 + u * (-1.0 + u * (3.0 + u * (-15.0 + u * 105.0)));
+    pdf_h = z2 / (1.0 + S); cdf_h = -z * T / (1.0 + S);
+    return -0.5 * z2 - LOGEI_HALF_LOG_2PI - 2.0 * log(-z) + log1p(S);
+}
+
 __device__ __forceinline__ double acq_score(int kind, double mu, double var, double p0, double best_y) {
     if (kind == ABO_ACQ_UCB) return -mu + p0 * sqrt(fmax(var, 0.0));
     if (kind == ABO_ACQ_MEAN) return -mu;
     const double delta = (best_y - p0) - mu;
+    if (kind == ABO_ACQ_LOGEI) {                                    // log EI: log σ + log h(z); exp of it is EI on both branches
+        if (var <= 1e-12) return log(fmax(delta, 0.0));
+        double a, b;
+        return 0.5 * log(var) + log_h(delta / sqrt(var), a, b);
+    }
     if (var <= 1e-12) return fmax(delta, 0.0);
     const double sg = sqrt(var);
     const double z = delta / sg;
@@ -51,6 +86,14 @@ __device__ __forceinline__ double acq_value_and_partials(int kind, double mu, do
     }
     if (kind == ABO_ACQ_MEAN) { dmu = -1.0; dvar = 0.0; return -mu; }
     const double delta = (best_y - p0) - mu;
+    if (kind == ABO_ACQ_LOGEI) {                                    // ∂/∂μ = −Φ/(σ·h), ∂/∂σ² = φ/(2σ²·h)
+        if (var <= 1e-12) { dmu = delta > 0.0 ? -1.0 / delta : 0.0; dvar = 0.0; return log(fmax(delta, 0.0)); }
+        const double sg = sqrt(var);
+        double cdf_h, pdf_h;
+        const double lh = log_h(delta / sg, cdf_h, pdf_h);
+        dmu = -cdf_h / sg; dvar = 0.5 * pdf_h / var;
+        return 0.5 * log(var) + lh;
+    }
     if (var <= 1e-12) { dmu = delta > 0.0 ? -1.0 : 0.0; dvar = 0.0; return fmax(delta, 0.0); }
     const double sg = sqrt(var), z = delta / sg, cdf = norm_cdf(z), pdf = norm_pdf(z);
     if (kind == ABO_ACQ_EI) { dmu = -cdf; dvar = 0.5 * pdf / sg; return delta * cdf + sg * pdf; }

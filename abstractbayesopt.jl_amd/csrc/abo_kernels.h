@@ -307,6 +307,9 @@ hipError_t launch_cand_gemv(const double* Kzx, int64_t ld, const double* v, int 
 // score[j] = acq(mu[j], var[j])
 hipError_t launch_score(const double* mu, const double* var, double* score, int64_t M, int kind, double p0, double best_y,
                         hipStream_t s);
+// f[j], dmu[j], dvar[j] = the epilogue's value and its partial derivatives with respect to μ and σ² (what the refinement evaluates)
+hipError_t launch_score_partials(const double* mu, const double* var, double* f, double* dmu, double* dvar, int64_t M, int kind, double p0,
+                                 double best_y, hipStream_t s);
 
 // rec = {tv[0], (double)ti[0], mu[ti[0] − idx_base], Z[ti[0] − idx_base][0..d)} (zeros for ti[0] < 0): a device's pick
 // record of one greedy q-EI sub-step, 3 + d doubles
@@ -396,10 +399,13 @@ hipError_t launch_lhs(double* Z, int64_t n, int d, const double* lower, const do
 
 // ---- objectives of the acquisition stage: a weighted sum of epilogues on ONE posterior evaluation ------------------
 // f(x) = Σ_t w_t · acq_t(x)  (EnsembleAcquisition, EnsembleAcq.jl:53-55; a plain acquisition function is one term of weight 1).
-// acq_t ∈ {EI, UCB, PI, MEAN} on the function-value posterior (μ, σ²), or GRADNORM_UCB on the posterior of the gradient outputs
+// acq_t ∈ {EI, UCB, PI, MEAN, LOGEI} on the function-value posterior (μ, σ²), or GRADNORM_UCB on the posterior of the gradient outputs
 // of a gradient-enhanced model (gradNormUCB.jl:43-51).
 constexpr int MAX_TERMS = 8;
 constexpr int ACQ_GRADNORM_UCB = 4;            // == ABO_ACQ_GRADNORM_UCB (include/abo_hip.h)
+constexpr int ACQ_LOGEI = 5;                   // == ABO_ACQ_LOGEI
+// the kinds of the entry points that take ONE kind: the epilogues on (μ, σ²) — EI, UCB, PI, MEAN (0 … 3) and LOGEI
+inline bool plain_kind(int kind) { return (kind >= 0 && kind < ACQ_GRADNORM_UCB) || kind == ACQ_LOGEI; }
 struct AcqTerms {
     int n;
     int kind[MAX_TERMS];
@@ -461,14 +467,17 @@ hipError_t launch_acq_grad_via_eval(const RefineArgs& a, int S, const double* me
 hipError_t launch_gather_points(const double* Z, const int64_t* idx, int64_t idx_base, int k, int d, double* out, hipStream_t s);
 
 // ---- pruned top-k selection (misc.hip): candidates whose guarded upper bound reaches the threshold, compacted in index order ----------
-// Margins of the guard ub + |ub|·PRUNE_REL + PRUNE_ABS (derivation: misc.hip, prune_keep)
+// Margins of the guard ub + |ub|·PRUNE_REL + abs_margin (derivation: misc.hip, prune_keep); abs_margin = PRUNE_ABS for EI and UCB,
+// PRUNE_ABS_LOGEI for the log-valued LOGEI, whose error does not vanish with the score
 constexpr double PRUNE_REL = 0x1p-30;
 constexpr double PRUNE_ABS = 0x1p-1022;
+constexpr double PRUNE_ABS_LOGEI = 0x1p-30;
 constexpr int PRUNE_SCAN_E = 1024;       // candidates per workgroup of the compaction
-// sel[0 … *count) = the indices j < M, ascending, with !(guard(ub[j]) < *tau) — a NaN on either side keeps the candidate, as the
+// sel[0 … *count) = the indices j < M, ascending, with !(guard(ub[j], abs_margin) < *tau) — a NaN on either side keeps the candidate, as the
 // selection's order ranks NaN first; *count = their number.  blk: ⌈M / PRUNE_SCAN_E⌉ ints of scratch; sel: room for M entries.
 // Stream-ordered, no atomics: the same list on every run.
-hipError_t launch_prune_compact(const double* ub, int64_t M, const double* tau, int* blk, int64_t* sel, int64_t* count, hipStream_t s);
+hipError_t launch_prune_compact(const double* ub, int64_t M, const double* tau, double abs_margin, int* blk, int64_t* sel, int64_t* count,
+                                hipStream_t s);
 // top_idx[e] = sel[top_idx[e]] + idx_base for e < k (−1 stays): positions in a compacted list back to candidate indices
 hipError_t launch_prune_map(int64_t* top_idx, int k, const int64_t* sel, int64_t idx_base, hipStream_t s);
 

@@ -1679,7 +1679,7 @@ int32_t make_terms(const abo_gp* g, const abo_acq_term* terms, int32_t n, AcqTer
     out->n = n;
     for (int i = 0; i < n; ++i) {
         const int k = terms[i].kind;
-        if (k < ABO_ACQ_EI || k > ABO_ACQ_GRADNORM_UCB) return fail(ABO_EINVAL, "%s: unknown acquisition kind %d (term %d)", fn, k, i);
+        if (k < ABO_ACQ_EI || k > ABO_ACQ_LOGEI) return fail(ABO_EINVAL, "%s: unknown acquisition kind %d (term %d)", fn, k, i);
         if (k == ABO_ACQ_GRADNORM_UCB && (!g || g->p_out < 2))
             return fail(ABO_EINVAL, "%s: GradientNormUCB (term %d) needs a gradient-enhanced model", fn, i);
         if (!(terms[i].weight == terms[i].weight)) return fail(ABO_EINVAL, "%s: weight of term %d is not a number", fn, i);
@@ -1739,7 +1739,7 @@ int32_t score_terms_device(abo_gp* g, const double* Zd, int64_t M, const AcqTerm
 
 // ---- exact top-k without the full variance contraction (DESIGN.md "Pruned top-k selection") -------------------------------------------
 // The sum of squares over the first R rows of V = L⁻¹K_XZ is the variance reduction from the first R training points alone, so
-// σ²_R = k_zz − Σ_{i<R} V_ij² ≥ σ², and EI and UCB (β ≥ 0) do not decrease with σ: the score of (μ, σ²_R) bounds the score from above.
+// σ²_R = k_zz − Σ_{i<R} V_ij² ≥ σ², and EI, LogEI and UCB (β ≥ 0) do not decrease with σ: the score of (μ, σ²_R) bounds the score from above.
 // W = L⁻¹ being triangular, its first R rows cost (R/N)² of the contraction.
 struct PrunePlan {
     bool eligible;
@@ -1778,7 +1778,7 @@ PrunePlan prune_plan(int64_t rows, int64_t M, int k, bool want_scores, int kind,
     // the survivor pass costs S/M of the full pass it replaces (plus a gather of S points): it is the cheaper of the two for any
     // S < M, and is taken while it saves at least an eighth of the pass — far more than the extra launches cost
     pp.max_survivors = M - M / 8;
-    const bool monotone = kind == ABO_ACQ_EI || (kind == ABO_ACQ_UCB && p0 >= 0.0);
+    const bool monotone = kind == ABO_ACQ_EI || kind == ABO_ACQ_LOGEI || (kind == ABO_ACQ_UCB && p0 >= 0.0);
     // two passes pay from a few times the K0 exactly evaluated candidates on (M ≥ 4·K0: the threshold pass is at most a quarter of
     // what the selection can save); the compaction counts in ints and gathers with 32-bit element indices
     pp.eligible = prune_enabled() && k > 0 && !want_scores && monotone && p_out == 1 && int8_fused && rb < tblocks &&
@@ -1831,7 +1831,8 @@ int32_t prune_select(abo_gp* g, const double* Zd, int64_t M, const AcqTerms& t, 
     }
 #endif
     // 3. survivors: every candidate whose guarded bound reaches τ (the k that set τ among them), in index order
-    HIPCHK(launch_prune_compact(ub, M, tau, g->pr_blk.as<int>(), g->pr_sel.as<int64_t>(), count_d, s));
+    HIPCHK(launch_prune_compact(ub, M, tau, kind == ABO_ACQ_LOGEI ? PRUNE_ABS_LOGEI : PRUNE_ABS, g->pr_blk.as<int>(), g->pr_sel.as<int64_t>(),
+                                count_d, s));
     HIPCHK(hipEventRecord(g->evs()[PE + 2], s));
     int64_t S = 0;
     HIPCHK(hipMemcpyAsync(&S, count_d, sizeof(int64_t), hipMemcpyDeviceToHost, s));
@@ -1947,7 +1948,7 @@ int32_t abo::acq_ex(abo_gp* g, const double* Z, int64_t M, int32_t d, int32_t z_
                     int64_t* top_idx, int32_t top_space) {
     int32_t rc = check_fitted(g, d);
     if (rc) return rc;
-    if (kind < ABO_ACQ_EI || kind > ABO_ACQ_MEAN) return fail(ABO_EINVAL, "abo_acq: unknown acquisition kind %d", kind);
+    if (!plain_kind(kind)) return fail(ABO_EINVAL, "abo_acq: unknown acquisition kind %d", kind);
     return acq_terms_impl(g, Z, M, d, z_space, one_term(kind, p0, best_y), idx_base, scores, out_space, k, top_val, top_idx, top_space);
 }
 
@@ -2369,7 +2370,7 @@ int32_t abo_cand_acq(abo_gp* g, abo_cand* c, int32_t kind, double p0, double bes
 int32_t abo::cand_acq_ex(abo_gp* g, abo_cand* c, int32_t kind, double p0, double best_y, int64_t idx_base, double* scores,
                          int32_t out_space, int32_t k, double* top_val, int64_t* top_idx, int32_t top_space) {
     if (!g || !c) return fail(ABO_EINVAL, "abo_cand_acq: null argument");
-    if (kind < ABO_ACQ_EI || kind > ABO_ACQ_MEAN) return fail(ABO_EINVAL, "abo_cand_acq: unknown acquisition kind %d", kind);
+    if (!plain_kind(kind)) return fail(ABO_EINVAL, "abo_cand_acq: unknown acquisition kind %d", kind);
     if (k < 0) return fail(ABO_EINVAL, "abo_cand_acq: k = %d is negative", k);
     if (k > 0 && (!top_val || !top_idx)) return fail(ABO_EINVAL, "abo_cand_acq: k > 0 needs top_val and top_idx");
     if (g->prm.device != c->device) return fail(ABO_EINVAL, "candidate set lives on device %d, model on %d", c->device, g->prm.device);
@@ -3671,7 +3672,7 @@ int32_t abo_lhs(int32_t device, int64_t n, int32_t d, const double* lower, const
 int32_t abo_score(int32_t device, const double* mu, const double* var, int64_t M, int32_t kind, double p0, double best_y,
                   double* scores) {
     if (M < 0 || (M > 0 && (!mu || !var || !scores))) return fail(ABO_EINVAL, "abo_score: bad argument");
-    if (kind < ABO_ACQ_EI || kind > ABO_ACQ_MEAN) return fail(ABO_EINVAL, "abo_score: unknown acquisition kind %d", kind);
+    if (!plain_kind(kind)) return fail(ABO_EINVAL, "abo_score: unknown acquisition kind %d", kind);
     HIPCHK(hipSetDevice(device));
     HIPCHK(launch_score(mu, var, scores, M, kind, p0, best_y, nullptr));
     HIPCHK(wait_stream(nullptr));
@@ -3679,6 +3680,16 @@ int32_t abo_score(int32_t device, const double* mu, const double* var, int64_t M
 }
 
 #ifdef ABO_TEST_HOOKS
+int32_t abo_test_acq_partials(int32_t device, const double* mu, const double* var, int64_t M, int32_t kind, double p0, double best_y,
+                              double* f, double* dmu, double* dvar) {
+    if (M < 0 || (M > 0 && (!mu || !var || !f || !dmu || !dvar))) return fail(ABO_EINVAL, "abo_test_acq_partials: bad argument");
+    if (!plain_kind(kind)) return fail(ABO_EINVAL, "abo_test_acq_partials: unknown acquisition kind %d", kind);
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(launch_score_partials(mu, var, f, dmu, dvar, M, kind, p0, best_y, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
 int32_t abo_test_prune_plan(int64_t rows, int64_t M, int32_t k, int32_t want_scores, int32_t kind, double p0, int32_t p_out, int32_t int8_fused,
                             int32_t d, int64_t* out) {
     if (!out) return fail(ABO_EINVAL, "abo_test_prune_plan: null argument");

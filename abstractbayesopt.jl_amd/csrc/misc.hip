@@ -33,7 +33,7 @@ __global__ void __launch_bounds__(256) finalize_kernel(FinalizeArgs p) {
     if (p.mu_tail) {
         mu += p.mu_tail[gj];
         p.mu_tail[gj] = mu;
-        mu -= p.mu_eps[gj];          // EI and UCB (β ≥ 0) do not increase with μ: the bound is taken at the low end (prune_keep)
+        mu -= p.mu_eps[gj];          // EI, LogEI and UCB (β ≥ 0) do not increase with μ: the bound is taken at the low end (prune_keep)
     }
     if (p.mu_out) p.mu_out[gj] = mu;
     if (p.var_out) p.var_out[gj] = var;
@@ -121,6 +121,24 @@ hipError_t launch_score(const double* mu, const double* var, double* score, int6
                         hipStream_t s) {
     if (M <= 0) return hipSuccess;
     hipLaunchKernelGGL(score_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, mu, var, score, M, kind, p0, best_y);
+    return hipGetLastError();
+}
+
+// value and the partial derivatives ∂/∂μ, ∂/∂σ² of one epilogue on a given posterior: the arithmetic the refinement stage evaluates per
+// point (acq_value_and_partials), exposed for the test build (abo_test_acq_partials)
+__global__ void __launch_bounds__(256) score_partials_kernel(const double* mu, const double* var, double* f, double* dmu, double* dvar,
+                                                              int64_t M, int kind, double p0, double best_y) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= M) return;
+    double a, b;
+    f[j] = acq_value_and_partials(kind, mu[j], var[j], p0, best_y, a, b);
+    dmu[j] = a; dvar[j] = b;
+}
+
+hipError_t launch_score_partials(const double* mu, const double* var, double* f, double* dmu, double* dvar, int64_t M, int kind, double p0,
+                                 double best_y, hipStream_t s) {
+    if (M <= 0) return hipSuccess;
+    hipLaunchKernelGGL(score_partials_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, mu, var, f, dmu, dvar, M, kind, p0, best_y);
     return hipGetLastError();
 }
 
@@ -691,8 +709,8 @@ hipError_t launch_gather_points(const double* Z, const int64_t* idx, int64_t idx
 // ub[j] is the score computed from μ̃_j − ε_j ≤ μ_j (the full pass's computed mean; ε_j from kgen_tail.hip, which sums the columns past
 // the bound's row blocks with shortened arithmetic and proves |μ̃_j − μ_j| ≤ ε_j — the subtraction's own rounding is inside ε_j) and from
 // σ²_R(j) = k_zz − Σ_{i<R} V_ij² + 1e-18 ≥ σ²(j): finalize_kernel adds the row blocks' sums in order, so the R-row sum is a prefix of the
-// full one and, the later terms being ≥ 0 and fp64 addition monotone, the COMPUTED σ²_R is ≥ the computed σ² as well.  The exact EI and
-// the exact UCB (β ≥ 0) do not decrease with var and do not increase with μ (∂EI/∂μ = −Φ ≤ 0), so the exact score at (μ̃ − ε, σ²_R)
+// full one and, the later terms being ≥ 0 and fp64 addition monotone, the COMPUTED σ²_R is ≥ the computed σ² as well.  The exact EI (and
+// with it LogEI) and the exact UCB (β ≥ 0) do not decrease with var and do not increase with μ (∂EI/∂μ = −Φ ≤ 0), so the exact score at (μ̃ − ε, σ²_R)
 // dominates the exact score at (μ, σ²).  What remains is how far acq_score, as computed, is from monotone in either argument:
 //   UCB  −μ + β·sqrt(max(var, 0)), β ≥ 0: sqrt, the product and the sum are each correctly rounded, hence monotone in var and in −μ — no
 //        margin needed.
@@ -707,16 +725,28 @@ hipError_t launch_gather_points(const double* Z, const int64_t* idx, int64_t idx
 //        (Δ = (best − ξ) − μ is one rounding of an exact difference, and its effect is the z-term already counted): computed bound ≥
 //        (1 − ρ)·exact bound ≥ (1 − ρ)·exact score ≥ (1 − ρ)/(1 + ρ)·computed score, and (1 + 2⁻³⁰)(1 − ρ)/(1 + ρ) > 1 needs 2ρ < 2⁻³⁰ =
 //        9.3·10⁻¹⁰: PRUNE_REL stays as it is with the bound taken at μ̃ − ε.
+//   LOGEI  log EI of the same arguments: exact LogEI is monotone where EI is (log is increasing; var ≤ 1e-12 gives log max(Δ, 0), −Inf for
+//        Δ ≤ 0, ≤ the exact LogEI of any larger var).  The computed value L̃ = ½log σ² + log h(z) (abo_acq_dev.h: log_h) against the exact
+//        L of its own arguments, in units of u = 2⁻⁵³, absolute: z carries 3 roundings (Δ, sqrt, the quotient) and d log h/dz = Φ/h ≤
+//        |z| + 3/|z| for z ≤ −1 (≤ 1.91 above), so 3(z² + 3) from z; z² and 6(z² + 3) from −z²/2 and from z·q under log1p (erfcx and
+//        two products: 6 on z·q, |z·q| < 1, and d log1p/dx = 1/(1 + zq) ≤ z² + 3, the Mills-ratio bound above); 50 from h = φ + zΦ
+//        for z > −1 (cancellation ≤ 4.8 there); the logs' and the sums' own roundings 3(|log h| + 9) + 2·355 (|½log σ²| ≤ 355) + |L|.
+//        With z² ≤ 2|log h| for z ≤ −1 and |log h| ≤ |L| + 355: |L̃ − L| ≤ E(L) = (24|L| + 9000)·u < 2.7·10⁻¹⁵·|L| + 10⁻¹² — the bound on
+//        the computed LogEI's error that the margin covers.  Pruning is safe when s̃ ≤ guard(b̃) for exact s ≤ b (s the score, b the bound):
+//        s̃ ≤ s + E(s) and b̃ ≥ b − E(b).  For s ≥ −2|b| − 1, E(s) + E(b) ≤ (72|b| + 18024)·u < 2⁻³⁰·(|b̃| + 1) by a factor 10⁵ in the
+//        relative and 460 in the absolute part: PRUNE_REL as it is, PRUNE_ABS_LOGEI = 2⁻³⁰ (the relative term alone is 0 at b̃ = 0,
+//        EI = 1).  For s < −2|b| − 1, s̃ ≤ s(1 − 24u) + 9000u < b − E(b) ≤ b̃ without any margin.  2⁻³⁰ in LogEI is a factor 1 + 10⁻⁹ in
+//        EI: no effect on how much is pruned.  A bound of −Inf (EI bounded by exactly 0) makes the guard −Inf + Inf = NaN: kept.
 // A NaN bound, score or threshold keeps the candidate (NaN ranks first in the selection's order).
-__device__ __forceinline__ bool prune_keep(double ub, double tau) {
-    return !(ub + fabs(ub) * PRUNE_REL + PRUNE_ABS < tau);
+__device__ __forceinline__ bool prune_keep(double ub, double tau, double abs_margin) {
+    return !(ub + fabs(ub) * PRUNE_REL + abs_margin < tau);
 }
 
 // workgroup b owns candidates [b·1024, (b+1)·1024), thread t four consecutive ones: SCATTER = false counts the kept ones into blk[b];
 // SCATTER = true (blk now holds the exclusive offsets) writes their indices at blk[b] + rank inside the workgroup — index order
 template <bool SCATTER>
 __global__ void __launch_bounds__(256) prune_compact_kernel(const double* __restrict__ ub, int64_t M, const double* __restrict__ tau,
-                                                            int* __restrict__ blk, int64_t* __restrict__ sel) {
+                                                            double abs_margin, int* __restrict__ blk, int64_t* __restrict__ sel) {
     __shared__ int wsum[4];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int64_t j0 = (int64_t)blockIdx.x * PRUNE_SCAN_E + 4 * t;
@@ -724,7 +754,7 @@ __global__ void __launch_bounds__(256) prune_compact_kernel(const double* __rest
     bool keep[4];
     int mine = 0;
 #pragma unroll
-    for (int u = 0; u < 4; ++u) { keep[u] = j0 + u < M && prune_keep(ub[j0 + u], th); mine += keep[u]; }
+    for (int u = 0; u < 4; ++u) { keep[u] = j0 + u < M && prune_keep(ub[j0 + u], th, abs_margin); mine += keep[u]; }
     int incl = mine;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) { const int v = __shfl_up(incl, o); if (lane >= o) incl += v; }
@@ -765,12 +795,13 @@ __global__ void __launch_bounds__(1024) prune_scan_kernel(int* __restrict__ blk,
     if (t == 0) count[0] = carry;
 }
 
-hipError_t launch_prune_compact(const double* ub, int64_t M, const double* tau, int* blk, int64_t* sel, int64_t* count, hipStream_t s) {
+hipError_t launch_prune_compact(const double* ub, int64_t M, const double* tau, double abs_margin, int* blk, int64_t* sel, int64_t* count,
+                                hipStream_t s) {
     if (M <= 0 || M >= (int64_t)1 << 31) return hipErrorInvalidValue;      // (the counts are ints)
     const int nb = (int)((M + PRUNE_SCAN_E - 1) / PRUNE_SCAN_E);
-    hipLaunchKernelGGL(prune_compact_kernel<false>, dim3(nb), dim3(256), 0, s, ub, M, tau, blk, sel);
+    hipLaunchKernelGGL(prune_compact_kernel<false>, dim3(nb), dim3(256), 0, s, ub, M, tau, abs_margin, blk, sel);
     hipLaunchKernelGGL(prune_scan_kernel, dim3(1), dim3(1024), 0, s, blk, nb, count);
-    hipLaunchKernelGGL(prune_compact_kernel<true>, dim3(nb), dim3(256), 0, s, ub, M, tau, blk, sel);
+    hipLaunchKernelGGL(prune_compact_kernel<true>, dim3(nb), dim3(256), 0, s, ub, M, tau, abs_margin, blk, sel);
     return hipGetLastError();
 }
 

@@ -46,7 +46,8 @@ extern "C" {
                                   ABO_UPDATE_SHARED / _APPENDED / _REFIT; abo_cand_qei_mc; abo_paths_create, abo_paths_destroy,
                                   abo_paths_eval, abo_paths_eval_cand, abo_paths_stats_get (struct abo_paths_stats is new); abo_paths_append,
                                   abo_paths_attach, abo_paths_detach, abo_paths_top, abo_paths_values, abo_paths_append_stats_get
-                                  (struct abo_paths_append_stats is new) */
+                                  (struct abo_paths_append_stats is new); ABO_ACQ_LOGEI (kind 5 in every entry point that takes a kind
+                                  or an abo_acq_term, and in the pruned top-k selection) */
 
 /* status codes */
 enum {
@@ -70,8 +71,14 @@ enum {
     ABO_ACQ_UCB = 1,  /* src/acquisition_functions/UpperConfidenceBound.jl:38-45  p0 = beta */
     ABO_ACQ_PI = 2,   /* src/acquisition_functions/ProbabilityImprovement.jl:38-63 p0 = xi  */
     ABO_ACQ_MEAN = 3, /* score = −mu (exploitation only; no reference counterpart) */
-    ABO_ACQ_GRADNORM_UCB = 4  /* src/acquisition_functions/gradNormUCB.jl:43-51  p0 = beta; gradient-enhanced handles, and only in
+    ABO_ACQ_GRADNORM_UCB = 4, /* src/acquisition_functions/gradNormUCB.jl:43-51  p0 = beta; gradient-enhanced handles, and only in
                                  the abo_*_terms entry points (abo_predict_grad_cov scores a batch with it directly) */
+    ABO_ACQ_LOGEI = 5 /* log EI, p0 = xi and best_y as for EI (no reference counterpart; Ament et al. 2023): log σ + log h(z), h(z) =
+                         φ(z) + z·Φ(z), z = Δ/σ, Δ = (best_y − xi) − μ, evaluated so that it is finite for every finite z (EI itself is
+                         exactly 0 from z ≈ −39 down, and every such candidate ties); σ² ≤ 1e-12 gives log max(Δ, 0), −Inf for Δ ≤ 0,
+                         so that exp(LogEI) = EI on both branches.  Same arg-max and same order as EI wherever EI > 0; standard and
+                         gradient-enhanced handles alike (it reads the function output's μ and σ² only).  The q-EI entry points
+                         (abo_cand_qei*, abo_cand_qei_mc) keep plain EI. */
 };
 
 /* An objective of the acquisition stage: f(x) = Σ_t weight_t · acq_t(x) on ONE posterior evaluation — EnsembleAcquisition
@@ -80,8 +87,8 @@ enum {
 typedef struct abo_acq_term {
     int32_t kind;       /* ABO_ACQ_* */
     int32_t reserved;
-    double p0;          /* xi (EI, PI) or beta (UCB, GradientNormUCB) */
-    double best_y;      /* EI, PI */
+    double p0;          /* xi (EI, PI, LOGEI) or beta (UCB, GradientNormUCB) */
+    double best_y;      /* EI, PI, LOGEI */
     double weight;
 } abo_acq_term;
 
@@ -152,7 +159,7 @@ typedef struct abo_timings {
 } abo_timings;
 
 /* The pruned top-k selection of the last abo_acq / abo_fit_acq on a handle (abo_get_prune_stats).  A call that asks for the top k
- * only (k > 0, scores == NULL) with EI, or UCB with β ≥ 0, on a StandardGP whose contraction runs on the int8-residue engine, over at
+ * only (k > 0, scores == NULL) with EI, LOGEI, or UCB with β ≥ 0, on a StandardGP whose contraction runs on the int8-residue engine, over at
  * least 4·K₀ candidates, does not compute σ² of every candidate: a bound pass over the first bound_rows rows of L⁻¹ gives σ²_R ≥ σ²
  * and so an upper bound of every score; the exact scores of the K₀ = max(4k, 1024) best-by-bound candidates set a threshold; only the
  * candidates whose bound reaches it (the survivors) go through the full contraction.  The k pairs returned are bit for bit those of
@@ -353,7 +360,7 @@ int32_t abo_optimize_acquisition_terms(abo_gp* gp, const abo_acq_term* terms, in
  * by re-evaluating the kernel:
  *   c(z) = k(z,x*) − k_zᵀK⁻¹k_*,   σ²(z) −= c(z)²/l_nn²,   μ(z) += c(z)·(y* − μ(x*))/l_nn²
  * (ABO_EINVAL if gp2 is not the one-point append of the model the set was last synced with).
- * abo_cand_acq runs the EI/UCB/PI epilogue + top-k of abo_acq on the stored posterior;
+ * abo_cand_acq runs the EI/UCB/PI/LOGEI epilogue + top-k of abo_acq on the stored posterior;
  * abo_cand_point returns one candidate's coordinates and posterior (host outputs, any may be NULL);
  * abo_cand_refresh re-evaluates from scratch (after a refit or a hyper-parameter change);
  * abo_cand_save / abo_cand_restore snapshot and roll back the stored posterior (greedy q-EI explores
@@ -568,7 +575,7 @@ int32_t abo_paths_append_stats_get(void* paths, abo_paths_append_stats* out);
  * (QuasiMonteCarlo.sample(n, lower, upper, LatinHypercubeSample()), src/acquisition_functions/acq_utils.jl:44-47)
  * written point-major to Z_dev; counter-based (keyed Feistel permutation per coordinate), so each rank
  * generates its own shard and the candidate grid never crosses PCIe.  lower/upper: d host doubles.
- * abo_score: scores[j] = acq(mu[j], var[j]) — the EI / UCB / PI epilogue on an existing posterior
+ * abo_score: scores[j] = acq(mu[j], var[j]) — the EI / UCB / PI / MEAN / LOGEI epilogue on an existing posterior
  * (several acquisition functions on one posterior pass: EnsembleAcquisition, EnsembleAcq.jl:53-55). */
 int32_t abo_lhs(int32_t device, int64_t n, int32_t d, const double* lower, const double* upper, uint64_t seed,
                 int64_t j0, int64_t count, double* Z_dev);
@@ -751,6 +758,10 @@ int32_t abo_test_acq_grad(abo_gp* gp, int32_t kind, double p0, double best_y, co
                           double* grad);
 int32_t abo_test_acq_grad_terms(abo_gp* gp, const abo_acq_term* terms, int32_t nterms, const double* Z, int64_t M, int32_t d,
                                 double* f, double* grad);
+/* f[j], dmu[j], dvar[j] = value and partial derivatives ∂/∂μ, ∂/∂σ² of the epilogue `kind` (as abo_score's) at mu[j], var[j] (device
+ * buffers): the closed-form partials that gradient is assembled from */
+int32_t abo_test_acq_partials(int32_t device, const double* mu, const double* var, int64_t M, int32_t kind, double p0, double best_y,
+                              double* f, double* dmu, double* dvar);
 /* out[i] = kappa(family, d2[i]) evaluated with the device math of the kernel-matrix generator */
 int32_t abo_test_kappa(int32_t device, int32_t family, const double* d2, double* out, int64_t n);
 /* C[i][j] = alpha·Σ_k A[i][k]·B[j][k] + beta·C[i][j]; M, N multiples of 128, K multiple of 16,

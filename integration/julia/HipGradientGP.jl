@@ -188,7 +188,8 @@ posterior_grad_cov(m::HipGradientGP, x) = (c = _grad_cov(m, x isa Real ? [x] : x
 # analytic gradient from the all-output posterior (∇μ = E[∇f] − m_∇, ∇σ² = 2·Cov(f, ∇f)); GradientNormUCB is differentiated by
 # central differences on the device, as the reference differentiates everything.
 _terms(a::GradientNormUCB, w=1.0) = [AboAcqTerm(Int32(4), Int32(0), Float64(a.β), 0.0, Float64(w))]
-function optimize_acquisition(acqf::Union{ExpectedImprovement,UpperConfidenceBound,ProbabilityImprovement,GradientNormUCB,EnsembleAcquisition},
+function optimize_acquisition(acqf::Union{ExpectedImprovement,LogExpectedImprovement,UpperConfidenceBound,ProbabilityImprovement,GradientNormUCB,
+                                          EnsembleAcquisition},
                               m::HipGradientGP, domain::ContinuousDomain; n_grid::Int=10_000, n_local::Int=100, seed::UInt64=rand(UInt64))
     m.gpx === nothing && throw(ArgumentError("surrogate is not conditioned on data yet (gpx === nothing)"))
     _optimize_terms(_terms(acqf), m.gpx, domain, n_grid, n_local, seed)
@@ -210,6 +211,7 @@ end
 (a::ExpectedImprovement)(m::HipGradientGP, x::AbstractVector)    = _acq_f(m, x, _acq_args(a)...)
 (a::UpperConfidenceBound)(m::HipGradientGP, x::AbstractVector)   = _acq_f(m, x, _acq_args(a)...)
 (a::ProbabilityImprovement)(m::HipGradientGP, x::AbstractVector) = _acq_f(m, x, _acq_args(a)...)
+(a::LogExpectedImprovement)(m::HipGradientGP, x::AbstractVector) = _acq_f(m, x, _acq_args(a)...)
 
 function unstandardized_mean_and_var(m::HipGradientGP, X, params::Tuple)           # :1019
     μ, σ = params[1], params[2][1]

@@ -564,6 +564,9 @@ end
 # the paths that follow the model through appends (abo_paths_append …) live in a file of their own
 include("ThompsonAppend.jl")
 
+# log-domain expected improvement (ABO_ACQ_LOGEI): the type and its methods on the helpers above
+include("LogExpectedImprovement.jl")
+
 # path s takes its best index not taken by paths 1 … s − 1 (idx: k × q orderings, 0 = no candidate)
 function _distinct_picks(idx::AbstractMatrix{Int64})
     picks = Int64[]
