@@ -4,7 +4,7 @@ top-k).  Import as ``import abstractbayesopt.jl_amd as abo``."""
 from . import _lib, acquisition, distributed, incremental, multigpu, synth, thompson
 from ._lib import AboError, DimensionMismatch, PosDefException
 from .acquisition import (AbstractAcquisition, EnsembleAcquisition, ExpectedImprovement, LogExpectedImprovement,
-                          ProbabilityImprovement, UpperConfidenceBound, device_latin_hypercube, evaluate, latin_hypercube,
+                          MaxValueEntropySearch, ProbabilityImprovement, UpperConfidenceBound, device_latin_hypercube, evaluate, latin_hypercube,
                           optimize_acquisition, optimize_acquisition_device, acquisition_value_and_grad, refine_starts,
                           update_and_evaluate)
 from .domains import ContinuousDomain
@@ -17,7 +17,7 @@ from .multigpu import HipShardedGP, HipShardedGradientGP, ShardedCandidates
 from .kernels import (ApproxMatern52Kernel, ApproxMatern72Kernel, ConstMean, Kernel, Matern32Kernel, Matern52Kernel,
                       ScaledKernel, SqExponentialKernel, ZeroMean, with_lengthscale)
 from . import surrogate as _s
-from .thompson import SamplePaths, sample_paths, spectral_frequencies, thompson_batch, thompson_step
+from .thompson import SamplePaths, max_value_samples, sample_paths, spectral_frequencies, thompson_batch, thompson_step
 from .surrogate import (AbstractSurrogate, HipStandardGP, _get_minimum, _update_model_parameters,
                         get_factor, get_kernel_constructor, get_lengthscale, get_mean_std, get_scale, mean_and_var,
                         nlml, nlml_fitted, nlml_ls, posterior_mean, posterior_var, prep_input, prep_output,

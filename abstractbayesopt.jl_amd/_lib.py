@@ -24,10 +24,11 @@ EXPORTS = ["abo_create", "abo_set_contraction", "abo_create_grad", "abo_predict_
            "abo_cand_qei_end", "abo_cand_qei_has", "abo_cand_qei_stats", "abo_mgpu_cand_qei_stats", "abo_cand_qei_eligible", "abo_fill_distance",
            "abo_update", "abo_mgpu_update", "abo_cand_qei_mc",
            "abo_paths_create", "abo_paths_destroy", "abo_paths_eval", "abo_paths_eval_cand", "abo_paths_stats_get",
-           "abo_paths_append", "abo_paths_attach", "abo_paths_detach", "abo_paths_top", "abo_paths_values", "abo_paths_append_stats_get"]
+           "abo_paths_append", "abo_paths_attach", "abo_paths_detach", "abo_paths_top", "abo_paths_values", "abo_paths_append_stats_get",
+           "abo_score_mes", "abo_acq_mes", "abo_cand_acq_mes", "abo_refine_mes", "abo_optimize_acquisition_mes"]
 TEST_EXPORTS = ["abo_test_gemm_nt", "abo_test_kappa", "abo_test_oz_plan", "abo_test_oz_contract", "abo_test_acq_grad",
                 "abo_test_acq_grad_terms", "abo_test_prune_plan", "abo_test_prune_force", "abo_test_prune_bounds", "abo_test_prune_mean",
-                "abo_test_kappa_tail", "abo_test_acq_partials"]
+                "abo_test_kappa_tail", "abo_test_acq_partials", "abo_test_mes_partials", "abo_test_acq_grad_mes"]
 ABI_VERSION = 7
 CONTRACT_AUTO, CONTRACT_FP64, CONTRACT_INT8 = 0, 1, 2
 # what abo_update / abo_mgpu_update ran (include/abo_hip.h)
@@ -239,6 +240,16 @@ def lib():
     L.abo_optimize_acquisition.argtypes = [vp, i32, f64, f64, vp, vp, i32, i64, i32, C.c_uint64, C.POINTER(AboRefineOpts),
                                            vp, C.POINTER(f64), vp, vp, vp, vp]
     L.abo_mgpu_optimize_acquisition.argtypes = L.abo_optimize_acquisition.argtypes
+    # max-value entropy search: the samples (pointer, count[, memory space]) in place of (kind, p0, best_y)
+    L.abo_score_mes.argtypes = [i32, vp, vp, i64, vp, i32, i32, vp]
+    L.abo_acq_mes.argtypes = [vp, vp, i64, i32, i32, vp, i32, i32, i64, vp, i32, vp, vp, i32]
+    L.abo_cand_acq_mes.argtypes = [vp, vp, vp, i32, i32, i64, vp, i32, vp, vp, i32]
+    L.abo_refine_mes.argtypes = [vp, vp, i32, vp, vp, i32, vp, i32, C.POINTER(AboRefineOpts), vp, vp, vp]
+    L.abo_optimize_acquisition_mes.argtypes = [vp, vp, i32, vp, vp, i32, i64, i32, C.c_uint64, C.POINTER(AboRefineOpts),
+                                               vp, C.POINTER(f64), vp, vp, vp, vp]
+    if hooks:
+        L.abo_test_mes_partials.argtypes = [i32, vp, vp, i64, vp, i32, vp, vp, vp]
+        L.abo_test_acq_grad_mes.argtypes = [vp, vp, i32, vp, i64, i32, vp, vp]
     if hooks:
         L.abo_test_acq_grad.argtypes = [vp, i32, f64, f64, vp, i64, i32, vp, vp]
         L.abo_test_acq_partials.argtypes = [i32, vp, vp, i64, i32, f64, f64, vp, vp, vp]

@@ -16,8 +16,9 @@ from . import _lib
 from ._lib import DEVICE, HOST
 from .surrogate import AbstractSurrogate, HipStandardGP, _get_minimum, as_points
 
-ACQ_EI, ACQ_UCB, ACQ_PI, ACQ_MEAN, ACQ_GRADNORM_UCB, ACQ_LOGEI = 0, 1, 2, 3, 4, 5
+ACQ_EI, ACQ_UCB, ACQ_PI, ACQ_MEAN, ACQ_GRADNORM_UCB, ACQ_LOGEI, ACQ_MES = 0, 1, 2, 3, 4, 5, 6
 MAX_TERMS = 8
+MES_MAX_SAMPLES = 1024
 
 
 class AbstractAcquisition:
@@ -69,6 +70,44 @@ class LogExpectedImprovement(AbstractAcquisition):
         return float(self.best_y)
 
 
+@dataclass(frozen=True, eq=False)
+class MaxValueEntropySearch(AbstractAcquisition):
+    """MaxValueEntropySearch(ystar): max-value entropy search (no reference counterpart; Wang & Jegelka 2017; include/abo_hip.h:
+    ABO_ACQ_MES).  ystar: 1 … 1024 samples of the objective's minimum value — `thompson.max_value_samples(model, grid, S)` draws them.
+    Value = mean over the samples of a(γ) = γ·φ(γ)/(2Φ(γ)) − log Φ(γ), γ = (μ − y*)/σ: ≥ 0, nothing to tune.  Its parameter is a vector,
+    so it travels through the abo_*_mes entry points, not as a (kind, p0, best_y) triple; `update` leaves it unchanged (new data calls
+    for new samples).  It cannot be a member of an EnsembleAcquisition."""
+    ystar: np.ndarray
+    kind = ACQ_MES
+
+    def __post_init__(self):
+        ys = np.ascontiguousarray(np.asarray(self.ystar, dtype=np.float64).reshape(-1)).copy()
+        if not 1 <= ys.shape[0] <= MES_MAX_SAMPLES:
+            raise ValueError(f"MaxValueEntropySearch takes 1 to {MES_MAX_SAMPLES} samples, got {ys.shape[0]}")
+        if not np.all(np.isfinite(ys)):
+            raise ValueError("MaxValueEntropySearch: the samples must be finite")
+        ys.setflags(write=False)
+        object.__setattr__(self, "ystar", ys)
+
+    def _p0(self):
+        raise TypeError("MaxValueEntropySearch has no scalar parameters: it is served by the abo_*_mes entry points")
+
+    def _samples(self):
+        """(pointer, count) of the samples for the C-ABI (host memory; the object keeps the array alive)"""
+        return self.ystar.ctypes.data, int(self.ystar.shape[0])
+
+    def __eq__(self, other):
+        return isinstance(other, MaxValueEntropySearch) and np.array_equal(self.ystar, other.ystar)
+
+    __hash__ = None
+
+
+def _mes_handle(surrogate, what):
+    if hasattr(surrogate, "devices") or hasattr(surrogate, "p"):
+        raise TypeError(f"{what}: MaxValueEntropySearch runs on a single-device HipStandardGP only")
+    return surrogate._require()
+
+
 @dataclass(frozen=True)
 class UpperConfidenceBound(AbstractAcquisition):
     """UpperConfidenceBound(β) (UpperConfidenceBound.jl:12-20, :38-45)."""
@@ -104,6 +143,9 @@ class EnsembleAcquisition(AbstractAcquisition):
         assert np.all(weights >= 0), "weights must be non-negative"
         total = float(weights.sum())
         assert total > 0, "sum of weights must be positive"
+        if any(isinstance(a, MaxValueEntropySearch) for a in acqs):
+            raise TypeError("MaxValueEntropySearch cannot be a member of an EnsembleAcquisition: its samples do not fit a weighted-sum "
+                            "term (include/abo_hip.h: abo_acq_term); evaluate it on its own")
         self.weights = weights / total
         self.acquisitions = list(acqs)
 
@@ -170,8 +212,8 @@ def evaluate(acq: AbstractAcquisition, surrogate: HipStandardGP, x, k: int = 0, 
         return evaluate_terms(terms, surrogate, x, k=k, idx_base=idx_base, return_scores=return_scores)
     L = _lib.lib()
     zp, m, d, zspace, keep = as_points(x)
-    if hasattr(surrogate, "devices") and zspace == HOST and idx_base == 0:   # HipShardedGP: sharded inside the library
-        from . import multigpu
+    if hasattr(surrogate, "devices") and zspace == HOST and idx_base == 0 and not isinstance(acq, MaxValueEntropySearch):
+        from . import multigpu                                               # HipShardedGP: sharded inside the library
         return multigpu.evaluate(acq, surrogate, keep, k=k, return_scores=return_scores)
     if zspace == DEVICE:
         import torch
@@ -185,8 +227,13 @@ def evaluate(acq: AbstractAcquisition, surrogate: HipStandardGP, x, k: int = 0, 
         tv = np.empty(k) if k > 0 else None
         ti = np.empty(k, dtype=np.int64) if k > 0 else None
         ptr = lambda a: a.ctypes.data if a is not None else None
-    st = L.abo_acq(surrogate._require(), zp, m, d, zspace, acq.kind, acq._p0(), acq._best(), idx_base,
-                   ptr(scores), k, ptr(tv), ptr(ti), zspace)
+    if isinstance(acq, MaxValueEntropySearch):
+        yp, ns = acq._samples()
+        st = L.abo_acq_mes(_mes_handle(surrogate, "evaluate"), zp, m, d, zspace, yp, ns, HOST, idx_base, ptr(scores), k, ptr(tv), ptr(ti),
+                           zspace)
+    else:
+        st = L.abo_acq(surrogate._require(), zp, m, d, zspace, acq.kind, acq._p0(), acq._best(), idx_base,
+                       ptr(scores), k, ptr(tv), ptr(ti), zspace)
     _lib.check(st)
     return scores, tv, ti
 
@@ -199,7 +246,7 @@ def update_and_evaluate(acq: AbstractAcquisition, model: HipStandardGP, xs, ys, 
     costs a device reduction and a synchronisation of its own).  Returns (new_model, scores, top_vals, top_idx).  At the
     reference's own sizes (tens of points, 10 000 grid points) the host round trip between the two calls is a third of a step."""
     from .surrogate import _Handle, _is_torch, parse_contraction
-    if isinstance(acq, EnsembleAcquisition) or hasattr(model, "devices") or hasattr(model, "p"):
+    if isinstance(acq, (EnsembleAcquisition, MaxValueEntropySearch)) or hasattr(model, "devices") or hasattr(model, "p"):
         from . import update as _update                      # not fused for these: the two calls
         new = _update(model, xs, ys)
         return (new,) + tuple(evaluate(update(acq, ys, new), new, x, k=k, return_scores=return_scores, idx_base=idx_base))
@@ -337,7 +384,9 @@ def evaluate_terms(terms, surrogate, x, k: int = 0, idx_base: int = 0, return_sc
 
 def _library_refinable(acqf, surrogate) -> bool:
     """the on-device refinement serves every objective that flattens into ≤ 8 weighted EI / UCB / PI / GradientNormUCB terms, on
-    StandardGP and gradient-enhanced handles (single device or sharded group)"""
+    StandardGP and gradient-enhanced handles (single device or sharded group), and MaxValueEntropySearch on a single-device StandardGP"""
+    if isinstance(acqf, MaxValueEntropySearch):
+        return not (hasattr(surrogate, "devices") or hasattr(surrogate, "p"))
     return flatten_terms(acqf, surrogate) is not None
 
 
@@ -355,8 +404,9 @@ def refine_starts(acqf: AbstractAcquisition, surrogate: HipStandardGP, starts, l
     Returns (points (S, d), values (S,)).  Ensemble acquisitions (weighted sums of ≤ 8 members) and gradient-enhanced models are
     served by the same call (`abo_refine_terms`); only an objective the library cannot express takes the host loop below
     (`_refine_starts_fd`: the same algorithm on batched finite-difference stencils)."""
-    terms = flatten_terms(acqf, surrogate)
-    if terms is None:                      # more than 8 members / a member the library does not know: the host loop
+    mes = isinstance(acqf, MaxValueEntropySearch)
+    terms = None if mes else flatten_terms(acqf, surrogate)
+    if terms is None and not mes:          # more than 8 members / a member the library does not know: the host loop
         return _refine_starts_fd(acqf, surrogate, starts, lower, upper, max_iter, g_tol, f_abstol, x_abstol, history)
     lower = np.ascontiguousarray(np.asarray(lower, dtype=np.float64))
     upper = np.ascontiguousarray(np.asarray(upper, dtype=np.float64))
@@ -364,6 +414,11 @@ def refine_starts(acqf: AbstractAcquisition, surrogate: HipStandardGP, starts, l
     S, d = st.shape
     x, f, it = np.empty((S, d)), np.empty(S), np.zeros((S, 2), dtype=np.int32)
     opts = _refine_opts(max_iter, g_tol, f_abstol, x_abstol, history)
+    if mes:
+        yp, ns = acqf._samples()
+        _lib.check(_lib.lib().abo_refine_mes(_mes_handle(surrogate, "refine_starts"), yp, ns, lower.ctypes.data, upper.ctypes.data, d,
+                                             st.ctypes.data, S, C.byref(opts), x.ctypes.data, f.ctypes.data, it.ctypes.data))
+        return (x, f, it) if return_iters else (x, f)
     h = surrogate.shard(0) if hasattr(surrogate, "devices") else surrogate._require()
     arr = _term_array(terms)
     _lib.check(_lib.lib().abo_refine_terms(h, arr, len(terms), lower.ctypes.data, upper.ctypes.data, d,
@@ -378,6 +433,11 @@ def acquisition_value_and_grad(acqf: AbstractAcquisition, surrogate: HipStandard
     if z.ndim == 1:
         z = z[:, None]
     f, g = np.empty(z.shape[0]), np.empty(z.shape)
+    if isinstance(acqf, MaxValueEntropySearch):
+        yp, ns = acqf._samples()
+        _lib.check(_lib.lib().abo_test_acq_grad_mes(_mes_handle(surrogate, "acquisition_value_and_grad"), yp, ns, z.ctypes.data,
+                                                    z.shape[0], z.shape[1], f.ctypes.data, g.ctypes.data))
+        return f, g
     terms = flatten_terms(acqf, surrogate)
     if terms is None:
         raise ValueError("the objective does not flatten into at most 8 library terms")
@@ -400,6 +460,13 @@ def optimize_acquisition_device(acqf: AbstractAcquisition, surrogate: HipStandar
     sx, sv, rx, rv = np.empty((k, d)), np.empty(k), np.empty((k, d)), np.empty(k)
     o = _refine_opts(opts.get("max_iter", 0), opts.get("g_tol", 0), opts.get("f_abstol", 0), opts.get("x_abstol", 0), opts.get("history", 0))
     L = _lib.lib()
+    if isinstance(acqf, MaxValueEntropySearch):
+        yp, ns = acqf._samples()
+        _lib.check(L.abo_optimize_acquisition_mes(_mes_handle(surrogate, "optimize_acquisition_device"), yp, ns, lower.ctypes.data,
+                                                  upper.ctypes.data, d, int(n_grid), int(n_local), int(seed) & (2 ** 64 - 1), C.byref(o),
+                                                  best.ctypes.data, C.byref(val), sx.ctypes.data, sv.ctypes.data, rx.ctypes.data,
+                                                  rv.ctypes.data))
+        return (best, val.value, sx, sv, rx, rv) if return_all else best
     terms = flatten_terms(acqf, surrogate)
     if terms is None:
         raise ValueError("the objective does not flatten into at most 8 library terms (use optimize_acquisition)")

@@ -5,6 +5,7 @@
 //   GradientNormUCB  src/acquisition_functions/gradNormUCB.jl:43-51
 //   EnsembleAcquisition  src/acquisition_functions/EnsembleAcq.jl:53-55  (Σ wᵢ·acqᵢ on one posterior)
 //   LogEI  no reference counterpart: log EI, finite for every finite z (Ament et al. 2023)
+//   MES    no reference counterpart: max-value entropy search (Wang & Jegelka 2017)
 #pragma once
 #include "abo_kernels.h"
 #include "../../include/abo_hip.h"
@@ -58,6 +59,63 @@ __device__ __forceinline__ double log_h(double z, double& cdf_h, double& pdf_h) 
     const double T = 1.0 + u * (-1.0 + u * (3.0 + u * (-15.0 + u * 105.0)));
     pdf_h = z2 / (1.0 + S); cdf_h = -z * T / (1.0 + S);
     return -0.5 * z2 - LOGEI_HALF_LOG_2PI - 2.0 * log(-z) + log1p(S);
+}
+
+// ---- max-value entropy search -------------------------------------------------------------------------------------------------------
+// One sample's term a(γ) = γ·φ(γ)/(2Φ(γ)) − log Φ(γ), γ = (μ − y*)/σ, and da/dγ = −(r/2)·(1 + γ² + γ·r), r = φ/Φ, in three ranges of γ.
+// a ≥ 0, non-increasing, → 0 for γ → +∞ and ≈ log|γ| + ½log 2π − ½ for γ → −∞; the bracket 1 + γ² + γ·r ≈ 2/γ² there.
+//   γ > −1        r = norm_pdf/norm_cdf; log Φ = log1p(−Φ(−γ)) for γ > 0 (log Φ itself would round to 0 from γ ≈ 8.3 on), log(Φ) up to
+//                 0.  The bracket is taken as r + γr·(γ + r) (= r·bracket): it cancels by at most a factor 4 (at −1), and for γ beyond
+//                 38.6, where φ and with it r are exactly 0, it is 0·(γ + 0) — γ² is never formed, so no 0·Inf for any finite γ.
+//   −32 < γ ≤ −1  q = Φ/φ = √(π/2)·erfcx(−γ/√2), w = 1 + γq (≈ 1/γ²; log_h's quantity), r = 1/q:
+//                 log Φ = −γ²/2 − ½log 2π + log q, γr/2 + γ²/2 = (γ/2q)·w, so a = (γ/2q)·w + ½log 2π − log q; bracket = 1 + (γ/q)·w.
+//                 w cancels up to 10 bits at the far end and the bracket as many again (≈ 2/γ² from two terms near ∓1): relative error
+//                 of a ≈ 10⁻¹³ there, of the bracket ≈ 10⁻¹⁰ — the reason the series takes over at −32 and not at log_h's −64
+//   γ ≤ −32       u = 1/γ², the asymptotic series of the Mills ratio q = T(u)/|γ|, T = Σ c_k u^k, c_k = (−1)^k (2k−1)!!, to u⁸, and of the
+//                 two combinations that cancel, written out so that nothing is subtracted:
+//                 T = 1 + u·T₁,  T₁ = −1 + 3u − 15u² + 105u³ − 945u⁴ + 10395u⁵ − 135135u⁶ + 2027025u⁷
+//                 a = T₁/(2T) + ½log 2π + log|γ| − log1p(u·T₁)
+//                 bracket = u·B₁/T,  B₁ = Σ (c_{j+1} + c_{j+2}) u^j = 2 − 12u + 90u² − 840u³ + 9450u⁴ − 124740u⁵ + 1891890u⁶ − 32432400u⁷
+//                 da/dγ = B₁/(2γT²)
+//                 (first dropped terms at u = 2⁻¹⁰: 3.4·10⁷u⁹ < 10⁻¹⁹ in T, 6.2·10⁸u⁸ < 10⁻¹⁵ in B₁).  u is (1/γ)², which underflows to 0
+//                 where γ² would overflow: a = log|γ| + ½log 2π − ½ and da/dγ = 1/γ there, finite for every finite γ.
+// A NaN γ fails both comparisons and leaves the last range as NaN.
+__device__ __forceinline__ double mes_a(double g, double& da) {
+    if (g > -1.0) {
+        const double cdf = norm_cdf(g), r = norm_pdf(g) / cdf, t = g * r;
+        da = -0.5 * (r + t * (g + r));
+        return 0.5 * t - (g > 0.0 ? log1p(-norm_cdf(-g)) : log(cdf));
+    }
+    if (g > -32.0) {
+        const double q = LOGEI_SQRT_HALF_PI * erfcx(-g * 0.70710678118654752440084436210485), w = 1.0 + g * q, gr = g / q;
+        da = -0.5 * (1.0 + gr * w) / q;
+        return 0.5 * gr * w + LOGEI_HALF_LOG_2PI - log(q);
+    }
+    const double inv = 1.0 / g, u = inv * inv;
+    const double T1 = -1.0 + u * (3.0 + u * (-15.0 + u * (105.0 + u * (-945.0 + u * (10395.0 + u * (-135135.0 + u * 2027025.0))))));
+    const double B1 = 2.0 + u * (-12.0 + u * (90.0 + u * (-840.0 + u * (9450.0 + u * (-124740.0 + u * (1891890.0 + u * -32432400.0))))));
+    const double T = 1.0 + u * T1;
+    da = 0.5 * inv * B1 / (T * T);
+    return 0.5 * T1 / T + LOGEI_HALF_LOG_2PI + log(-g) - log1p(u * T1);
+}
+
+// MES(μ, σ²) = (1/S)·Σ_s a(γ_s), γ_s = (μ − y*_s)/σ, summed in the order s = 0 … S − 1 by ONE lane (the scoring kernel; the refinement
+// spreads the samples over a workgroup, refine.hip).  σ² ≤ 1e-12 — the library's degenerate-variance threshold, and what an excluded
+// candidate (μ = +Inf, σ² = 0) carries — gives 0 with zero partials; a NaN μ or σ² gives NaN.
+// PARTIALS: ∂/∂μ = (1/S)·Σ a'(γ_s)/σ, ∂/∂σ² = −(1/S)·Σ a'(γ_s)·γ_s/(2σ²)  (∂γ/∂μ = 1/σ, ∂γ/∂σ² = −γ/(2σ²))
+template <bool PARTIALS>
+__device__ __forceinline__ double mes_value(double mu, double var, const double* ys, int S, double& dmu, double& dvar) {
+    if (var <= 1e-12) { dmu = dvar = mu != mu ? mu : 0.0; return dmu; }
+    const double sg = sqrt(var);
+    double f = 0.0, sa = 0.0, sb = 0.0;
+    for (int s = 0; s < S; ++s) {
+        const double g = (mu - ys[s]) / sg;
+        double da;
+        f += mes_a(g, da);
+        if (PARTIALS) { sa += da; sb += da * g; }
+    }
+    if (PARTIALS) { dmu = sa / (sg * S); dvar = -sb / (2.0 * var * S); }
+    return f / S;
 }
 
 __device__ __forceinline__ double acq_score(int kind, double mu, double var, double p0, double best_y) {

@@ -404,20 +404,33 @@ hipError_t launch_lhs(double* Z, int64_t n, int d, const double* lower, const do
 constexpr int MAX_TERMS = 8;
 constexpr int ACQ_GRADNORM_UCB = 4;            // == ABO_ACQ_GRADNORM_UCB (include/abo_hip.h)
 constexpr int ACQ_LOGEI = 5;                   // == ABO_ACQ_LOGEI
+// max-value entropy search (== ABO_ACQ_MES): the one epilogue whose parameter is a VECTOR, the samples y*₀ … y*_{S−1} of the minimum
+// value, so it is no kind of the scalar entry points (plain_kind) and no member of an ensemble (api.hip: make_terms): an objective is
+// MES exactly when it is the single term built by the abo_*_mes entry points (terms_mes)
+constexpr int ACQ_MES = 6;
+constexpr int MES_MAX_SAMPLES = 1024;          // 8 KiB of LDS in the scoring kernel
 // the kinds of the entry points that take ONE kind: the epilogues on (μ, σ²) — EI, UCB, PI, MEAN (0 … 3) and LOGEI
 inline bool plain_kind(int kind) { return (kind >= 0 && kind < ACQ_GRADNORM_UCB) || kind == ACQ_LOGEI; }
 struct AcqTerms {
     int n;
     int kind[MAX_TERMS];
     double p0[MAX_TERMS], best_y[MAX_TERMS], w[MAX_TERMS];
+    const double* ystar;                       // ACQ_MES: the samples (device memory) and their number; null / 0 otherwise
+    int n_ystar;
 };
+inline bool terms_mes(const AcqTerms& t) { return t.n == 1 && t.kind[0] == ACQ_MES; }
 inline bool terms_have_gradnorm(const AcqTerms& t) {
     for (int i = 0; i < t.n; ++i) if (t.kind[i] == ACQ_GRADNORM_UCB) return true;
     return false;
 }
-inline bool terms_plain(const AcqTerms& t) { return t.n == 1 && t.w[0] == 1.0 && t.kind[0] != ACQ_GRADNORM_UCB; }
+// one term of weight 1 that the fused posterior + epilogue pass scores (MES runs on the μ, σ² of a posterior pass instead)
+inline bool terms_plain(const AcqTerms& t) { return t.n == 1 && t.w[0] == 1.0 && t.kind[0] != ACQ_GRADNORM_UCB && t.kind[0] != ACQ_MES; }
 // score[j] = Σ_t w_t·acq_t(mu[j], var[j]) (function-value terms only)
 hipError_t launch_score_terms(const double* mu, const double* var, double* score, int64_t M, const AcqTerms& t, hipStream_t s);
+// score[j] = MES(mu[j], var[j]) = (1/S)·Σ_s a((mu[j] − ystar[s])/σ_j), summed in the order s = 0 … S − 1 (abo_acq_dev.h: mes_a); one lane per
+// candidate, the samples staged in LDS; 1 ≤ S ≤ MES_MAX_SAMPLES.  dmu / dvar (both or neither): its partial derivatives as well
+hipError_t launch_score_mes(const double* mu, const double* var, int64_t M, const double* ystar, int S, double* score, double* dmu,
+                            double* dvar, hipStream_t s);
 // gradient-enhanced model: score[j] from the per-point mean mu[j][p] and covariance block cov[j][p][p]
 hipError_t launch_score_terms_grad(const double* mu, const double* cov, double* score, int64_t M, int p, const AcqTerms& t, hipStream_t s);
 

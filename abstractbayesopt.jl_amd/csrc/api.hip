@@ -368,6 +368,7 @@ struct abo_gp {
     const double* in_y = nullptr;      // null: the model's own copies
     // posterior workspace
     DevBuf Zdev, Kxz, partial, mu_c, mu_all, var_all, score_all, tk_keys0, tk_keys1, tk_idx0, tk_idx1, top_val, top_idx;
+    DevBuf ystar;                      // the samples of an abo_*_mes call that came from host memory
     // int8-residue contraction (ozaki.hip): engine choice, the residue planes of this view's W (valid for oz_gen / oz_N /
     // oz_plan.n) and the per-chunk scratch
     int oz_engine = ABO_CONTRACT_AUTO, oz_nmod = 0;
@@ -393,7 +394,7 @@ struct abo_gp {
         DevBuf* all[] = {&alpha, &vext, &tvec, &T, &info, &scal, &Zdev, &Kxz, &partial, &mu_c, &mu_all, &var_all,
                          &score_all, &tk_keys0, &tk_keys1, &tk_idx0, &tk_idx1, &top_val, &top_idx,
                          &oz_WR, &oz_sexp, &oz_badr, &oz_KR, &oz_U, &oz_badc, &pr_ub, &pr_z, &pr_sc, &pr_sel, &pr_blk, &pr_tv, &pr_ti,
-                         &pr_mut, &pr_eps, &pr_nrm};
+                         &pr_mut, &pr_eps, &pr_nrm, &ystar};
         for (DevBuf* b : all) b->dev = dev;
     }
 
@@ -401,7 +402,7 @@ struct abo_gp {
         DevBuf* all[] = {&alpha, &vext, &tvec, &T, &info, &scal, &Zdev, &Kxz, &partial, &mu_c, &mu_all, &var_all,
                          &score_all, &tk_keys0, &tk_keys1, &tk_idx0, &tk_idx1, &top_val, &top_idx,
                          &oz_WR, &oz_sexp, &oz_badr, &oz_KR, &oz_U, &oz_badc, &pr_ub, &pr_z, &pr_sc, &pr_sel, &pr_blk, &pr_tv, &pr_ti,
-                         &pr_mut, &pr_eps, &pr_nrm};
+                         &pr_mut, &pr_eps, &pr_nrm, &ystar};
         for (DevBuf* b : all) b->release();
         oz_N = -1;
         oz_ctr_clean = nullptr;
@@ -1679,6 +1680,8 @@ int32_t make_terms(const abo_gp* g, const abo_acq_term* terms, int32_t n, AcqTer
     out->n = n;
     for (int i = 0; i < n; ++i) {
         const int k = terms[i].kind;
+        if (k == ABO_ACQ_MES) return fail(ABO_EINVAL, "%s: ABO_ACQ_MES (term %d) takes a vector of samples and is no member of a weighted sum: "
+                                                      "use the abo_*_mes entry points (abo_acq_mes, abo_refine_mes, …)", fn, i);
         if (k < ABO_ACQ_EI || k > ABO_ACQ_LOGEI) return fail(ABO_EINVAL, "%s: unknown acquisition kind %d (term %d)", fn, k, i);
         if (k == ABO_ACQ_GRADNORM_UCB && (!g || g->p_out < 2))
             return fail(ABO_EINVAL, "%s: GradientNormUCB (term %d) needs a gradient-enhanced model", fn, i);
@@ -1697,6 +1700,7 @@ AcqTerms one_term(int32_t kind, double p0, double best_y) {
 // scores of M device-resident candidates under the objective `t` into sc_d (device), queued on the handle's stream:
 //   one plain term            the fused posterior + epilogue pass (what abo_acq has always run: same bits)
 //   function-value terms      ONE posterior pass, then every member's epilogue on that μ, σ² (EnsembleAcq.jl:53-55)
+//   MES                       the same posterior pass, then the sum over the samples per candidate (misc.hip: score_mes_kernel)
 //   a GRADNORM_UCB term       the all-output posterior per point (mean[p], covariance block) in slabs, epilogue on those
 //   more: the call already ran posterior passes (a pruned selection that fell back): this one is counted next to them
 int32_t score_terms_device(abo_gp* g, const double* Zd, int64_t M, const AcqTerms& t, double* sc_d, bool more = false) {
@@ -1719,7 +1723,10 @@ int32_t score_terms_device(abo_gp* g, const double* Zd, int64_t M, const AcqTerm
         HIPCHK(g->var_all.ensure(sizeof(double) * M));
         int32_t rc = posterior(g, Zd, M, -1, 0.0, 0.0, g->mu_all.as<double>(), g->var_all.as<double>(), nullptr);
         if (rc) return rc;
-        HIPCHK(launch_score_terms(g->mu_all.as<double>(), g->var_all.as<double>(), sc_d, M, t, s));
+        if (terms_mes(t))
+            HIPCHK(launch_score_mes(g->mu_all.as<double>(), g->var_all.as<double>(), M, t.ystar, t.n_ystar, sc_d, nullptr, nullptr, s));
+        else
+            HIPCHK(launch_score_terms(g->mu_all.as<double>(), g->var_all.as<double>(), sc_d, M, t, s));
         return ABO_OK;
     }
     const int P = g->p_out;
@@ -1948,6 +1955,7 @@ int32_t abo::acq_ex(abo_gp* g, const double* Z, int64_t M, int32_t d, int32_t z_
                     int64_t* top_idx, int32_t top_space) {
     int32_t rc = check_fitted(g, d);
     if (rc) return rc;
+    if (kind == ABO_ACQ_MES) return fail(ABO_EINVAL, "abo_acq: ABO_ACQ_MES takes a vector of samples: use abo_acq_mes");
     if (!plain_kind(kind)) return fail(ABO_EINVAL, "abo_acq: unknown acquisition kind %d", kind);
     return acq_terms_impl(g, Z, M, d, z_space, one_term(kind, p0, best_y), idx_base, scores, out_space, k, top_val, top_idx, top_space);
 }
@@ -2370,6 +2378,7 @@ int32_t abo_cand_acq(abo_gp* g, abo_cand* c, int32_t kind, double p0, double bes
 int32_t abo::cand_acq_ex(abo_gp* g, abo_cand* c, int32_t kind, double p0, double best_y, int64_t idx_base, double* scores,
                          int32_t out_space, int32_t k, double* top_val, int64_t* top_idx, int32_t top_space) {
     if (!g || !c) return fail(ABO_EINVAL, "abo_cand_acq: null argument");
+    if (kind == ABO_ACQ_MES) return fail(ABO_EINVAL, "abo_cand_acq: ABO_ACQ_MES takes a vector of samples: use abo_cand_acq_mes");
     if (!plain_kind(kind)) return fail(ABO_EINVAL, "abo_cand_acq: unknown acquisition kind %d", kind);
     if (k < 0) return fail(ABO_EINVAL, "abo_cand_acq: k = %d is negative", k);
     if (k > 0 && (!top_val || !top_idx)) return fail(ABO_EINVAL, "abo_cand_acq: k > 0 needs top_val and top_idx");
@@ -2996,6 +3005,9 @@ int32_t refine_device(abo_gp* g, const AcqTerms& terms, const double* bounds_d, 
     if (refine_lds_bytes(g->d, g->dp, m) > 65536)
         return fail(ABO_EINVAL, "abo_refine: input dimension %d too large for the on-device refinement (library limit: %d)", g->d, 700);
     ra.max_iter = o.max_iter; ra.ls_max = o.ls_max; ra.history = m; ra.g_tol = o.g_tol; ra.f_abstol = o.f_abstol; ra.x_abstol = o.x_abstol;
+    // MES is evaluated by the StandardGP kernels only (refine.hip: objective_value_and_partials<true>); rl_grad_ev_kernel below goes
+    // through terms_value_and_partials, which has no case for it
+    if (g->p_out > 1 && terms_mes(terms)) return fail(ABO_EINVAL, "abo_refine: max-value entropy search on a gradient-enhanced handle");
     if (g->p_out > 1) {
         // gradient-enhanced model: lockstep rounds over the all-output posterior (refine.hip: launch_refine_lockstep_grad) — value
         // and gradient of the function-value terms come out of ONE mean / covariance-block evaluation per point
@@ -3115,6 +3127,7 @@ int32_t abo_refine(abo_gp* g, int32_t kind, double p0, double best_y, const doub
 }
 
 #ifdef ABO_TEST_HOOKS
+static int32_t acq_grad_impl(abo_gp* g, const AcqTerms& t, const double* Z, int64_t M, int32_t d, double* f, double* grad);
 int32_t abo_test_acq_grad_terms(abo_gp* g, const abo_acq_term* terms, int32_t nterms, const double* Z, int64_t M, int32_t d, double* f,
                                 double* grad) {
     if (!g) return fail(ABO_EINVAL, "abo_test_acq_grad: null handle");
@@ -3125,6 +3138,11 @@ int32_t abo_test_acq_grad_terms(abo_gp* g, const abo_acq_term* terms, int32_t nt
     if (rc) return rc;
     if (M < 0 || M > 65535 || (M > 0 && (!Z || !f || !grad))) return fail(ABO_EINVAL, "abo_test_acq_grad: bad argument (M ≤ 65535)");
     if (M == 0) return ABO_OK;
+    return acq_grad_impl(g, t, Z, M, d, f, grad);
+}
+
+static int32_t acq_grad_impl(abo_gp* g, const AcqTerms& t, const double* Z, int64_t M, int32_t d, double* f, double* grad) {
+    int32_t rc;
     HIPCHK(hipSetDevice(g->prm.device));
     hipStream_t s = g->stream;
     const size_t ns = (size_t)M * d;
@@ -3301,6 +3319,168 @@ int32_t abo_acq_lhs(abo_gp* g, int64_t n, int32_t d, const double* lower, const 
     }
     return ABO_OK;
 }
+
+}  // extern "C"
+
+// ---- max-value entropy search (ABO_ACQ_MES): the entry points that carry the samples ---------------------------------------
+// The scalar entry points take (kind, p0, best_y); MES takes S samples of the minimum value instead, so it has entry points of its own
+// that build the objective's one term (AcqTerms::ystar) and run the same stages: acq_terms_impl (posterior pass + epilogue + the
+// selection of abo_acq; never the pruned one: terms_plain is false), refine_terms_impl, optimize_terms_impl.
+
+namespace {
+
+// the checks that need no handle: they run first
+int32_t mes_check_samples(const double* ystar, int32_t S, int32_t ys_space, const char* fn) {
+    if (!ystar) return fail(ABO_EINVAL, "%s: null ystar", fn);
+    if (S < 1 || S > MES_MAX_SAMPLES) return fail(ABO_EINVAL, "%s: S = %d samples outside 1..%d", fn, S, MES_MAX_SAMPLES);
+    if (ys_space != ABO_HOST && ys_space != ABO_DEVICE) return fail(ABO_EINVAL, "%s: unknown memory space %d", fn, ys_space);
+    if (ys_space == ABO_HOST)
+        for (int i = 0; i < S; ++i)
+            if (!std::isfinite(ystar[i])) return fail(ABO_EINVAL, "%s: ystar[%d] is not finite", fn, i);
+    return ABO_OK;
+}
+
+int32_t mes_check_handle(abo_gp* g, const char* fn) {
+    if (g->p_out > 1) return fail(ABO_EINVAL, "%s: max-value entropy search runs on StandardGP handles only (this one is gradient-enhanced)", fn);
+    return ABO_OK;
+}
+
+// the objective: host samples are copied to the handle's buffer on its stream (in order before every kernel that reads them), device
+// samples are read where they are
+int32_t mes_terms(abo_gp* g, const double* ystar, int32_t S, int32_t ys_space, AcqTerms* t) {
+    *t = AcqTerms{};
+    t->n = 1; t->kind[0] = ACQ_MES; t->w[0] = 1.0; t->n_ystar = S;
+    if (ys_space == ABO_DEVICE) { t->ystar = ystar; return ABO_OK; }
+    HIPCHK(hipSetDevice(g->prm.device));
+    HIPCHK(g->ystar.ensure(sizeof(double) * MES_MAX_SAMPLES));
+    HIPCHK(hipMemcpyAsync(g->ystar.p, ystar, sizeof(double) * S, hipMemcpyHostToDevice, g->stream));
+    t->ystar = g->ystar.as<double>();
+    return ABO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t abo_score_mes(int32_t device, const double* mu, const double* var, int64_t M, const double* ystar, int32_t S, int32_t ys_space,
+                      double* scores) {
+    if (M < 0 || (M > 0 && (!mu || !var || !scores))) return fail(ABO_EINVAL, "abo_score_mes: bad argument");
+    int32_t rc = mes_check_samples(ystar, S, ys_space, "abo_score_mes");
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(device));
+    ScratchBuf ys(device, nullptr);
+    const double* yd = ystar;
+    if (ys_space == ABO_HOST) {
+        HIPCHK(ys.b.ensure(sizeof(double) * S));
+        HIPCHK(hipMemcpyAsync(ys.b.p, ystar, sizeof(double) * S, hipMemcpyHostToDevice, nullptr));
+        yd = ys.b.as<double>();
+    }
+    HIPCHK(launch_score_mes(mu, var, M, yd, S, scores, nullptr, nullptr, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_acq_mes(abo_gp* g, const double* Z, int64_t M, int32_t d, int32_t z_space, const double* ystar, int32_t S, int32_t ys_space,
+                    int64_t idx_base, double* scores, int32_t k, double* top_val, int64_t* top_idx, int32_t out_space) {
+    int32_t rc = mes_check_samples(ystar, S, ys_space, "abo_acq_mes");
+    if (rc) return rc;
+    rc = check_fitted(g, d);
+    if (rc) return rc;
+    rc = mes_check_handle(g, "abo_acq_mes");
+    if (rc) return rc;
+    AcqTerms t;
+    rc = mes_terms(g, ystar, S, ys_space, &t);
+    if (rc) return rc;
+    return acq_terms_impl(g, Z, M, d, z_space, t, idx_base, scores, out_space, k, top_val, top_idx, out_space);
+}
+
+int32_t abo_cand_acq_mes(abo_gp* g, abo_cand* c, const double* ystar, int32_t S, int32_t ys_space, int64_t idx_base, double* scores,
+                         int32_t k, double* top_val, int64_t* top_idx, int32_t out_space) {
+    int32_t rc = mes_check_samples(ystar, S, ys_space, "abo_cand_acq_mes");
+    if (rc) return rc;
+    if (!g || !c) return fail(ABO_EINVAL, "abo_cand_acq_mes: null argument");
+    if (k < 0) return fail(ABO_EINVAL, "abo_cand_acq_mes: k = %d is negative", k);
+    if (k > 0 && (!top_val || !top_idx)) return fail(ABO_EINVAL, "abo_cand_acq_mes: k > 0 needs top_val and top_idx");
+    rc = mes_check_handle(g, "abo_cand_acq_mes");
+    if (rc) return rc;
+    if (g->prm.device != c->device) return fail(ABO_EINVAL, "candidate set lives on device %d, model on %d", c->device, g->prm.device);
+    HIPCHK(hipSetDevice(g->prm.device));
+    hipStream_t s = g->stream;
+    AcqTerms t;
+    rc = mes_terms(g, ystar, S, ys_space, &t);
+    if (rc) return rc;
+    double* sc_d = (scores && out_space == ABO_DEVICE) ? scores : nullptr;
+    if (!sc_d) { HIPCHK(c->score.ensure(sizeof(double) * (c->M > 0 ? c->M : 1))); sc_d = c->score.as<double>(); }
+    HIPCHK(launch_score_mes(c->mu.as<double>(), c->var.as<double>(), c->M, t.ystar, S, sc_d, nullptr, nullptr, s));
+    if (k > 0) { rc = cand_topk(g, c, sc_d, k, idx_base, top_val, top_idx, out_space); if (rc) return rc; }
+    if (scores && out_space == ABO_HOST && c->M > 0) {
+        rc = copy_out(scores, sc_d, sizeof(double) * c->M, ABO_HOST, s);
+        if (rc) return rc;
+    }
+    HIPCHK(wait_stream(s));
+    return ABO_OK;
+}
+
+int32_t abo_refine_mes(abo_gp* g, const double* ystar, int32_t S, const double* lower, const double* upper, int32_t d, const double* starts,
+                       int32_t n_starts, const abo_refine_opts* opts, double* x_out, double* f_out, int32_t* iters_out) {
+    int32_t rc = mes_check_samples(ystar, S, ABO_HOST, "abo_refine_mes");
+    if (rc) return rc;
+    if (!g) return fail(ABO_EINVAL, "abo_refine_mes: null handle");
+    rc = check_refinable(g, d, "abo_refine_mes");
+    if (rc) return rc;
+    rc = mes_check_handle(g, "abo_refine_mes");
+    if (rc) return rc;
+    AcqTerms t;
+    rc = mes_terms(g, ystar, S, ABO_HOST, &t);
+    if (rc) return rc;
+    return refine_terms_impl(g, t, lower, upper, d, starts, n_starts, opts, x_out, f_out, iters_out);
+}
+
+int32_t abo_optimize_acquisition_mes(abo_gp* g, const double* ystar, int32_t S, const double* lower, const double* upper, int32_t d,
+                                     int64_t n_grid, int32_t n_local, uint64_t seed, const abo_refine_opts* opts, double* best_x,
+                                     double* best_val, double* starts_x, double* starts_val, double* refined_x, double* refined_val) {
+    int32_t rc = mes_check_samples(ystar, S, ABO_HOST, "abo_optimize_acquisition_mes");
+    if (rc) return rc;
+    if (!g) return fail(ABO_EINVAL, "abo_optimize_acquisition_mes: null handle");
+    rc = check_refinable(g, d, "abo_optimize_acquisition_mes");
+    if (rc) return rc;
+    rc = mes_check_handle(g, "abo_optimize_acquisition_mes");
+    if (rc) return rc;
+    AcqTerms t;
+    rc = mes_terms(g, ystar, S, ABO_HOST, &t);
+    if (rc) return rc;
+    return optimize_terms_impl(g, t, lower, upper, d, n_grid, n_local, seed, opts, best_x, best_val, starts_x, starts_val, refined_x,
+                               refined_val);
+}
+
+#ifdef ABO_TEST_HOOKS
+int32_t abo_test_mes_partials(int32_t device, const double* mu, const double* var, int64_t M, const double* ystar, int32_t S, double* f,
+                              double* dmu, double* dvar) {
+    if (M < 0 || (M > 0 && (!mu || !var || !f || !dmu || !dvar))) return fail(ABO_EINVAL, "abo_test_mes_partials: bad argument");
+    int32_t rc = mes_check_samples(ystar, S, ABO_DEVICE, "abo_test_mes_partials");
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(launch_score_mes(mu, var, M, ystar, S, f, dmu, dvar, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_acq_grad_mes(abo_gp* g, const double* ystar, int32_t S, const double* Z, int64_t M, int32_t d, double* f, double* grad) {
+    int32_t rc = mes_check_samples(ystar, S, ABO_HOST, "abo_test_acq_grad_mes");
+    if (rc) return rc;
+    if (!g) return fail(ABO_EINVAL, "abo_test_acq_grad_mes: null handle");
+    rc = check_refinable(g, d, "abo_test_acq_grad_mes");
+    if (rc) return rc;
+    rc = mes_check_handle(g, "abo_test_acq_grad_mes");
+    if (rc) return rc;
+    if (M < 0 || M > 65535 || (M > 0 && (!Z || !f || !grad))) return fail(ABO_EINVAL, "abo_test_acq_grad_mes: bad argument (M ≤ 65535)");
+    if (M == 0) return ABO_OK;
+    AcqTerms t;
+    rc = mes_terms(g, ystar, S, ABO_HOST, &t);
+    if (rc) return rc;
+    return acq_grad_impl(g, t, Z, M, d, f, grad);
+}
+#endif  // ABO_TEST_HOOKS
 
 }  // extern "C"
 
@@ -3672,6 +3852,7 @@ int32_t abo_lhs(int32_t device, int64_t n, int32_t d, const double* lower, const
 int32_t abo_score(int32_t device, const double* mu, const double* var, int64_t M, int32_t kind, double p0, double best_y,
                   double* scores) {
     if (M < 0 || (M > 0 && (!mu || !var || !scores))) return fail(ABO_EINVAL, "abo_score: bad argument");
+    if (kind == ABO_ACQ_MES) return fail(ABO_EINVAL, "abo_score: ABO_ACQ_MES takes a vector of samples: use abo_score_mes");
     if (!plain_kind(kind)) return fail(ABO_EINVAL, "abo_score: unknown acquisition kind %d", kind);
     HIPCHK(hipSetDevice(device));
     HIPCHK(launch_score(mu, var, scores, M, kind, p0, best_y, nullptr));

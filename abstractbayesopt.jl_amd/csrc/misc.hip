@@ -153,6 +153,33 @@ hipError_t launch_score_terms(const double* mu, const double* var, double* score
     return hipGetLastError();
 }
 
+// max-value entropy search on a given posterior: one lane per candidate, the S samples staged in LDS once per workgroup (every lane
+// reads the same sample at the same time: a broadcast, no bank conflict), the sum over the samples in the order s = 0 … S − 1 in the
+// lane's own register — no atomics, the same bits on every run and for any M.  PARTIALS: ∂/∂μ and ∂/∂σ² as well (abo_test_mes_partials).
+template <bool PARTIALS>
+__global__ void __launch_bounds__(256) score_mes_kernel(const double* __restrict__ mu, const double* __restrict__ var, int64_t M,
+                                                         const double* __restrict__ ystar, int S, double* __restrict__ score,
+                                                         double* __restrict__ dmu, double* __restrict__ dvar) {
+    __shared__ double ys[MES_MAX_SAMPLES];
+    for (int i = threadIdx.x; i < S; i += 256) ys[i] = ystar[i];
+    __syncthreads();
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= M) return;
+    double a, b;
+    score[j] = mes_value<PARTIALS>(mu[j], var[j], ys, S, a, b);
+    if (PARTIALS) { dmu[j] = a; dvar[j] = b; }
+}
+
+hipError_t launch_score_mes(const double* mu, const double* var, int64_t M, const double* ystar, int S, double* score, double* dmu,
+                            double* dvar, hipStream_t s) {
+    if (M <= 0) return hipSuccess;
+    if (S < 1 || S > MES_MAX_SAMPLES || !ystar || (dmu == nullptr) != (dvar == nullptr)) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((M + 255) / 256));
+    if (dmu) hipLaunchKernelGGL(score_mes_kernel<true>, grid, dim3(256), 0, s, mu, var, M, ystar, S, score, dmu, dvar);
+    else hipLaunchKernelGGL(score_mes_kernel<false>, grid, dim3(256), 0, s, mu, var, M, ystar, S, score, dmu, dvar);
+    return hipGetLastError();
+}
+
 // gradient-enhanced model: one thread per point over its mean mu[j][p] and covariance block cov[j][p][p] — function-value terms on
 // (mu[0], cov[0][0]), GRADNORM_UCB terms on the gradient block
 __global__ void __launch_bounds__(128) score_terms_grad_kernel(const double* mu, const double* cov, double* score, int64_t M, int p,

@@ -79,9 +79,40 @@ __device__ __forceinline__ void block_sum(double* vals, int nv, double* red, dou
     __syncthreads();
 }
 
+// The objective's value and its partial derivatives at one posterior (μ, σ²), called by ALL threads of the workgroup with the same
+// arguments.  Every kind but MES is a handful of operations that each thread does for itself (terms_value_and_partials).  MES sums up
+// to 1024 terms of erfcx / log cost: one lane looping over them would serialise the workgroup, so thread t takes the samples t, t + RT
+// (read from global memory: 8 KiB that stay in L2) and block_sum adds the three partial sums — xor tree over the lanes, then the waves
+// in order: a fixed order, the same bits on every run.  It is another order than the scoring kernel's s = 0 … S − 1, so a refined value
+// agrees with abo_acq_mes at the same point to rounding (a few ulps), not bit for bit.  MES is a template parameter of the kernels, not
+// a branch: the instantiations that serve the other kinds are the code they were before MES existed.
+template <bool MES>
+__device__ __forceinline__ double objective_value_and_partials(const AcqTerms& t, double mu, double var, double* red, double* out,
+                                                               double& dmu, double& dvar) {
+    if constexpr (!MES) {
+        return terms_value_and_partials(t, mu, var, dmu, dvar);
+    } else {
+        if (var <= 1e-12) { dmu = dvar = mu != mu ? mu : 0.0; return dmu; }           // (uniform: mes_value's degenerate branch)
+        const double sg = sqrt(var);
+        const int S = t.n_ystar;
+        double acc[3] = {0.0, 0.0, 0.0};
+        for (int s = threadIdx.x; s < S; s += RT) {
+            const double g = (mu - t.ystar[s]) / sg;
+            double da;
+            acc[0] += mes_a(g, da);
+            acc[1] += da; acc[2] += da * g;
+        }
+        block_sum(acc, 3, red, out);
+        const double f = out[0] / S;
+        dmu = out[1] / (sg * S); dvar = -out[2] / (2.0 * var * S);
+        __syncthreads();                                                              // out is reused by the gradient's block_sum
+        return f;
+    }
+}
+
 // value f and gradient grad[0..d) of the acquisition function at x (LDS).  xs: LDS [dp]; scr: this start's 4·Np doubles;
 // red: LDS [RW·2·RCH]; out: LDS [2·RCH]; fres: LDS [4] (f, μ, σ²).  All threads call it; all see the result after the final barrier.
-template <int FAM>
+template <int FAM, bool MES>
 __device__ void eval_point(const RefineArgs& a, const double* x, double* xs, double* scr, double* red, double* out, double* fres,
                            double* grad) {
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -203,7 +234,7 @@ __device__ void eval_point(const RefineArgs& a, const double* x, double* xs, dou
     }
     __syncthreads();
     double dmu, dvar;
-    const double f = terms_value_and_partials(a.terms, mu, var, dmu, dvar);
+    const double f = objective_value_and_partials<MES>(a.terms, mu, var, red, out, dmu, dvar);
     // gradient, RCH components per pass: ∂k_i/∂x_c = g_i · 2 (xs_c − Xs_ic) · s
     for (int c0 = 0; c0 < d; c0 += RCH) {
         const int nc = (d - c0) < RCH ? (d - c0) : RCH;
@@ -307,7 +338,7 @@ __device__ __forceinline__ int outer_converged(int d, const double* x, const dou
     return (dx <= x_abstol || fabs(f - frun) <= f_abstol) ? 1 : 0;
 }
 
-template <int FAM>
+template <int FAM, bool MES>
 __global__ void __launch_bounds__(RT) refine_kernel(RefineArgs a) {
     extern __shared__ double sm[];
     const int t = threadIdx.x, d = a.d, dp = a.dp, m = a.history;
@@ -341,7 +372,7 @@ __global__ void __launch_bounds__(RT) refine_kernel(RefineArgs a) {
         xrun[c] = x[c];
     }
     __syncthreads();
-    eval_point<FAM>(a, x, xs, scr, red, out, fres, g);
+    eval_point<FAM, MES>(a, x, xs, scr, red, out, fres, g);
     double f = fres[0];
     double frun = f;                                                       // value at the beginning of the current inner run
     int nev = 1, it = 0, nh = 0;
@@ -364,7 +395,7 @@ __global__ void __launch_bounds__(RT) refine_kernel(RefineArgs a) {
             for (int ls = 0; ls < a.ls_max; ++ls) {
                 for (int c = t; c < d; c += RT) cand[c] = fmin(fmax(fma(tstep, p[c], x[c]), lo[c]), up[c]);
                 __syncthreads();
-                eval_point<FAM>(a, cand, xs, scr, red, out, fres, gc);
+                eval_point<FAM, MES>(a, cand, xs, scr, red, out, fres, gc);
                 fc = fres[0];
                 ++nev;
                 if (t == 0) {
@@ -412,7 +443,7 @@ __global__ void __launch_bounds__(RT) refine_kernel(RefineArgs a) {
 }
 
 // value and gradient at S points in one launch (one workgroup per point): the test hook behind abo_test_acq_grad
-template <int FAM>
+template <int FAM, bool MES>
 __global__ void __launch_bounds__(RT) acq_grad_kernel(RefineArgs a) {
     extern __shared__ double sm[];
     const int t = threadIdx.x, d = a.d, dp = a.dp;
@@ -425,7 +456,7 @@ __global__ void __launch_bounds__(RT) acq_grad_kernel(RefineArgs a) {
     const int sidx = blockIdx.x;
     for (int c = t; c < d; c += RT) x[c] = a.starts[(int64_t)sidx * d + c];
     __syncthreads();
-    eval_point<FAM>(a, x, xs, a.scratch + (int64_t)sidx * 4 * a.Np, red, out, fres, g);
+    eval_point<FAM, MES>(a, x, xs, a.scratch + (int64_t)sidx * 4 * a.Np, red, out, fres, g);
     for (int c = t; c < d; c += RT) a.x_out[(int64_t)sidx * d + c] = g[c];
     if (t == 0) a.f_out[sidx] = fres[0];
 }
@@ -510,6 +541,7 @@ __global__ void rl_zero_tail_kernel(double* V, int Np, int N, int Sp) {
 }
 
 // EV[j] = {f, ∇f[0..d)} of pending point j
+template <bool MES>
 __global__ void __launch_bounds__(RT) rl_reduce_kernel(RefineArgs a, const double* __restrict__ P, const int* __restrict__ start_of,
                                                        const int* __restrict__ nact, const double* __restrict__ KX,
                                                        const double* __restrict__ GV, const double* __restrict__ V,
@@ -538,7 +570,7 @@ __global__ void __launch_bounds__(RT) rl_reduce_kernel(RefineArgs a, const doubl
     const double var = a.sigma_f2 - out[1] + 1e-18;
     __syncthreads();
     double dmu, dvar;
-    const double f = terms_value_and_partials(a.terms, mu, var, dmu, dvar);
+    const double f = objective_value_and_partials<MES>(a.terms, mu, var, red, out, dmu, dvar);
     double* ev = EV + (int64_t)j * (d + 1);
     for (int c0 = 0; c0 < d; c0 += RCH) {
         const int nc = (d - c0) < RCH ? (d - c0) : RCH;
@@ -790,7 +822,8 @@ hipError_t launch_refine_lockstep(const RefineArgs& a, int S, void* work, hipStr
             g2.A = a.WT; g2.B = V; g2.Ct = U; g2.kmode = K_A_UPPER;
             if ((e = launch_gemm_nt(g2, s)) != hipSuccess) return e;
         }
-        hipLaunchKernelGGL(rl_reduce_kernel, dim3(rows), dim3(RT), lds, s, a, P, start_of, nact, KX, GV, V, U, EV);
+        if (terms_mes(a.terms)) hipLaunchKernelGGL(rl_reduce_kernel<true>, dim3(rows), dim3(RT), lds, s, a, P, start_of, nact, KX, GV, V, U, EV);
+        else hipLaunchKernelGGL(rl_reduce_kernel<false>, dim3(rows), dim3(RT), lds, s, a, P, start_of, nact, KX, GV, V, U, EV);
         hipLaunchKernelGGL(rl_step_kernel, dim3(S), dim3(64), rl_step_lds(d, m), s, a, S, 0, P, active, EV, vec, st, counters);
         hipLaunchKernelGGL(rl_compact_kernel, dim3(1), dim3(256), 0, s, active, S, start_of, nact);
         if ((r & 7) == 7 || r + 1 == max_rounds) {
@@ -844,7 +877,7 @@ __global__ void rl_grad_ev_kernel(RefineArgs a, const double* __restrict__ mean_
     const double* m = MU + (size_t)j * npp * p;
     const double* C = COV + (size_t)j * npp * p * p;
     double dmu, dvar;
-    double f = terms_value_and_partials(a.terms, m[0], C[0], dmu, dvar);
+    double f = terms_value_and_partials(a.terms, m[0], C[0], dmu, dvar);         // (never MES: api.hip's refine_device refuses it here)
     const bool st = npp > 1;
     if (st) f += terms_gradnorm(a.terms, m, C, p);
     double* ev = EV ? EV + (size_t)j * (d + 1) : nullptr;
@@ -943,15 +976,20 @@ hipError_t launch_acq_grad_via_eval(const RefineArgs& a, int S, const double* me
     return hipGetLastError();
 }
 
-template <int FAM>
-static hipError_t launch_refine_fam(const RefineArgs& a, int S, bool grad_only, hipStream_t s) {
+template <int FAM, bool MES>
+static hipError_t launch_refine_obj(const RefineArgs& a, int S, bool grad_only, hipStream_t s) {
     if (grad_only) {
         const size_t lds = sizeof(double) * ((size_t)2 * a.d + a.dp + RW * 2 * RCH + 2 * RCH + 4);
-        hipLaunchKernelGGL((acq_grad_kernel<FAM>), dim3(S), dim3(RT), lds, s, a);
+        hipLaunchKernelGGL((acq_grad_kernel<FAM, MES>), dim3(S), dim3(RT), lds, s, a);
     } else {
-        hipLaunchKernelGGL((refine_kernel<FAM>), dim3(S), dim3(RT), refine_lds_bytes(a.d, a.dp, a.history), s, a);
+        hipLaunchKernelGGL((refine_kernel<FAM, MES>), dim3(S), dim3(RT), refine_lds_bytes(a.d, a.dp, a.history), s, a);
     }
     return hipGetLastError();
+}
+// (MES reduces through red / out, which every LDS layout above already holds: the same LDS sizes for both instantiations)
+template <int FAM>
+static hipError_t launch_refine_fam(const RefineArgs& a, int S, bool grad_only, hipStream_t s) {
+    return terms_mes(a.terms) ? launch_refine_obj<FAM, true>(a, S, grad_only, s) : launch_refine_obj<FAM, false>(a, S, grad_only, s);
 }
 
 hipError_t launch_refine(const RefineArgs& a, int S, int grad_only, hipStream_t s) {

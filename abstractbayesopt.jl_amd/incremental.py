@@ -156,6 +156,12 @@ class ResidentCandidates:
             ti = np.empty(k, dtype=np.int64) if k > 0 else None
             ptr = lambda a: a.ctypes.data if a is not None else None
             space = HOST
+        from .acquisition import MaxValueEntropySearch
+        if isinstance(acq, MaxValueEntropySearch):
+            yp, ns = acq._samples()
+            _lib.check(L.abo_cand_acq_mes(self.model._require(), self._h.ptr, yp, ns, HOST, idx_base, ptr(scores), k, ptr(tv), ptr(ti),
+                                          space))
+            return scores, tv, ti
         _lib.check(L.abo_cand_acq(self.model._require(), self._h.ptr, acq.kind, acq._p0(), acq._best(), idx_base,
                                   ptr(scores), k, ptr(tv), ptr(ti), space))
         return scores, tv, ti

@@ -217,6 +217,19 @@ def sample_paths(model, S: int, R: int = 1024, rng=None) -> SamplePaths:
     return SamplePaths(model, *draw_base(model.kernel, int(S), int(R), N, d, rng))
 
 
+def max_value_samples(model, Z, S: int, R: int = 1024, rng=None) -> np.ndarray:
+    """S samples of the objective's minimum value for `acquisition.MaxValueEntropySearch`: the minimum of each of S posterior sample
+    paths over the candidates Z (points, or a ResidentCandidates set) — `sample_paths(model, S, R, rng).argmin(Z, k=1)`'s values, bit for
+    bit, as a host array (S,).  The minimum over a finite grid is an upper estimate of the path's true minimum."""
+    S = int(S)
+    if not 1 <= S <= 1024:
+        raise ValueError(f"max_value_samples: S = {S} outside 1..1024 (the limit of MaxValueEntropySearch)")
+    tv, _ = sample_paths(model, S, R, rng).argmin(Z, k=1)
+    if _is_torch(tv):
+        tv = tv.cpu().numpy()
+    return np.ascontiguousarray(np.asarray(tv, dtype=np.float64)[:, 0])
+
+
 def thompson_step(paths: SamplePaths, model2, cand_set, eps_new=None, rng=None, idx_base: int = 0):
     """One incremental Thompson step after `model2 = append(model, x, y)`: down-date the resident set to model2 (unless it is there
     already), advance the paths and their resident values, and return each path's arg-min (values (S,), indices (S,)).  The set is

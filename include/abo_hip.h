@@ -47,7 +47,8 @@ extern "C" {
                                   abo_paths_eval, abo_paths_eval_cand, abo_paths_stats_get (struct abo_paths_stats is new); abo_paths_append,
                                   abo_paths_attach, abo_paths_detach, abo_paths_top, abo_paths_values, abo_paths_append_stats_get
                                   (struct abo_paths_append_stats is new); ABO_ACQ_LOGEI (kind 5 in every entry point that takes a kind
-                                  or an abo_acq_term, and in the pruned top-k selection) */
+                                  or an abo_acq_term, and in the pruned top-k selection); ABO_ACQ_MES and abo_score_mes, abo_acq_mes,
+                                  abo_cand_acq_mes, abo_refine_mes, abo_optimize_acquisition_mes */
 
 /* status codes */
 enum {
@@ -73,12 +74,18 @@ enum {
     ABO_ACQ_MEAN = 3, /* score = −mu (exploitation only; no reference counterpart) */
     ABO_ACQ_GRADNORM_UCB = 4, /* src/acquisition_functions/gradNormUCB.jl:43-51  p0 = beta; gradient-enhanced handles, and only in
                                  the abo_*_terms entry points (abo_predict_grad_cov scores a batch with it directly) */
-    ABO_ACQ_LOGEI = 5 /* log EI, p0 = xi and best_y as for EI (no reference counterpart; Ament et al. 2023): log σ + log h(z), h(z) =
+    ABO_ACQ_LOGEI = 5,/* log EI, p0 = xi and best_y as for EI (no reference counterpart; Ament et al. 2023): log σ + log h(z), h(z) =
                          φ(z) + z·Φ(z), z = Δ/σ, Δ = (best_y − xi) − μ, evaluated so that it is finite for every finite z (EI itself is
                          exactly 0 from z ≈ −39 down, and every such candidate ties); σ² ≤ 1e-12 gives log max(Δ, 0), −Inf for Δ ≤ 0,
                          so that exp(LogEI) = EI on both branches.  Same arg-max and same order as EI wherever EI > 0; standard and
                          gradient-enhanced handles alike (it reads the function output's μ and σ² only).  The q-EI entry points
                          (abo_cand_qei*, abo_cand_qei_mc) keep plain EI. */
+    ABO_ACQ_MES = 6   /* max-value entropy search (no reference counterpart; Wang & Jegelka 2017).  Named here for documentation: its
+                         parameter is a vector — S samples y*_s of the objective's minimum value — so the entry points that take
+                         (kind, p0, best_y) or an abo_acq_term return ABO_EINVAL for it; the abo_*_mes entry points below carry the
+                         samples.  MES = (1/S)·Σ_s a(γ_s), γ_s = (μ − y*_s)/σ, a(γ) = γ·φ(γ)/(2Φ(γ)) − log Φ(γ), summed in the order
+                         s = 0 … S−1, finite for every finite γ; a ≥ 0 and non-increasing in γ.  σ² ≤ 1e-12 gives 0 (so does a
+                         candidate excluded by abo_cand_exclude); a NaN μ or σ² gives NaN.  1 ≤ S ≤ 1024. */
 };
 
 /* An objective of the acquisition stage: f(x) = Σ_t weight_t · acq_t(x) on ONE posterior evaluation — EnsembleAcquisition
@@ -581,6 +588,31 @@ int32_t abo_lhs(int32_t device, int64_t n, int32_t d, const double* lower, const
                 int64_t j0, int64_t count, double* Z_dev);
 int32_t abo_score(int32_t device, const double* mu, const double* var, int64_t M, int32_t kind, double p0,
                   double best_y, double* scores);
+
+/* Max-value entropy search (ABO_ACQ_MES above), ABI 7.  ystar: S samples of the minimum value, 1 ≤ S ≤ 1024, in HOST or DEVICE memory
+ * (ys_space; abo_refine_mes and abo_optimize_acquisition_mes: host) — what abo_paths_eval(…, k = 1) leaves in top_val for S sample
+ * paths over a grid.  A null pointer, S out of range and a non-finite host sample return ABO_EINVAL before the handle is looked at;
+ * StandardGP handles only (ABO_EINVAL for a gradient-enhanced one).  No abo_mgpu_* twins, and no MES member in an abo_acq_term sum.
+ * abo_score_mes: scores[j] = MES(mu[j], var[j]) on an existing posterior (mu, var, scores: device buffers, as abo_score's).
+ * abo_acq_mes: abo_acq with MES as the epilogue — one posterior pass, the epilogue on its μ, σ² (the same bits as abo_score_mes on
+ * abo_predict's output), then abo_acq's selection: its order, idx_base, k > 1024 and the (NaN, −1) tail.  The pruned top-k selection
+ * never applies (MES is not monotone in σ): abo_get_prune_stats reads all zeros afterwards.
+ * abo_cand_acq_mes: the same on a resident set's stored posterior (abo_cand_acq).
+ * abo_refine_mes / abo_optimize_acquisition_mes: abo_refine / abo_optimize_acquisition with MES as the objective (analytic gradient;
+ * the samples are spread over the workgroup's lanes and summed in a fixed tree, so a refined value agrees with abo_acq_mes at the same
+ * point to rounding, not bit for bit). */
+int32_t abo_score_mes(int32_t device, const double* mu, const double* var, int64_t M, const double* ystar, int32_t S, int32_t ys_space,
+                      double* scores);
+int32_t abo_acq_mes(abo_gp* gp, const double* Z, int64_t M, int32_t d, int32_t z_space, const double* ystar, int32_t S, int32_t ys_space,
+                    int64_t idx_base, double* scores, int32_t k, double* top_val, int64_t* top_idx, int32_t out_space);
+int32_t abo_cand_acq_mes(abo_gp* gp, abo_cand* c, const double* ystar, int32_t S, int32_t ys_space, int64_t idx_base, double* scores,
+                         int32_t k, double* top_val, int64_t* top_idx, int32_t out_space);
+int32_t abo_refine_mes(abo_gp* gp, const double* ystar, int32_t S, const double* lower, const double* upper, int32_t d,
+                       const double* starts, int32_t n_starts, const abo_refine_opts* opts, double* x_out, double* f_out,
+                       int32_t* iters_out);
+int32_t abo_optimize_acquisition_mes(abo_gp* gp, const double* ystar, int32_t S, const double* lower, const double* upper, int32_t d,
+                                     int64_t n_grid, int32_t n_local, uint64_t seed, const abo_refine_opts* opts, double* best_x,
+                                     double* best_val, double* starts_x, double* starts_val, double* refined_x, double* refined_val);
 /* monte_carlo_fill_distance (src/BO_utils.jl:140-159; the lower length-scale bound of optimize_hyperparameters,
  * src/BO_utils.jl:87-125): *out = max over the n_samples points S of the distance to the nearest of the N training points X
  * (both point-major, d coordinates; HOST or DEVICE memory each; out: one host double).  The caller draws the sample points — the
@@ -762,6 +794,10 @@ int32_t abo_test_acq_grad_terms(abo_gp* gp, const abo_acq_term* terms, int32_t n
  * buffers): the closed-form partials that gradient is assembled from */
 int32_t abo_test_acq_partials(int32_t device, const double* mu, const double* var, int64_t M, int32_t kind, double p0, double best_y,
                               double* f, double* dmu, double* dvar);
+/* the same two hooks for max-value entropy search (ystar: S samples; device memory for the partials, host memory for the gradient) */
+int32_t abo_test_mes_partials(int32_t device, const double* mu, const double* var, int64_t M, const double* ystar, int32_t S, double* f,
+                              double* dmu, double* dvar);
+int32_t abo_test_acq_grad_mes(abo_gp* gp, const double* ystar, int32_t S, const double* Z, int64_t M, int32_t d, double* f, double* grad);
 /* out[i] = kappa(family, d2[i]) evaluated with the device math of the kernel-matrix generator */
 int32_t abo_test_kappa(int32_t device, int32_t family, const double* d2, double* out, int64_t n);
 /* C[i][j] = alpha·Σ_k A[i][k]·B[j][k] + beta·C[i][j]; M, N multiples of 128, K multiple of 16,

@@ -567,6 +567,9 @@ include("ThompsonAppend.jl")
 # log-domain expected improvement (ABO_ACQ_LOGEI): the type and its methods on the helpers above
 include("LogExpectedImprovement.jl")
 
+# max-value entropy search (ABO_ACQ_MES): the type, its samples from the paths above, and the abo_*_mes calls
+include("MaxValueEntropySearch.jl")
+
 # path s takes its best index not taken by paths 1 … s − 1 (idx: k × q orderings, 0 = no candidate)
 function _distinct_picks(idx::AbstractMatrix{Int64})
     picks = Int64[]
