@@ -28,7 +28,7 @@ EXPORTS = ["abo_create", "abo_set_contraction", "abo_create_grad", "abo_predict_
            "abo_score_mes", "abo_acq_mes", "abo_cand_acq_mes", "abo_refine_mes", "abo_optimize_acquisition_mes"]
 TEST_EXPORTS = ["abo_test_gemm_nt", "abo_test_kappa", "abo_test_oz_plan", "abo_test_oz_contract", "abo_test_acq_grad",
                 "abo_test_acq_grad_terms", "abo_test_prune_plan", "abo_test_prune_force", "abo_test_prune_bounds", "abo_test_prune_mean",
-                "abo_test_kappa_tail", "abo_test_acq_partials", "abo_test_mes_partials", "abo_test_acq_grad_mes"]
+                "abo_test_kappa_tail", "abo_test_prune_bound_moduli", "abo_test_prune_bound_plan", "abo_test_oz_contract_bound", "abo_test_acq_partials", "abo_test_mes_partials", "abo_test_acq_grad_mes"]
 ABI_VERSION = 7
 CONTRACT_AUTO, CONTRACT_FP64, CONTRACT_INT8 = 0, 1, 2
 # what abo_update / abo_mgpu_update ran (include/abo_hip.h)
@@ -182,6 +182,8 @@ def lib():
         L.abo_test_prune_force.argtypes = [i32, i32]
         L.abo_test_prune_bounds.argtypes = [vp, vp, i64]
         L.abo_test_prune_mean.argtypes = [vp, vp, vp, i64]
+        L.abo_test_prune_bound_moduli.argtypes = [i32]
+        L.abo_test_prune_bound_plan.argtypes = [vp, vp, vp, i64]
         L.abo_test_kappa_tail.argtypes = [i32, i32, vp, vp, i64]
     L.abo_last_error.argtypes = [C.c_char_p, C.c_size_t]
     L.abo_abi_version.argtypes = []
@@ -192,6 +194,7 @@ def lib():
         L.abo_test_oz_plan.argtypes = [i32, vp, vp, vp, vp]
     if hooks:
         L.abo_test_oz_contract.argtypes = [i32, vp, i64, i32, i32, vp, i64, i32, f64, i32, vp, i64]
+        L.abo_test_oz_contract_bound.argtypes = [i32, vp, i64, i32, i32, vp, i64, i32, f64, i32, i32, vp, i64, vp]
     if hooks:
         L.abo_test_gemm_nt.argtypes = [i32, vp, vp, vp, i32, i32, i32, i64, i64, i64, f64, f64]
     L.abo_mgpu_create.argtypes = [C.POINTER(AboParams), i32, C.POINTER(i32), C.POINTER(vp)]

@@ -75,11 +75,20 @@ struct OzPlan {
 bool oz_make_plan(int n, OzPlan* out);
 size_t oz_w_bytes(int n, int Np);            // residue planes of W: n × pad256(Np)²
 size_t oz_k_bytes(int n, int Np, int Mc);    // residue planes of a candidate chunk (and of its U): n × pad256(Mc) × pad256(Np)
-int oz_k_scale(double kmax);                 // sK with rint(K·2^sK) < 2^53 for 0 ≤ K ≤ kmax
+int oz_k_scale(double kmax, int bits = 53);  // sK with rint(K·2^sK) ≤ 2^(bits−1) for 0 ≤ K ≤ kmax (bits = 53: the full-width image)
 // W (lower-triangular, [Np][ldw]) → WR [n][Np256][Np256] int8, sexp[Np256] (row scales s_i), bad_row[Np256] (non-finite rows)
 // rows ≥ nvalid (identity padding, or the remains of a discarded appended branch) become zero planes
 hipError_t oz_prepare_w(const OzPlan& pl, const double* W, int64_t ldw, int Np, int nvalid, int8_t* WR, int* sexp, int* bad_row, hipStream_t s,
                         int kper = 1, int ktg = 0);
+// ---- the short plan of the pruned selection's bound pass (ozaki.hip: "the guarded bound") ----
+// K bits of a short plan with exponent budget eP over `rows` factor rows: K' ≤ 2^(bK−1), W' keeps bW = eP − bK bits below its row's L1 norm
+int oz_bound_kbits(int eP, int rows);
+// The first `rows` (a multiple of 256, ≤ pad256(Np)) rows of W under the short plan `pl`: WRb [pl.n][rows][pad256(Np)] int8 (the row
+// stride of the full planes, so that the residue GEMM walks both with one stride; only the k < rows bytes of a row are written or
+// read), sexp_b / bad_row_b / delta [rows]: delta[i] ≥ |Ṽ_ij − v_ij| + the roundings of either side, for Ṽ the short plan's
+// reconstruction at (sexp_b[i], sK_b) and v the reconstruction of the plan `full` at its own row scale and sK_full.
+hipError_t oz_prepare_w_bound(const OzPlan& pl, const OzPlan& full, const double* W, int64_t ldw, int Np, int nvalid, int rows, int kbits, int sK_b,
+                              int sK_full, double kmax, int8_t* WRb, int* sexp_b, int* bad_row_b, double* delta, hipStream_t s);
 constexpr int OZ_CTR_INTS = 16;
 struct OzVarArgs {
     const OzPlan* plan;
@@ -102,6 +111,10 @@ struct OzVarArgs {
     // > 0: only the first rblocks 256-row blocks of W are contracted — partial[tb] for tb < 2·rblocks, the sum of squares over the
     // first min(nvalid, 256·rblocks) rows of V, bit for bit what the full call writes there (the buffers keep their full layout)
     int rblocks = 0;
+    // the guarded bound (rblocks > 0 only): delta[i] per contracted row — the column sums are of max(|V_ij| − delta[i], 0)²; nullptr =
+    // the exact sums.  w_plane: bytes between the residue planes of WR when they are not the full pad256(Np)² planes (0 = they are)
+    const double* delta = nullptr;
+    int64_t w_plane = 0;
     double* Vout = nullptr;     // when given: V = W.K_XZ itself, [Mc][ldv] fp64 (candidate-major), instead of the column sums of squares
     int64_t ldv = 0;
     hipEvent_t ev_quant = nullptr, ev_gemm = nullptr;   // optional: recorded after the quantisation / after the GEMM
@@ -143,8 +156,12 @@ struct KgenArgs {
                           // never read by a contraction limited to the first res_kmax rows of the triangular W): planes for them, and
                           // mu = mean_c + their part of the sum — the other columns' part comes from launch_kgen_tail; 0 = all columns
 };
-// true when launch_kgen honours KgenArgs::res for this shape and n moduli (the fused output is instantiated for the default plan)
-inline bool kgen_writes_residues(const KgenArgs& a, int n) { return a.dp <= 32 && n == 14 && !a.dlogell; }
+// true when launch_kgen honours KgenArgs::res for this shape and n moduli (the fused output is instantiated for the default plan, and
+// for the short plans of the pruned selection's bound pass — 8, 9, 10 moduli — in the partial launch res_kmax > 0 of a StandardGP alone)
+inline bool kgen_short_moduli(int n) { return n >= 8 && n <= 10; }
+inline bool kgen_writes_residues(const KgenArgs& a, int n) {
+    return a.dp <= 32 && !a.dlogell && (n == 14 || (kgen_short_moduli(n) && a.res_kmax > 0 && a.pt == 1));
+}
 hipError_t launch_kgen(const KgenArgs& a, hipStream_t s);
 // ---- the μ-only tail of the pruned selection's bound pass (kgen_tail.hip) ----
 // over the N training points: norms[0] = Σ_{k ≥ k0} |alpha_k|, norms[1] = Σ_k |alpha_k|, norms[2] = max_{k ≥ k0} |Xs_k|² — one

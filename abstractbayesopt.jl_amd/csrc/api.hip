@@ -379,11 +379,16 @@ struct abo_gp {
     int64_t oz_N = -1;
     // the posterior passes of the current call, in launch order (their per-chunk events are read back with them): the pruned top-k
     // selection of abo_acq runs up to three, everything else one
-    struct PostPass { int64_t chunk0, nchunk, M, rows; };     // first chunk's event slot, chunks, candidate rows, rows of W contracted
+    struct PostPass { int64_t chunk0, nchunk, M, rows; int nmod; };   // first chunk's event slot, chunks, candidate rows, rows of W contracted, moduli launched
     std::vector<PostPass> passes;
     DevBuf pr_ub, pr_z, pr_sc, pr_sel, pr_blk, pr_tv, pr_ti;   // pruned selection: bounds, gathered points, their scores, survivor list, scan scratch, threshold pairs
     DevBuf pr_mut, pr_eps, pr_nrm;                             // its bound pass: μ̃ and ε of every candidate, the norms ε is built from (kgen_tail.hip)
     abo_prune_stats pst{};
+    // the bound pass's short residue plan (ozaki.hip: "the guarded bound"): the plan, the residue planes of the first bound rows of W
+    // under it, their row scales, flags and guards — rebuilt by every bound pass (pb_rows of them by the last one, at pb_sK)
+    OzPlan oz_plan_b{};
+    DevBuf oz_WRb, oz_sexpb, oz_badrb, oz_delta;
+    int pb_rows = 0, pb_sK = 0;
     DevBuf oz_WR, oz_sexp, oz_badr, oz_KR, oz_U, oz_badc;
     abo_timings tm{};
 
@@ -394,7 +399,7 @@ struct abo_gp {
         DevBuf* all[] = {&alpha, &vext, &tvec, &T, &info, &scal, &Zdev, &Kxz, &partial, &mu_c, &mu_all, &var_all,
                          &score_all, &tk_keys0, &tk_keys1, &tk_idx0, &tk_idx1, &top_val, &top_idx,
                          &oz_WR, &oz_sexp, &oz_badr, &oz_KR, &oz_U, &oz_badc, &pr_ub, &pr_z, &pr_sc, &pr_sel, &pr_blk, &pr_tv, &pr_ti,
-                         &pr_mut, &pr_eps, &pr_nrm, &ystar};
+                         &pr_mut, &pr_eps, &pr_nrm, &ystar, &oz_WRb, &oz_sexpb, &oz_badrb, &oz_delta};
         for (DevBuf* b : all) b->dev = dev;
     }
 
@@ -402,7 +407,7 @@ struct abo_gp {
         DevBuf* all[] = {&alpha, &vext, &tvec, &T, &info, &scal, &Zdev, &Kxz, &partial, &mu_c, &mu_all, &var_all,
                          &score_all, &tk_keys0, &tk_keys1, &tk_idx0, &tk_idx1, &top_val, &top_idx,
                          &oz_WR, &oz_sexp, &oz_badr, &oz_KR, &oz_U, &oz_badc, &pr_ub, &pr_z, &pr_sc, &pr_sel, &pr_blk, &pr_tv, &pr_ti,
-                         &pr_mut, &pr_eps, &pr_nrm, &ystar};
+                         &pr_mut, &pr_eps, &pr_nrm, &ystar, &oz_WRb, &oz_sexpb, &oz_badrb, &oz_delta};
         for (DevBuf* b : all) b->release();
         oz_N = -1;
         oz_ctr_clean = nullptr;
@@ -857,6 +862,26 @@ int32_t oz_planes_of_w(abo_gp* g) {
 // columns past those blocks are summed by the cheaper launch_kgen_tail, which also proves ε ≥ |μ̃ − μ| (kgen_tail.hip).
 // more: a further pass of the same call — its events and counts are kept next to those of the passes before it.
 constexpr int32_t PRUNE_UNAVAILABLE = -100;
+
+#ifdef ABO_TEST_HOOKS
+std::atomic<int> g_prune_bound_moduli{0};       // abo_test_prune_bound_moduli: 0 = the environment's / the default
+#endif
+
+// moduli of the bound pass's residue plan: 8 (default), 9, 10 — a short plan with the guard of ozaki.hip — or 14: the handle's plan,
+// exact contraction, as before the short plan existed.  ABO_PRUNE_BOUND_MODULI; any other value (11 – 13, below 8, text) is IGNORED and
+// the default 8 used — the head generator is instantiated for these counts alone; the test hook refuses such a value with an error.
+int prune_bound_moduli() {
+    static const int env = [] {
+        const char* e = getenv("ABO_PRUNE_BOUND_MODULI");
+        const int v = e ? atoi(e) : 0;
+        return (kgen_short_moduli(v) || v == 14) ? v : 8;
+    }();
+#ifdef ABO_TEST_HOOKS
+    if (g_prune_bound_moduli.load() > 0) return g_prune_bound_moduli.load();
+#endif
+    return env;
+}
+
 int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0, double best_y, double* mu_out,
                   double* var_out, double* score_out, int pc = 1, int point_major = 0, double* kstore = nullptr,
                   int64_t ldstore = 0, int rblocks = 0, bool more = false) {
@@ -892,8 +917,30 @@ int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0
     }
     const int64_t chunk0 = g->passes.empty() ? 0 : g->passes.back().chunk0 + g->passes.back().nchunk;
     HIPCHK(g->events(EV_BASE + EV_PER_CHUNK * (size_t)(chunk0 + nchunk)));
-    g->passes.push_back({chunk0, nchunk, M, rblocks > 0 && (int64_t)256 * rblocks < g->N ? (int64_t)256 * rblocks : g->N});
     if (oz) { int32_t rc = oz_planes_of_w(g); if (rc) return rc; }
+    // the bound pass on a short plan: its own planes of the first 256·rblocks rows of W, row scales and guards — rebuilt every call (one
+    // row-scale and one quantiser launch over R × R; appends, abo_update, a changed R and shared factor storage would all have to
+    // invalidate a cache)
+    const int nb = rblocks > 0 ? prune_bound_moduli() : 0;
+    const bool shortp = nb > 0 && nb != g->oz_plan.n;
+    const double sf2k = g->p_out > 1 ? (pc > 1 ? 2.0 : 1.5) * g->prm.sigma_f2 : g->prm.sigma_f2;
+    if (shortp) {
+        if (g->oz_plan_b.n != nb && !oz_make_plan(nb, &g->oz_plan_b)) return fail(ABO_EINVAL, "bound pass: %d moduli not supported", nb);
+        const int rows = 256 * rblocks;
+        const int64_t q = pad_up(Np, 256);
+        HIPCHK(g->oz_WRb.ensure((size_t)nb * rows * q));
+        HIPCHK(g->oz_sexpb.ensure(sizeof(int) * rows));
+        HIPCHK(g->oz_badrb.ensure(sizeof(int) * rows));
+        HIPCHK(g->oz_delta.ensure(sizeof(double) * rows));
+        const int bK = oz_bound_kbits(g->oz_plan_b.eP, rows);
+        g->pb_sK = oz_k_scale(sf2k, bK);
+        g->pb_rows = rows;
+        HIPCHK(oz_prepare_w_bound(g->oz_plan_b, g->oz_plan, g->st->W.as<double>(), g->st->cap, (int)Np, (int)g->N, rows, bK, g->pb_sK,
+                                  oz_k_scale(sf2k), sf2k * (1.0 + 0x1p-40), g->oz_WRb.as<int8_t>(), g->oz_sexpb.as<int>(), g->oz_badrb.as<int>(),
+                                  g->oz_delta.as<double>(), s));
+    } else if (rblocks > 0) g->pb_rows = 0;
+    const OzPlan& plan = shortp ? g->oz_plan_b : g->oz_plan;
+    g->passes.push_back({chunk0, nchunk, M, rblocks > 0 && (int64_t)256 * rblocks < g->N ? (int64_t)256 * rblocks : g->N, oz ? plan.n : 0});
     g->tm.contraction_engine = want_var ? (oz ? ABO_CONTRACT_INT8 : ABO_CONTRACT_FP64) : 0;
     g->tm.oz_nmod = oz ? g->oz_plan.n : 0;
     // (prune_plan: fewer row blocks than the model has, so the tail is never empty)
@@ -914,18 +961,18 @@ int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0
         ka.sigma_f2 = g->prm.sigma_f2; ka.mean_c = g->prm.mean_c;
         // int8 engine: the generator writes the residue planes of the chunk itself (the fp64 K_XZ is then only materialised for a
         // caller that keeps it — the resident K_ZX of a candidate set)
-        const bool fused = oz && kgen_writes_residues(ka, g->oz_plan.n);
+        ka.res_kmax = 256 * rblocks;
+        const bool fused = oz && kgen_writes_residues(ka, plan.n);
         if (fused) {
             const int64_t q = pad_up(Np, 256);
             ka.res = g->oz_KR.as<int8_t>(); ka.res_ld = q; ka.res_plane = pad_up(mcp, 256) * q;
             // (a gradient-enhanced model's scaled chunk is bounded by σ_f²·√2, its all-output chunk by 2σ_f²: the exponent the
             // contraction below is told, oa.sK)
-            ka.res_bad = g->oz_badc.as<int>(); ka.res_n = g->oz_plan.n;
-            ka.res_sK = oz_k_scale(g->p_out > 1 ? (pc > 1 ? 2.0 : 1.5) * g->prm.sigma_f2 : g->prm.sigma_f2);
+            ka.res_bad = g->oz_badc.as<int>(); ka.res_n = plan.n;
+            ka.res_sK = shortp ? g->pb_sK : oz_k_scale(sf2k);
             ka.res_ktg = oz_grad_exp(g);
-            ka.res_kmax = 256 * rblocks;
             if (!kstore) ka.Kout = nullptr;
-        }
+        } else ka.res_kmax = 0;
         PHASE_EVENT(e[0], s);
         HIPCHK(launch_kgen(ka, s));
         if (rblocks > 0) {
@@ -939,12 +986,16 @@ int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0
         PHASE_EVENT(e[1], s);
         if (oz) {
             OzVarArgs oa{};
-            oa.plan = &g->oz_plan; oa.Kxz = kchunk; oa.ldk = ldk; oa.WR = g->oz_WR.as<int8_t>(); oa.sexp = g->oz_sexp.as<int>();
+            oa.plan = &plan; oa.Kxz = kchunk; oa.ldk = ldk; oa.WR = g->oz_WR.as<int8_t>(); oa.sexp = g->oz_sexp.as<int>();
             oa.bad_row = g->oz_badr.as<int>(); oa.KR = g->oz_KR.as<int8_t>(); oa.U = g->oz_U.as<int8_t>();
             oa.bad_col = g->oz_badc.as<int>(); oa.ctr_clean = &g->oz_ctr_clean; oa.partial = g->partial.as<double>(); oa.ldp = Mc; oa.Np = (int)Np; oa.Mc = mcp;
+            if (shortp) {           // the short plan's planes of W (row stride of the full planes), scales, flags and guards
+                oa.WR = g->oz_WRb.as<int8_t>(); oa.sexp = g->oz_sexpb.as<int>(); oa.bad_row = g->oz_badrb.as<int>();
+                oa.delta = g->oz_delta.as<double>(); oa.w_plane = (int64_t)256 * rblocks * pad_up(Np, 256);
+            }
             // a gradient-enhanced model's scaled chunk is bounded by σ_f²·√2 (oz_prepare_w), a StandardGP's by σ_f²
             // (derivative candidates against derivative training rows, both scaled: 2σ_f²)
-            oa.nvalid = (int)g->N; oa.sK = oz_k_scale(g->p_out > 1 ? (pc > 1 ? 2.0 : 1.5) * g->prm.sigma_f2 : g->prm.sigma_f2);
+            oa.nvalid = (int)g->N; oa.sK = shortp ? g->pb_sK : oz_k_scale(sf2k);
             oa.kper = g->p_out; oa.ktg = oz_grad_exp(g);
             if (pc > 1) { oa.rmode = point_major ? 1 : 2; oa.rper = pc; oa.r0 = j0; oa.rpts = Mpts; }
             oa.ev_quant = phase_events() ? e[6] : nullptr; oa.ev_gemm = phase_events() ? e[7] : nullptr; oa.planes_ready = fused ? 1 : 0;
@@ -1060,7 +1111,7 @@ int32_t grad_eval_device(abo_gp* g, const double* Zd, int64_t M, double beta, do
 // phase times and algorithmic work of the call's posterior passes (what was launched: a bound pass counts its R rows, a survivor pass
 // its survivors)
 void collect_posterior_timings(abo_gp* g, bool with_var) {
-    double kx = 0, vg = 0, fi = 0, oq = 0, og = 0, oc = 0, work = 0;
+    double kx = 0, vg = 0, fi = 0, oq = 0, og = 0, oc = 0, work = 0, ozops = 0;
     const bool oz = with_var && g->tm.contraction_engine == ABO_CONTRACT_INT8;
     for (const abo_gp::PostPass& ps : g->passes) {
         for (int64_t c = 0; phase_events() && c < ps.nchunk; ++c) {
@@ -1071,6 +1122,7 @@ void collect_posterior_timings(abo_gp* g, bool with_var) {
             fi += ev_ms(e[4], e[5]);
         }
         work += (double)ps.rows * (double)ps.rows * (double)ps.M;
+        ozops += (double)ps.nmod * (double)ps.rows * (double)ps.rows * (double)ps.M;
     }
     g->tm.acq_kxz_ms = kx;
     g->tm.acq_var_gemm_ms = vg;
@@ -1080,8 +1132,8 @@ void collect_posterior_timings(abo_gp* g, bool with_var) {
     // ALGORITHMIC int8 operations of the residue GEMMs: n moduli × the triangular product R²·M per pass (R(R+1)/2 multiply-adds per
     // candidate over the R rows of W the pass contracts — R = N but for a bound pass —, 2 operations each ≈ R²).  What the kernel issues
     // beyond that — the upper halves of its 256-wide diagonal blocks (of which it skips 6 of 16 units), padding of N and M to 256 — is
-    // not credited.
-    g->tm.oz_gemm_ops = oz ? (double)g->tm.oz_nmod * work : 0.0;
+    // not credited.  The moduli are those each pass launched: a bound pass on its short plan counts that plan's.
+    g->tm.oz_gemm_ops = oz ? ozops : 0.0;
     // algorithmic (triangular) flop of the contraction: R²·M per pass
     g->tm.var_gemm_flop = with_var ? work : 0.0;
 }
@@ -3886,6 +3938,23 @@ int32_t abo_test_prune_force(int32_t rblocks, int32_t mode) {
     return ABO_OK;
 }
 
+int32_t abo_test_prune_bound_moduli(int32_t n) {
+    if (n != 0 && n != 14 && !kgen_short_moduli(n)) return fail(ABO_EINVAL, "abo_test_prune_bound_moduli: n = %d (0 = default, 8, 9, 10, 14)", n);
+    g_prune_bound_moduli.store(n);
+    return ABO_OK;
+}
+
+int32_t abo_test_prune_bound_plan(abo_gp* g, int32_t* sexp_b, double* delta, int64_t n_rows) {
+    if (!g || !sexp_b || !delta || n_rows < 0) return fail(ABO_EINVAL, "abo_test_prune_bound_plan: bad argument");
+    if (!g->pst.bound_rows || g->pb_rows <= 0 || n_rows > g->pb_rows)
+        return fail(ABO_EINVAL, "abo_test_prune_bound_plan: the last abo_acq on this handle ran no bound pass on a short plan over %lld rows", (long long)n_rows);
+    HIPCHK(hipSetDevice(g->prm.device));
+    HIPCHK(hipMemcpyAsync(sexp_b, g->oz_sexpb.p, sizeof(int) * n_rows, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(delta, g->oz_delta.p, sizeof(double) * n_rows, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(wait_stream(g->stream));
+    return ABO_OK;
+}
+
 int32_t abo_test_prune_bounds(abo_gp* g, double* out, int64_t M) {
     if (!g || !out || M < 0) return fail(ABO_EINVAL, "abo_test_prune_bounds: bad argument");
     if (!g->pst.bound_rows || g->pr_ub.cap < sizeof(double) * (size_t)M) return fail(ABO_EINVAL, "abo_test_prune_bounds: the last abo_acq on this handle ran no bound pass over %lld candidates", (long long)M);
@@ -3951,6 +4020,36 @@ int32_t abo_test_oz_contract(int32_t device, const double* W, int64_t ldw, int32
     oa.plan = &pl; oa.Kxz = Kxz; oa.ldk = ldk; oa.WR = wr.b.as<int8_t>(); oa.sexp = sexp; oa.bad_row = sexp + q;
     oa.KR = kr.b.as<int8_t>(); oa.U = u.b.as<int8_t>(); oa.bad_col = sexp + 2 * q; oa.partial = partial; oa.ldp = ldp;
     oa.Np = Np; oa.Mc = Mc; oa.nvalid = nvalid; oa.sK = oz_k_scale(kmax);
+    HIPCHK(launch_var_ozaki(oa, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_oz_contract_bound(int32_t device, const double* W, int64_t ldw, int32_t Np, int32_t nvalid, const double* Kxz, int64_t ldk,
+                                   int32_t Mc, double kmax, int32_t nmod_b, int32_t rblocks, double* partial, int64_t ldp, double* delta) {
+    if (!W || !Kxz || !partial || !delta) return fail(ABO_EINVAL, "abo_test_oz_contract_bound: null argument");
+    const int rows = 256 * rblocks;
+    if (Np <= 0 || Np % TB || Mc <= 0 || Mc % TB || nvalid < 0 || nvalid > Np || ldw < Np || ldk < Np || ldp < Mc || !(kmax > 0.0) ||
+        rblocks <= 0 || rows > pad_up(Np, 256))
+        return fail(ABO_EINVAL, "abo_test_oz_contract_bound: Np and Mc multiples of 128, nvalid <= Np, leading dimensions >= Np / Mc, kmax > 0, 256·rblocks <= pad256(Np)");
+    OzPlan pl, full;
+    if (!oz_make_plan(nmod_b, &pl) || !oz_make_plan(14, &full)) return fail(ABO_EINVAL, "abo_test_oz_contract_bound: %d moduli not supported", nmod_b);
+    HIPCHK(hipSetDevice(device));
+    const int64_t q = pad_up(Np, 256), mq = pad_up(Mc, 256);
+    ScratchBuf wr(device, nullptr), kr(device, nullptr), u(device, nullptr), ints(device, nullptr);
+    HIPCHK(wr.b.ensure((size_t)nmod_b * rows * q));
+    HIPCHK(kr.b.ensure(oz_k_bytes(nmod_b, Np, Mc)));
+    HIPCHK(u.b.ensure(oz_k_bytes(nmod_b, Np, Mc)));
+    HIPCHK(ints.b.ensure(sizeof(int) * (2 * q + mq + OZ_CTR_INTS)));
+    int* sexp = ints.b.as<int>();
+    const int bK = oz_bound_kbits(pl.eP, rows);
+    const int sKb = oz_k_scale(kmax, bK);
+    HIPCHK(oz_prepare_w_bound(pl, full, W, ldw, Np, nvalid, rows, bK, sKb, oz_k_scale(kmax), kmax * (1.0 + 0x1p-40), wr.b.as<int8_t>(), sexp, sexp + q,
+                              delta, nullptr));
+    OzVarArgs oa{};
+    oa.plan = &pl; oa.Kxz = Kxz; oa.ldk = ldk; oa.WR = wr.b.as<int8_t>(); oa.sexp = sexp; oa.bad_row = sexp + q;
+    oa.KR = kr.b.as<int8_t>(); oa.U = u.b.as<int8_t>(); oa.bad_col = sexp + 2 * q; oa.partial = partial; oa.ldp = ldp;
+    oa.Np = Np; oa.Mc = Mc; oa.nvalid = nvalid; oa.sK = sKb; oa.rblocks = rblocks; oa.delta = delta; oa.w_plane = (int64_t)rows * q;
     HIPCHK(launch_var_ozaki(oa, nullptr));
     HIPCHK(wait_stream(nullptr));
     return ABO_OK;

@@ -360,7 +360,10 @@ static hipError_t launch_fam(const KgenArgs& a, hipStream_t s) {
         return hipGetLastError();
     }
     if (a.res) {
-        if (a.res_n != 14) return hipErrorInvalidValue;          // kgen_writes_residues() told the caller not to ask
+        if (!kgen_writes_residues(a, a.res_n)) return hipErrorInvalidValue;      // the caller was told not to ask
+        if (a.res_n == 8) return launch_kgen_res_short8(a, s);                    // the bound pass's short plans: partial launch only
+        if (a.res_n == 9) return launch_kgen_res_short9(a, s);
+        if (a.res_n == 10) return launch_kgen_res_short10(a, s);
         return launch_kgen_res14(a, s);               // (writes every res_bad entry of the chunk itself)
     }
     return launch_kgen_dp<FAM, 0>(a, s);

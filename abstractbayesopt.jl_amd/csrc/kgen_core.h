@@ -130,7 +130,8 @@ __global__ void __launch_bounds__(256) kgen_kernel(KgenArgs p) {
 
 
 // launch kgen_kernel<FAM, dp, RES> for the run-time dp ∈ {1, 2, 4, 8, 16, 32}
-template <int FAM, int RES>
+// PART_ONLY: the partial launch (res_kmax > 0) alone is instantiated (the short plans of the bound pass: kgen_res_short.hip)
+template <int FAM, int RES, bool PART_ONLY = false>
 static hipError_t launch_kgen_dp(const KgenArgs& a, hipStream_t s) {
     dim3 grid(a.Mc / JT), block(256);
     if constexpr (RES != 0) {
@@ -148,6 +149,8 @@ static hipError_t launch_kgen_dp(const KgenArgs& a, hipStream_t s) {
             return hipGetLastError();
         }
     }
+    if constexpr (PART_ONLY) return hipErrorInvalidValue;
+    else
     switch (a.dp) {
         case 1: hipLaunchKernelGGL((kgen_kernel<FAM, 1, RES>), grid, block, 0, s, a); break;
         case 2: hipLaunchKernelGGL((kgen_kernel<FAM, 2, RES>), grid, block, 0, s, a); break;
@@ -162,5 +165,20 @@ static hipError_t launch_kgen_dp(const KgenArgs& a, hipStream_t s) {
 
 // kgen_res.hip: the RES = 14 instantiations
 hipError_t launch_kgen_res14(const KgenArgs& a, hipStream_t s);
+// kgen_res_short.hip (8 moduli), kgen_res_short9.hip, kgen_res_short10.hip: the partial launch under a short plan
+hipError_t launch_kgen_res_short8(const KgenArgs& a, hipStream_t s);
+hipError_t launch_kgen_res_short9(const KgenArgs& a, hipStream_t s);
+hipError_t launch_kgen_res_short10(const KgenArgs& a, hipStream_t s);
+
+template <int RES>
+static hipError_t launch_kgen_res_short(const KgenArgs& a, hipStream_t s) {
+    switch (a.family) {
+        case ABO_KERNEL_SE: return launch_kgen_dp<ABO_KERNEL_SE, RES, true>(a, s);
+        case ABO_KERNEL_MATERN52: return launch_kgen_dp<ABO_KERNEL_MATERN52, RES, true>(a, s);
+        case ABO_KERNEL_MATERN72: return launch_kgen_dp<ABO_KERNEL_MATERN72, RES, true>(a, s);
+        case ABO_KERNEL_MATERN32: return launch_kgen_dp<ABO_KERNEL_MATERN32, RES, true>(a, s);
+        default: return hipErrorInvalidValue;
+    }
+}
 
 }  // namespace abo

@@ -37,7 +37,14 @@ __global__ void __launch_bounds__(256) finalize_kernel(FinalizeArgs p) {
     }
     if (p.mu_out) p.mu_out[gj] = mu;
     if (p.var_out) p.var_out[gj] = var;
-    if (p.score_out) p.score_out[gj] = acq_score(p.kind, mu, var, p.p0, p.best_y);
+    if (p.score_out) {
+        double sc = acq_score(p.kind, mu, var, p.p0, p.best_y);
+        // the bound pass stores the GUARDED bound (margins and their derivation: prune_keep below): as stored it is ≥ the full pass's
+        // computed score of the candidate, not only ≥ up to those margins.  An infinite bound stays what it is (−Inf + Inf would be NaN,
+        // and a NaN bound ranks first in the threshold pass).
+        if (p.mu_tail && fabs(sc) < __builtin_inf()) sc = sc + fabs(sc) * PRUNE_REL + (p.kind == ABO_ACQ_LOGEI ? PRUNE_ABS_LOGEI : PRUNE_ABS);
+        p.score_out[gj] = sc;
+    }
 }
 
 hipError_t launch_finalize(const FinalizeArgs& a, hipStream_t s) {
@@ -765,6 +772,8 @@ hipError_t launch_gather_points(const double* Z, const int64_t* idx, int64_t idx
 //        EI = 1).  For s < −2|b| − 1, s̃ ≤ s(1 − 24u) + 9000u < b − E(b) ≤ b̃ without any margin.  2⁻³⁰ in LogEI is a factor 1 + 10⁻⁹ in
 //        EI: no effect on how much is pruned.  A bound of −Inf (EI bounded by exactly 0) makes the guard −Inf + Inf = NaN: kept.
 // A NaN bound, score or threshold keeps the candidate (NaN ranks first in the selection's order).
+// finalize_kernel applies the same guard once to the bound it stores, so the stored ub[j] itself dominates the computed score (what
+// abo_test_prune_bounds hands out); the comparison below keeps its own margins — a second 2⁻³⁰, as far from the survivor count as the first.
 __device__ __forceinline__ bool prune_keep(double ub, double tau, double abs_margin) {
     return !(ub + fabs(ub) * PRUNE_REL + abs_margin < tau);
 }

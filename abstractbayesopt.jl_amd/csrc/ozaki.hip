@@ -91,12 +91,58 @@ bool oz_make_plan(int n, OzPlan* out) {
 
 // ---- device helpers --------------------------------------------------------------------------------------------------------------
 // ---- row scales of W ---------------------------------------------------------------------------------------------------------------
-// one wave per row i < Np: L1 = Σ_{k≤i} |W[i][k]|, mx = max; s_i = min(eP − 53 − e(L1), 52 − e(mx)) with e(x) the frexp exponent
-// (x < 2^e), so that 2^s_i·L1·2^53 ≤ P/4 and |W'| < 2^52.  sexp[i] = s_i; rows ≥ Np (padding to 256) get 0.
+// one wave per row i < Np: L1 = Σ_{k≤i} |W[i][k]|, mx = max; s_i = min(eP − kbits − e(L1), 52 − e(mx)) with e(x) the frexp exponent
+// (x < 2^e), so that 2^s_i·L1·2^kbits ≤ P/4 and |W'| < 2^52.  sexp[i] = s_i; rows ≥ Np (padding to 256) get 0.  kbits = 53: the
+// full-width image of K (oz_k_scale's default), every plan but the bound pass's short one.
 // kper / ktg: columns k with k % kper != 0 carry an extra factor 2^ktg (the gradient outputs of a gradient-enhanced model, see
 // oz_prepare_w); kper = 1 → none.
+//
+// ---- the guarded bound (gd.delta != nullptr: the short plan of the pruned selection's bound pass) ----------------
+// The bound pass contracts the first R rows of W against K_XZ on a SHORT plan (n_b moduli, P_b = Π p_l, 2^eP_b ≤ P_b/4) whose exponent
+// budget is divided between the operands: K' = rint(K·2^sK_b) ≤ 2^(bK−1), W'_i = rint(W_i·2^s_i) with 2^s_i·‖W_i‖₁ < 2^(eP_b − bK), so
+// |Σ_k W'_ik K'_jk| ≤ (2^s_i·‖W_i‖₁ + (i+1)/2)·2^(bK−1) < P_b/4 and the reconstruction Ṽ_ij = (Σ_k W'_ik K'_jk)·2^−(s_i+sK_b) is that
+// integer, exactly.  Against V_ij = Σ_{k≤i} W_ik·K_jk on the fp64 operands (real arithmetic), with W' = W·2^s + a, K' = K·2^sK + b,
+// |a|, |b| ≤ ½, 0 ≤ K_jk ≤ kmax = σ_f²(1 + 2^-40):
+//     |Ṽ_ij − V_ij| ≤ A(s_i, sK_b),   A(s, sK) = ½·2^−sK·‖W_i‖₁ + ½·2^−s·(i+1)·kmax + ¼·(i+1)·2^−(s+sK).
+// The bit split: the K term does not grow with the row index, the W term does by (i+1)·kmax/‖W_i‖₁, so W gets ⌈log₂R⌉ more bits than
+// K: bK = ⌊(eP_b − ⌈log₂R⌉)/2⌋ (oz_bound_kbits; n_b = 8, R = 1024: eP_b = 61, bK = 25, 36 bits below the row norm for W).
+// What the bound is compared with is not V but the FULL plan's computed v_ij (the survivor / threshold / fallback passes):
+//     |V''_ij − V_ij| ≤ A(s''_i, sK'')    the same formula at the full plan's own scales (s''_i is recomputed here, by the rule above);
+//     either reconstruction in fp64:  c1 and c1 − Q·P1 are exact, c2 takes n roundings of ≤ n·2^7·2^(t−53) and c2 − Q·P2 one of
+//     ≤ n·2^8·2^(t−53) (t = bitlen(P) − 41 = eP − 38), i.e. ≤ rec = (128n² + 256n)·2^(eP−91) integer units (gd.rec_b, gd.rec_full), the
+//     closing sum one relative 2^-53, the scaling none; the subtraction |ṽ| − δ below one more relative 2^-53.  The relative terms
+//     are of values ≤ ‖W_i‖₁·kmax + A: together ≤ 2^-50·(‖W_i‖₁·kmax + A_b + A_full).
+// delta[i] = (A(s_i, sK_b) + A(s''_i, sK'') + rec_b·2^−(s_i+sK_b) + rec_full·2^−(s''_i+sK'') + 2^-50·(…))·(1 + 2^-40), evaluated on
+// L1u = L1·(1 + (i+1)·2^-52) ≥ ‖W_i‖₁ (the wave's sum of i+1 non-negative terms errs by less than (i+1)·2^-53 relative); the factor
+// 1 + 2^-40 covers the roundings of this expression itself (all terms positive, fewer than 32 operations).  Then, as fp64 numbers,
+//     d_ij = max(|ṽ_ij| − delta[i], 0) ≤ |v_ij|   for every row i and candidate j,
+// and since fp64 addition and fma are monotone and oz_crt_kernel sums the rows of a candidate in one fixed order whatever the plan
+// (the same lanes, steps, shuffles and LDS order; finalize_kernel then adds the 128-row blocks in order), every partial sum of d²
+// is ≤ the same partial sum of v²: the bound pass's sum over its rows is ≤ the prefix over those rows of the full pass's computed
+// column sum, and the rest of that sum only adds non-negative terms.  σ²_R(bound) ≥ σ²(full pass, as computed).  (The column sums are
+// shaved by 1 − (R + 16)·2^-52 on top — not needed while the two passes share their summation order; it keeps the claim true should
+// they ever stop sharing it.)  A row with a non-finite or overflowing norm gets delta = +Inf (it contributes 0, and bad_row makes
+// the bound NaN: kept, as today); an all-zero row 0.
+struct OzGuardArgs {
+    double* delta;          // [Np256] or nullptr: no guard (every plan but the short one)
+    int eP_full, sK_b, sK_full;
+    double kmax, rec_b, rec_full;
+};
+
+// THE row-scale rule, for every plan: the full plan's scales (oz_prepare_w) and the guard's re-derivation of them go through this one
+// function, so δ cannot drift from the scale the full pass actually uses (e1 = e(L1), e2 = e(max))
+__device__ __forceinline__ int oz_row_scale(int eP, int kbits, int e1, int e2) {
+    const int sa = eP - kbits - e1, sb = 52 - e2;
+    return sa < sb ? sa : sb;
+}
+constexpr int OZ_FULL_KBITS = 53;      // the full-width image of K: what oz_prepare_w scales the handle's plan for
+
+__device__ __forceinline__ double oz_guard_A(double l1u, double nk, double n1, int s, int sK) {
+    return 0.5 * __builtin_ldexp(l1u, -sK) + 0.5 * __builtin_ldexp(nk, -s) + 0.25 * __builtin_ldexp(n1, -(s + sK));
+}
+
 __global__ void __launch_bounds__(256) oz_rowscale_kernel(const double* __restrict__ W, int64_t ldw, int Np, int Np256, int eP,
-                                                          int* __restrict__ sexp, int kper, int ktg) {
+                                                          int* __restrict__ sexp, int kper, int ktg, int kbits, OzGuardArgs gd) {
     const double cw = __builtin_ldexp(1.0, ktg);
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= Np256) return;
@@ -116,14 +162,25 @@ __global__ void __launch_bounds__(256) oz_rowscale_kernel(const double* __restri
     }
     if (lane == 0) {
         int s = 0;
+        double dl = 0.0;
         if (mx > 0.0 && l1 < 1.0e300) {                // a NaN/Inf row keeps s = 0: its residues are garbage, its V is flagged
             int e1, e2;
             (void)frexp(l1, &e1);
             (void)frexp(mx, &e2);
-            const int sa = eP - 53 - e1, sb = 52 - e2;
-            s = sa < sb ? sa : sb;
-        }
+            s = oz_row_scale(eP, kbits, e1, e2);
+            if (gd.delta) {
+                // the full plan's scale of this row: same kernel, same l1 / mx (kper = 1: the bound pass is StandardGP only), same rule
+                const int sf = oz_row_scale(gd.eP_full, OZ_FULL_KBITS, e1, e2);
+                const double n1 = (double)(row + 1);
+                const double l1u = l1 * (1.0 + n1 * 0x1p-52);
+                const double Ab = oz_guard_A(l1u, n1 * gd.kmax, n1, s, gd.sK_b), Af = oz_guard_A(l1u, n1 * gd.kmax, n1, sf, gd.sK_full);
+                dl = Ab + Af + __builtin_ldexp(gd.rec_b, -(s + gd.sK_b)) + __builtin_ldexp(gd.rec_full, -(sf + gd.sK_full)) +
+                     0x1p-50 * (l1u * gd.kmax + Ab + Af);
+                dl *= 1.0 + 0x1p-40;
+            }
+        } else if (!(mx == 0.0)) dl = __builtin_inf();
         sexp[row] = s;
+        if (gd.delta) gd.delta[row] = dl;
     }
 }
 
@@ -633,6 +690,8 @@ struct OzCrtArgs {
     int rmode, rper, rtg;  // candidate j is a derivative output (oz_row_output != 0): its image was taken at 2^-rtg, sums get 2^(2 rtg)
     int64_t r0, rpts;
     int* ctr_reset;        // the residue GEMM's tile counters (OZ_CTR_INTS): zeroed here, behind the GEMM that used them (or nullptr)
+    const double* delta;   // GUARD: delta[i] per row (oz_rowscale_kernel: "the guarded bound"); nullptr = exact
+    double shave;          // GUARD: factor on the column sums
     OzPlan pl;
 };
 
@@ -643,7 +702,9 @@ struct OzCrtArgs {
 // NM > 0: the moduli count is the compile-time NM (the default plan): the residues of a row's NM planes are fetched by NM loads issued
 // back to back — each wave keeps NM × 1 KiB in flight instead of one load per loop trip, which is what a kernel that reads 7.5 GB once
 // needs to approach the HBM rate — and read past the caches (non-temporal: nothing here is touched twice).
-template <int NM>
+// GUARD (the short plan of the pruned selection's bound pass): the sums are of max(|V_ij| − delta[i], 0)² and leave multiplied by
+// a.shave (oz_rowscale_kernel: "the guarded bound"); the exact form's code does not change.
+template <int NM, bool GUARD = false>
 __global__ void __launch_bounds__(256) oz_crt_kernel(OzCrtArgs a) {
     __shared__ double red[3][16][17];
     const int tb = blockIdx.y, tj = blockIdx.x;
@@ -671,6 +732,8 @@ __global__ void __launch_bounds__(256) oz_crt_kernel(OzCrtArgs a) {
                 for (int l = 0; l < NM; ++l) wl[l] = __builtin_nontemporal_load(reinterpret_cast<const v4i_t*>(u + (int64_t)l * (OZ_T * OZ_T)));
             }
             const double sc = __builtin_ldexp(1.0, -(a.sexp[i] + a.sK));
+            double dl = 0.0;
+            if constexpr (GUARD) dl = a.delta[i];
             if (a.bad_row && a.bad_row[i]) bad = true;
             // four candidates (one dword of every plane) at a time: 8 partial sums live instead of 32 — 4 waves per SIMD instead of 3
 #pragma unroll
@@ -699,7 +762,8 @@ __global__ void __launch_bounds__(256) oz_crt_kernel(OzCrtArgs a) {
                 for (int b = 0; b < 4; ++b) {
                     const double Q = __builtin_rint((c1[b] + c2[b]) * a.pl.invP);
                     const double cp = __builtin_fma(-Q, a.pl.P1, c1[b]) + __builtin_fma(-Q, a.pl.P2, c2[b]);
-                    const double v = cp * sc;
+                    double v = cp * sc;
+                    if constexpr (GUARD) v = __builtin_fmax(__builtin_fabs(v) - dl, 0.0);
                     sum[4 * g4 + b] = __builtin_fma(v, v, sum[4 * g4 + b]);
                 }
             }
@@ -725,7 +789,8 @@ __global__ void __launch_bounds__(256) oz_crt_kernel(OzCrtArgs a) {
             const double t = ((sum[b] + red[0][cg][b]) + red[1][cg][b]) + red[2][cg][b];
             const bool bb = anybad || (a.bad_col && a.bad_col[j + b]);
             const double cf = (a.rmode && oz_row_output(a.rmode, a.rper, a.r0, a.rpts, j + b) != 0) ? __builtin_ldexp(1.0, 2 * a.rtg) : 1.0;
-            a.partial[(int64_t)tb * a.ldp + j + b] = bb ? nan : t * cf;
+            if constexpr (GUARD) a.partial[(int64_t)tb * a.ldp + j + b] = bb ? nan : t * a.shave;
+            else a.partial[(int64_t)tb * a.ldp + j + b] = bb ? nan : t * cf;
         }
     }
 }
@@ -828,7 +893,7 @@ hipError_t oz_prepare_w(const OzPlan& pl, const double* W, int64_t ldw, int Np, 
     const int Np256 = (int)pad_up(Np, OZ_T);
     hipError_t e = hipMemsetAsync(bad_row, 0, sizeof(int) * Np256, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(oz_rowscale_kernel, dim3((Np256 + 3) / 4), dim3(256), 0, s, W, ldw, nvalid, Np256, pl.eP, sexp, kper, ktg);
+    hipLaunchKernelGGL(oz_rowscale_kernel, dim3((Np256 + 3) / 4), dim3(256), 0, s, W, ldw, nvalid, Np256, pl.eP, sexp, kper, ktg, OZ_FULL_KBITS, OzGuardArgs{});
     OzQuantArgs q{};
     q.in = W; q.ldin = ldw; q.rows_in = nvalid; q.cols_in = Np; q.rows_out = Np256; q.cols_out = Np256; q.lower = 1;
     q.srow = sexp; q.sconst = 0; q.kper = kper; q.ktg = ktg; q.rmode = 0; q.rper = 1; q.rtg = 0; q.r0 = 0; q.rpts = 1; q.out = WR; q.ld = Np256; q.plane = (int64_t)Np256 * Np256; q.bad = bad_row; q.pl = pl;
@@ -838,10 +903,42 @@ hipError_t oz_prepare_w(const OzPlan& pl, const double* W, int64_t ldw, int Np, 
 }
 
 // sK: K' = rint(K·2^sK) < 2^53 for K ≤ kmax (kmax = σ_f²: the stationary kernels of this library peak at distance 0)
-int oz_k_scale(double kmax) {
+// bits < 53 (the short plan of the bound pass): K·2^sK < 2^(bits−1), K' ≤ 2^(bits−1)
+int oz_k_scale(double kmax, int bits) {
     int e;
     (void)std::frexp(kmax * (1.0 + 1e-12), &e);        // kmax < 2^e
-    return 52 - e;                                      // K' < 2^52·(1+…) < 2^53
+    return bits - 1 - e;                                // K' < 2^52·(1+…) < 2^53
+}
+
+// ---- the short plan of the bound pass: bit split and the planes of the first rows of W ("the guarded bound" above) -------------------
+int oz_bound_kbits(int eP, int rows) {
+    int lg = 0;
+    while (((int64_t)1 << lg) < rows) ++lg;             // ⌈log₂ rows⌉
+    int bK = (eP - lg) / 2;
+    if (bK > 53) bK = 53;
+    return bK < 2 ? 2 : bK;
+}
+
+hipError_t oz_prepare_w_bound(const OzPlan& pl, const OzPlan& full, const double* W, int64_t ldw, int Np, int nvalid, int rows, int kbits, int sK_b,
+                              int sK_full, double kmax, int8_t* WRb, int* sexp_b, int* bad_row_b, double* delta, hipStream_t s) {
+    const int Np256 = (int)pad_up(Np, OZ_T);
+    if (rows <= 0 || rows % OZ_T || rows > Np256) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(bad_row_b, 0, sizeof(int) * rows, s);
+    if (e != hipSuccess) return e;
+    const int nv = nvalid < rows ? nvalid : rows;
+    OzGuardArgs gd{};
+    gd.delta = delta; gd.eP_full = full.eP; gd.sK_b = sK_b; gd.sK_full = sK_full; gd.kmax = kmax;
+    gd.rec_b = (128.0 * pl.n * pl.n + 256.0 * pl.n) * std::ldexp(1.0, pl.eP - 91);
+    gd.rec_full = (128.0 * full.n * full.n + 256.0 * full.n) * std::ldexp(1.0, full.eP - 91);
+    hipLaunchKernelGGL(oz_rowscale_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, W, ldw, nv, rows, pl.eP, sexp_b, 1, 0, kbits, gd);
+    // rows × rows of the triangle, in planes that keep the full planes' row stride (block (R, H) of a plane at (R·nhs + H)·16 KB,
+    // nhs = Np256 / 64): the bytes k ≥ rows of a row are neither written here nor read by a contraction limited to these rows
+    OzQuantArgs q{};
+    q.in = W; q.ldin = ldw; q.rows_in = nv; q.cols_in = Np < rows ? Np : rows; q.rows_out = rows; q.cols_out = rows; q.lower = 1;
+    q.srow = sexp_b; q.sconst = 0; q.kper = 1; q.ktg = 0; q.rmode = 0; q.rper = 1; q.rtg = 0; q.r0 = 0; q.rpts = 1; q.out = WRb; q.ld = Np256; q.plane = (int64_t)rows * Np256; q.bad = bad_row_b; q.pl = pl;
+    const int64_t threads = (int64_t)rows * (rows / 16);
+    hipLaunchKernelGGL(oz_quant_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, q);
+    return hipGetLastError();
 }
 
 hipError_t launch_var_ozaki(const OzVarArgs& v, hipStream_t s) {
@@ -861,7 +958,7 @@ hipError_t launch_var_ozaki(const OzVarArgs& v, hipStream_t s) {
     OzGemmArgs g{};
     g.KR = v.KR; g.WR = v.WR; g.U = v.U;
     g.nhs = Np256 / 64;
-    g.sK = (int64_t)Mc256 * Np256; g.sW = (int64_t)Np256 * Np256;
+    g.sK = (int64_t)Mc256 * Np256; g.sW = v.w_plane > 0 ? v.w_plane : (int64_t)Np256 * Np256;
     // (rblocks: the tile list, the layout of U and the reconstruction cover the first row blocks only; nhs, the stride between the
     // row blocks of a plane, stays that of the buffers)
     g.Ti = v.rblocks > 0 && v.rblocks < Np256 / OZ_T ? v.rblocks : Np256 / OZ_T; g.Tj = Mc256 / OZ_T; g.n = pl.n;
@@ -899,7 +996,12 @@ hipError_t launch_var_ozaki(const OzVarArgs& v, hipStream_t s) {
     c.rmode = v.rmode; c.rper = v.rper; c.rtg = v.ktg; c.r0 = v.r0; c.rpts = v.rpts;
     c.ctr_reset = v.ctr_clean ? v.bad_col + Mc256 : nullptr;
     const int tbs = 2 * g.Ti < v.Np / 128 ? 2 * g.Ti : v.Np / 128;      // 128-row blocks of partial
-    if (pl.n == 14) hipLaunchKernelGGL(oz_crt_kernel<14>, dim3((v.Mc + 255) / 256, tbs), dim3(256), 0, s, c);
+    if (v.delta) {             // the guarded bound of a short plan
+        if (!(v.rblocks > 0) || v.rmode) return hipErrorInvalidValue;
+        c.delta = v.delta; c.shave = 1.0 - (double)(c.nvalid + 16) * 0x1p-52;
+        if (pl.n == 8) hipLaunchKernelGGL((oz_crt_kernel<8, true>), dim3((v.Mc + 255) / 256, tbs), dim3(256), 0, s, c);
+        else hipLaunchKernelGGL((oz_crt_kernel<0, true>), dim3((v.Mc + 255) / 256, tbs), dim3(256), 0, s, c);
+    } else if (pl.n == 14) hipLaunchKernelGGL(oz_crt_kernel<14>, dim3((v.Mc + 255) / 256, tbs), dim3(256), 0, s, c);
     else hipLaunchKernelGGL(oz_crt_kernel<0>, dim3((v.Mc + 255) / 256, tbs), dim3(256), 0, s, c);
     e = hipGetLastError();
     if (e == hipSuccess && v.ctr_clean) *v.ctr_clean = v.bad_col + Mc256;

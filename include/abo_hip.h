@@ -768,7 +768,14 @@ int32_t abo_test_prune_plan(int64_t rows, int64_t M, int32_t k, int32_t want_sco
  * mode 1 = a threshold of −Inf (every candidate survives: the selection's worst case on any data), mode 2 = the path is off, as under
  * ABO_ACQ_PRUNE=0.  (0, 0) restores the defaults. */
 int32_t abo_test_prune_force(int32_t rblocks, int32_t mode);
-/* out[0..M) (host) = the upper bounds the last abo_acq on this handle computed in its bound pass */
+/* Moduli of the bound pass's residue plan, process-wide: 8, 9, 10 = a short plan with the guard of csrc/ozaki.hip ("the guarded
+ * bound"), 14 = the handle's plan, exact; 0 restores ABO_PRUNE_BOUND_MODULI / the default (8). */
+int32_t abo_test_prune_bound_moduli(int32_t n);
+/* sexp_b[0..n_rows), delta[0..n_rows) (host) = the row scales s_i and the guards delta[i] of the short plan the last abo_acq on this
+ * handle ran its bound pass on (n_rows ≤ 256 × its row blocks); an error when that pass ran on the handle's own plan */
+int32_t abo_test_prune_bound_plan(abo_gp* gp, int32_t* sexp_b, double* delta, int64_t n_rows);
+/* out[0..M) (host) = the upper bounds the last abo_acq on this handle stored in its bound pass: the score at (μ̃ − ε, σ²_R) plus the
+ * margins of prune_keep (csrc/misc.hip), so that each is ≥ the full pass's computed score of the candidate */
 int32_t abo_test_prune_bounds(abo_gp* gp, double* out, int64_t M);
 /* mu[0..M), eps[0..M) (host) = the mean μ̃ the last abo_acq on this handle computed in its bound pass (first row blocks' columns by the
  * full generator, the others by the shortened sequences of csrc/kgen_tail.hip) and the distance ε it proved to the full pass's mean:
@@ -784,6 +791,12 @@ int32_t abo_test_oz_plan(int32_t n, int32_t* p, double* tables, double* scal, in
  * buffers; Np, Mc multiples of 128; partial [Np/128][ldp]). */
 int32_t abo_test_oz_contract(int32_t device, const double* W, int64_t ldw, int32_t Np, int32_t nvalid, const double* Kxz, int64_t ldk,
                              int32_t Mc, double kmax, int32_t nmod, double* partial, int64_t ldp);
+/* The same for the first 256·rblocks rows of W on the SHORT plan of the pruned selection's bound pass (nmod_b moduli, the bit split
+ * and the guard of csrc/ozaki.hip, "the guarded bound"): partial[tb][j] for tb < 2·rblocks = Σ max(|Ṽ_ij| − delta[i], 0)², and
+ * delta[0 .. 256·rblocks) (device) the guards; every entry ≤ what abo_test_oz_contract writes there with 14 moduli, NaN for a 128-row
+ * block that holds a non-finite row of W.  kmax bounds Kxz up to the factor 1 + 2^-40. */
+int32_t abo_test_oz_contract_bound(int32_t device, const double* W, int64_t ldw, int32_t Np, int32_t nvalid, const double* Kxz, int64_t ldk,
+                                   int32_t Mc, double kmax, int32_t nmod_b, int32_t rblocks, double* partial, int64_t ldp, double* delta);
 /* f[j], grad[j][0..d) = value and analytic gradient of the acquisition function at Z[j] (host buffers, M × d): the evaluation
  * the refinement stage is built on, one workgroup per point */
 int32_t abo_test_acq_grad(abo_gp* gp, int32_t kind, double p0, double best_y, const double* Z, int64_t M, int32_t d, double* f,
