@@ -14,7 +14,7 @@ HOST, DEVICE = 0, 1
 
 EXPORTS = ["abo_create", "abo_set_contraction", "abo_create_grad", "abo_predict_grad", "abo_predict_grad_cov", "abo_retain", "abo_destroy", "abo_fit", "abo_append", "abo_append_grad", "abo_cand_create", "abo_cand_destroy",
            "abo_cand_refresh", "abo_cand_downdate", "abo_cand_save", "abo_cand_restore", "abo_cand_acq", "abo_cand_get", "abo_cand_point", "abo_cand_exclude", "abo_predict", "abo_acq", "abo_nlml", "abo_nlml_grad", "abo_lhs", "abo_score",
-           "abo_get_factor", "abo_get_n", "abo_get_data", "abo_get_timings", "abo_get_prune_stats", "abo_last_error", "abo_abi_version", "abo_pool_trim",
+           "abo_get_factor", "abo_get_n", "abo_get_data", "abo_get_timings", "abo_get_prune_stats", "abo_get_prune_levels", "abo_last_error", "abo_abi_version", "abo_pool_trim",
            "abo_mgpu_create", "abo_mgpu_clone", "abo_mgpu_destroy", "abo_mgpu_info", "abo_mgpu_get", "abo_mgpu_fit",
            "abo_mgpu_predict", "abo_mgpu_acq", "abo_mgpu_acq_lhs", "abo_mgpu_append", "abo_mgpu_cand_create",
            "abo_mgpu_cand_create_lhs", "abo_mgpu_cand_refresh", "abo_mgpu_cand_destroy", "abo_mgpu_cand_acq",
@@ -27,7 +27,7 @@ EXPORTS = ["abo_create", "abo_set_contraction", "abo_create_grad", "abo_predict_
            "abo_paths_append", "abo_paths_attach", "abo_paths_detach", "abo_paths_top", "abo_paths_values", "abo_paths_append_stats_get",
            "abo_score_mes", "abo_acq_mes", "abo_cand_acq_mes", "abo_refine_mes", "abo_optimize_acquisition_mes"]
 TEST_EXPORTS = ["abo_test_gemm_nt", "abo_test_kappa", "abo_test_oz_plan", "abo_test_oz_contract", "abo_test_acq_grad",
-                "abo_test_acq_grad_terms", "abo_test_prune_plan", "abo_test_prune_force", "abo_test_prune_bounds", "abo_test_prune_mean",
+                "abo_test_acq_grad_terms", "abo_test_prune_plan", "abo_test_prune_force", "abo_test_prune_levels", "abo_test_prune_plan_levels", "abo_test_prune_bounds", "abo_test_prune_mean",
                 "abo_test_kappa_tail", "abo_test_prune_bound_moduli", "abo_test_prune_bound_plan", "abo_test_oz_contract_bound", "abo_test_acq_partials", "abo_test_mes_partials", "abo_test_acq_grad_mes"]
 ABI_VERSION = 7
 CONTRACT_AUTO, CONTRACT_FP64, CONTRACT_INT8 = 0, 1, 2
@@ -177,9 +177,12 @@ def lib():
     L.abo_get_data.argtypes = [vp, vp, vp]
     L.abo_get_timings.argtypes = [vp, C.POINTER(AboTimings)]
     L.abo_get_prune_stats.argtypes = [vp, C.POINTER(AboPruneStats)]
+    L.abo_get_prune_levels.argtypes = [vp, vp]
     if hooks:
         L.abo_test_prune_plan.argtypes = [i64, i64, i32, i32, i32, f64, i32, i32, i32, vp]
         L.abo_test_prune_force.argtypes = [i32, i32]
+        L.abo_test_prune_levels.argtypes = [i32, i64]
+        L.abo_test_prune_plan_levels.argtypes = [i64, i64, i32, i32, i32, f64, i32, i32, i32, vp]
         L.abo_test_prune_bounds.argtypes = [vp, vp, i64]
         L.abo_test_prune_mean.argtypes = [vp, vp, vp, i64]
         L.abo_test_prune_bound_moduli.argtypes = [i32]

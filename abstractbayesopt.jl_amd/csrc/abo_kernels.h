@@ -508,6 +508,9 @@ constexpr int PRUNE_SCAN_E = 1024;       // candidates per workgroup of the comp
 // Stream-ordered, no atomics: the same list on every run.
 hipError_t launch_prune_compact(const double* ub, int64_t M, const double* tau, double abs_margin, int* blk, int64_t* sel, int64_t* count,
                                 hipStream_t s);
+// ub[sel[i]] = min(ub[sel[i]], ub2[i]) for i < n, a NaN on either side giving NaN (kept, as above): the second bound level's tighter
+// bounds of the first level's survivors, written back into the bounds of all candidates.  sel: distinct indices (a compacted list).
+hipError_t launch_prune_min_scatter(double* ub, const int64_t* sel, const double* ub2, int64_t n, hipStream_t s);
 // top_idx[e] = sel[top_idx[e]] + idx_base for e < k (−1 stays): positions in a compacted list back to candidate indices
 hipError_t launch_prune_map(int64_t* top_idx, int k, const int64_t* sel, int64_t idx_base, hipStream_t s);
 

@@ -378,12 +378,14 @@ struct abo_gp {
     uint64_t oz_gen = 0;
     int64_t oz_N = -1;
     // the posterior passes of the current call, in launch order (their per-chunk events are read back with them): the pruned top-k
-    // selection of abo_acq runs up to three, everything else one
+    // selection of abo_acq runs up to five (two bound levels, threshold, survivors or the fallback's full pass), everything else one
     struct PostPass { int64_t chunk0, nchunk, M, rows; int nmod; };   // first chunk's event slot, chunks, candidate rows, rows of W contracted, moduli launched
     std::vector<PostPass> passes;
     DevBuf pr_ub, pr_z, pr_sc, pr_sel, pr_blk, pr_tv, pr_ti;   // pruned selection: bounds, gathered points, their scores, survivor list, scan scratch, threshold pairs
     DevBuf pr_mut, pr_eps, pr_nrm;                             // its bound pass: μ̃ and ε of every candidate, the norms ε is built from (kgen_tail.hip)
+    DevBuf pr_ub2, pr_mut2, pr_eps2;                           // second bound level: bounds, μ̃ and ε of the first level's survivors, in list order
     abo_prune_stats pst{};
+    struct PruneLevels { int64_t rows1, s1, rows2, s2; double ms1, ms2; } plv{};      // abo_get_prune_levels
     // the bound pass's short residue plan (ozaki.hip: "the guarded bound"): the plan, the residue planes of the first bound rows of W
     // under it, their row scales, flags and guards — rebuilt by every bound pass (pb_rows of them by the last one, at pb_sK)
     OzPlan oz_plan_b{};
@@ -399,7 +401,7 @@ struct abo_gp {
         DevBuf* all[] = {&alpha, &vext, &tvec, &T, &info, &scal, &Zdev, &Kxz, &partial, &mu_c, &mu_all, &var_all,
                          &score_all, &tk_keys0, &tk_keys1, &tk_idx0, &tk_idx1, &top_val, &top_idx,
                          &oz_WR, &oz_sexp, &oz_badr, &oz_KR, &oz_U, &oz_badc, &pr_ub, &pr_z, &pr_sc, &pr_sel, &pr_blk, &pr_tv, &pr_ti,
-                         &pr_mut, &pr_eps, &pr_nrm, &ystar, &oz_WRb, &oz_sexpb, &oz_badrb, &oz_delta};
+                         &pr_mut, &pr_eps, &pr_nrm, &pr_ub2, &pr_mut2, &pr_eps2, &ystar, &oz_WRb, &oz_sexpb, &oz_badrb, &oz_delta};
         for (DevBuf* b : all) b->dev = dev;
     }
 
@@ -407,7 +409,7 @@ struct abo_gp {
         DevBuf* all[] = {&alpha, &vext, &tvec, &T, &info, &scal, &Zdev, &Kxz, &partial, &mu_c, &mu_all, &var_all,
                          &score_all, &tk_keys0, &tk_keys1, &tk_idx0, &tk_idx1, &top_val, &top_idx,
                          &oz_WR, &oz_sexp, &oz_badr, &oz_KR, &oz_U, &oz_badc, &pr_ub, &pr_z, &pr_sc, &pr_sel, &pr_blk, &pr_tv, &pr_ti,
-                         &pr_mut, &pr_eps, &pr_nrm, &ystar, &oz_WRb, &oz_sexpb, &oz_badrb, &oz_delta};
+                         &pr_mut, &pr_eps, &pr_nrm, &pr_ub2, &pr_mut2, &pr_eps2, &ystar, &oz_WRb, &oz_sexpb, &oz_badrb, &oz_delta};
         for (DevBuf* b : all) b->release();
         oz_N = -1;
         oz_ctr_clean = nullptr;
@@ -550,7 +552,7 @@ void fit_collect(abo_gp* g) {
     g->tm.fit_total_ms = ev_ms(g->evs()[0], g->evs()[4]);
 }
 
-constexpr size_t EV_BASE = 14;        // 0-4 fit phases, 5-7 acquisition call, 8-9 residue planes of W, 10-13 passes of the pruned selection; from EV_BASE: per-chunk events of a
+constexpr size_t EV_BASE = 16;        // 0-4 fit phases, 5-7 acquisition call, 8-9 residue planes of W, 10-13 passes of the pruned selection, 14-15 its second bound level; from EV_BASE: per-chunk events of a
                                       // posterior call, or (inside a fit) the strip events of the factorisation's look-ahead
 constexpr size_t EV_PER_CHUNK = 8;   // kgen 0-1, contraction 2-3, epilogue 4-5, int8 pipeline: end of quantisation 6, end of GEMM 7
 
@@ -861,6 +863,7 @@ int32_t oz_planes_of_w(abo_gp* g) {
 // the contraction covers the first rblocks 256-row blocks of W — var / score then come from σ²_R ≥ σ² and from μ̃ − ε ≤ μ: the mean's
 // columns past those blocks are summed by the cheaper launch_kgen_tail, which also proves ε ≥ |μ̃ − μ| (kgen_tail.hip).
 // more: a further pass of the same call — its events and counts are kept next to those of the passes before it.
+// level2: a bound pass over the survivors of a first one — μ̃ and ε go to buffers of their own.
 constexpr int32_t PRUNE_UNAVAILABLE = -100;
 
 #ifdef ABO_TEST_HOOKS
@@ -884,7 +887,7 @@ int prune_bound_moduli() {
 
 int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0, double best_y, double* mu_out,
                   double* var_out, double* score_out, int pc = 1, int point_major = 0, double* kstore = nullptr,
-                  int64_t ldstore = 0, int rblocks = 0, bool more = false) {
+                  int64_t ldstore = 0, int rblocks = 0, bool more = false, bool level2 = false) {
     const int64_t M = Mpts * pc;                         // candidate rows
     hipStream_t s = g->stream;
     const int64_t Np = g->Np;
@@ -903,9 +906,11 @@ int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0
     }
     HIPCHK(g->partial.ensure(sizeof(double) * T * Mc));
     HIPCHK(g->mu_c.ensure(sizeof(double) * Mc));
+    DevBuf& mut = level2 ? g->pr_mut2 : g->pr_mut;       // (the first level's μ̃ and ε of all candidates stay what abo_test_prune_mean reads)
+    DevBuf& eps = level2 ? g->pr_eps2 : g->pr_eps;
     if (rblocks > 0) {
-        HIPCHK(g->pr_mut.ensure(sizeof(double) * M));
-        HIPCHK(g->pr_eps.ensure(sizeof(double) * M));
+        HIPCHK(mut.ensure(sizeof(double) * M));
+        HIPCHK(eps.ensure(sizeof(double) * M));
         HIPCHK(g->pr_nrm.ensure(sizeof(double) * 4));
     }
     const int64_t nchunk = (M + Mc - 1) / Mc;
@@ -978,7 +983,7 @@ int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0
         if (rblocks > 0) {
             KgenTailArgs kt{};
             kt.Xs = ka.Xs; kt.Z = Zd; kt.alpha = ka.alpha; kt.norms = g->pr_nrm.as<double>();
-            kt.mu_tail = g->pr_mut.as<double>(); kt.eps = g->pr_eps.as<double>();
+            kt.mu_tail = mut.as<double>(); kt.eps = eps.as<double>();
             kt.M = Mpts; kt.j0 = j0; kt.Mc = mcp; kt.N = (int)g->npts; kt.Np = (int)Np; kt.k0 = ka.res_kmax; kt.d = g->d; kt.dp = g->dp; kt.family = ka.family;
             kt.s = ka.s; kt.sigma_f2 = ka.sigma_f2; kt.mean_c = ka.mean_c;
             HIPCHK(launch_kgen_tail(kt, s));
@@ -1019,7 +1024,7 @@ int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0
         fa.T = (var_out || score_out) ? (rblocks > 0 && 2 * rblocks < T ? 2 * rblocks : T) : 0; fa.Mc = mcp; fa.kind = kind; fa.sigma_f2 = g->prm.sigma_f2;
         fa.p0 = p0; fa.best_y = best_y;
         fa.prior_grad = grad_prior_var(g); fa.pc = pc; fa.point_major = point_major; fa.Mpts = Mpts;
-        if (rblocks > 0) { fa.mu_tail = g->pr_mut.as<double>(); fa.mu_eps = g->pr_eps.as<double>(); }
+        if (rblocks > 0) { fa.mu_tail = mut.as<double>(); fa.mu_eps = eps.as<double>(); }
         PHASE_EVENT(e[4], s);
         HIPCHK(launch_finalize(fa, s));
         PHASE_EVENT(e[5], s);
@@ -1805,11 +1810,15 @@ struct PrunePlan {
     int rblocks;            // 256-row blocks of W in the bound pass
     int64_t k0;             // candidates whose exact scores set the threshold
     int64_t max_survivors;  // more than this: the ordinary full pass runs instead of the survivor pass
+    int rblocks0;           // 256-row blocks of a first, narrower bound level over all candidates (0: none — one bound pass, at rblocks)
+    int64_t level2_min;     // the pass at rblocks runs on the first level's survivors when there are more than this many
 };
 
 #ifdef ABO_TEST_HOOKS
 std::atomic<int> g_prune_force_rblocks{0};      // abo_test_prune_force: row blocks of the bound pass (0 = the rule); mode 1 = a threshold
 std::atomic<int> g_prune_force_mode{0};         // of −Inf (every candidate survives: the worst case, on any data), 2 = as ABO_ACQ_PRUNE=0
+std::atomic<int> g_prune_pre_rblocks{0};        // abo_test_prune_levels: row blocks of the first level (−1 = none, 0 = the rule)
+std::atomic<int64_t> g_prune_level2_min{-1};    // … and the survivor count above which the second runs (−1 = the rule)
 #endif
 
 bool prune_enabled() {
@@ -1822,18 +1831,39 @@ bool prune_enabled() {
 
 // rows: factor rows N of the model; int8_fused: the int8-residue engine would run this call's contraction with generator-written planes
 PrunePlan prune_plan(int64_t rows, int64_t M, int k, bool want_scores, int kind, double p0, int p_out, bool int8_fused, int d) {
-    PrunePlan pp{false, 0, 0, 0};
+    PrunePlan pp{false, 0, 0, 0, 0, 0};
     const int64_t tblocks = (rows + 255) / 256;
     // R = N/8, rounded to whole 256-row blocks: the bound pass then costs 1/64 of the contraction.  On the synthetic problem of the
     // benchmark R = N/8, N/4, N/2 left 4 %, 2 %, 1 % of the candidates: R = N/4 would halve a survivor pass that costs 0.04 of the
     // full one at four times a bound pass that costs 0.016 of it.
     int rb = (int)((rows / 8 + 128) / 256);
     if (rb < 1) rb = 1;
+    // Two levels: how many candidates a bound removes hardly depends on R — μ decides nearly all of it — while the
+    // pass's residue work grows with R (generator, reconstruction) and R² (GEMM).  So a first level of R₀ = N/32, rounded the same
+    // way, runs over all M and sets the threshold, and the N/8 pass above runs only on the S₁ candidates it leaves, at S₁/M of its
+    // cost: the survivor pass sees what it saw with one level.  (A narrow SINGLE level would not do: where N/8 leaves 4 % of the
+    // candidates, a narrower bound leaves more, and a 4 % survivor pass already costs twice what the narrower bound saves.)  Only where
+    // R₀ is fewer blocks than R — from N = 3072 on — and, under a forced R, only when the test hook asks for one.  Measured at C3:
+    // 312 survivors at N/32 against 172 at N/8, the call 24.1 → 17.8 ms (N/16: 207 survivors, 18.7 ms); N = 4096: 12.6 → 11.5 ms.
+    int rb0 = (int)((rows / 32 + 128) / 256);
+    if (rb0 < 1) rb0 = 1;
+    bool forced = false;
+    int pre = 0;
 #ifdef ABO_TEST_HOOKS
-    if (g_prune_force_rblocks.load() > 0) rb = g_prune_force_rblocks.load();
+    forced = g_prune_force_rblocks.load() > 0;
+    if (forced) rb = g_prune_force_rblocks.load();
+    pre = g_prune_pre_rblocks.load();
 #endif
+    if (pre > 0) rb0 = pre;              // (a forced first level that is not below rblocks: an error the callers report)
+    else if (pre < 0 || forced || rb0 >= rb) rb0 = 0;
     pp.rblocks = rb;
+    pp.rblocks0 = rb0;
     pp.k0 = k > 0 ? ((int64_t)4 * k > 1024 ? (int64_t)4 * k : 1024) : 0;
+    // below 4·K0 survivors the full pass on them costs less than the ≈ 16 launches of another bound pass
+    pp.level2_min = 4 * pp.k0;
+#ifdef ABO_TEST_HOOKS
+    if (g_prune_level2_min.load() >= 0) pp.level2_min = g_prune_level2_min.load();
+#endif
     // the survivor pass costs S/M of the full pass it replaces (plus a gather of S points): it is the cheaper of the two for any
     // S < M, and is taken while it saves at least an eighth of the pass — far more than the extra launches cost
     pp.max_survivors = M - M / 8;
@@ -1867,9 +1897,10 @@ int32_t prune_select(abo_gp* g, const double* Zd, int64_t M, const AcqTerms& t, 
     int64_t* count_d = reinterpret_cast<int64_t*>(g->pr_tv.as<double>() + K0);
     HIPCHK(g->events(EV_BASE));
     constexpr size_t PE = 10;          // events 10-13, by index: the passes below may grow (and move) the context's event list
-    // 1. bound pass: the chunk pipeline on the first row blocks of W
+    // 1. bound pass: the chunk pipeline on the first row blocks of W — those of the first level where the plan has one
+    const bool two_levels = pp.rblocks0 > 0;
     HIPCHK(hipEventRecord(g->evs()[PE], s));
-    int32_t rc = posterior(g, Zd, M, kind, p0, best_y, nullptr, nullptr, ub, 1, 0, nullptr, 0, pp.rblocks, false);
+    int32_t rc = posterior(g, Zd, M, kind, p0, best_y, nullptr, nullptr, ub, 1, 0, nullptr, 0, two_levels ? pp.rblocks0 : pp.rblocks, false);
     if (rc == PRUNE_UNAVAILABLE) return ABO_OK;
     if (rc) return rc;
     g->pst.bound_rows = g->passes.back().rows;
@@ -1896,6 +1927,31 @@ int32_t prune_select(abo_gp* g, const double* Zd, int64_t M, const AcqTerms& t, 
     int64_t S = 0;
     HIPCHK(hipMemcpyAsync(&S, count_d, sizeof(int64_t), hipMemcpyDeviceToHost, s));
     HIPCHK(wait_stream(s));
+    // 3b. second level: the bound pass at rblocks on the first level's survivors, against the SAME τ (the k-th best exact score of any
+    // subset is a valid threshold).  ub keeps min(level 1, level 2) — still an upper bound for every one of the M candidates — and is
+    // compacted again over all M (8 bytes a candidate: cheaper than a second index map), so the list stays in index order.
+    if (two_levels) {
+        g->plv.rows1 = g->pst.bound_rows;
+        g->plv.s1 = S;
+    }
+    if (two_levels && S > pp.level2_min) {
+        HIPCHK(hipEventRecord(g->evs()[14], s));
+        HIPCHK(g->pr_z.ensure(sizeof(double) * S * d));
+        HIPCHK(g->pr_ub2.ensure(sizeof(double) * S));
+        HIPCHK(launch_gather_points(Zd, g->pr_sel.as<int64_t>(), 0, (int)S, d, g->pr_z.as<double>(), s));
+        rc = posterior(g, g->pr_z.as<double>(), S, kind, p0, best_y, nullptr, nullptr, g->pr_ub2.as<double>(), 1, 0, nullptr, 0, pp.rblocks, true, true);
+        if (rc && rc != PRUNE_UNAVAILABLE) return rc;
+        if (!rc) {          // (no scratch for the engine at this size: the first level's list goes on as it is)
+            g->plv.rows2 = g->passes.back().rows;
+            HIPCHK(launch_prune_min_scatter(ub, g->pr_sel.as<int64_t>(), g->pr_ub2.as<double>(), S, s));
+            HIPCHK(launch_prune_compact(ub, M, tau, kind == ABO_ACQ_LOGEI ? PRUNE_ABS_LOGEI : PRUNE_ABS, g->pr_blk.as<int>(),
+                                        g->pr_sel.as<int64_t>(), count_d, s));
+            HIPCHK(hipEventRecord(g->evs()[15], s));
+            HIPCHK(hipMemcpyAsync(&S, count_d, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+            HIPCHK(wait_stream(s));
+            g->plv.s2 = S;
+        }
+    }
     g->pst.survivors = S;
     if (S < k || S > pp.max_survivors) { g->pst.fallback = 1; return ABO_OK; }
     HIPCHK(g->pr_z.ensure(sizeof(double) * S * d));
@@ -1926,13 +1982,16 @@ int32_t acq_terms_impl(abo_gp* g, const double* Z, int64_t M, int32_t d, int32_t
     const bool with_var = !(terms_plain(t) && t.kind[0] == ABO_ACQ_MEAN);
     const bool fused_timings = !terms_have_gradnorm(t);           // the slab path does not keep per-chunk events
     g->pst = abo_prune_stats{};
-    PrunePlan pp{false, 0, 0, 0};
+    g->plv = abo_gp::PruneLevels{};
+    PrunePlan pp{false, 0, 0, 0, 0, 0};
     if (M > 0 && terms_plain(t)) {
         int nm = 0;
         KgenArgs probe{};
         probe.pt = g->p_out; probe.dp = g->dp;
         const bool int8_fused = wants_int8(g, true, 1, &nm) && kgen_writes_residues(probe, nm);
         pp = prune_plan(g->N, M, k, scores != nullptr, t.kind[0], t.p0[0], g->p_out, int8_fused, g->d);
+        if (pp.eligible && pp.rblocks0 >= pp.rblocks)          // (abo_test_prune_levels alone can ask for this)
+            return fail(ABO_EINVAL, "abo_acq: a first bound level of %d row blocks is not below the bound pass's %d", pp.rblocks0, pp.rblocks);
     }
     TopkWork w{};
     double* tv = top_val;
@@ -1990,10 +2049,13 @@ int32_t acq_terms_impl(abo_gp* g, const double* Z, int64_t M, int32_t d, int32_t
     g->tm.acq_topk_ms = phase_events() ? ev_ms(g->evs()[6], g->evs()[7]) : 0.0;
     g->tm.acq_total_ms = ev_ms(g->evs()[5], g->evs()[7]);
     if (g->pst.bound_rows > 0) {
-        hipEvent_t* pe = &g->evs()[10];
-        g->pst.bound_ms = ev_ms(pe[0], pe[1]);
+        hipEvent_t* pe = &g->evs()[10];          // 10 … 15: start, end of the (first) bound pass, end of the threshold pass and compaction,
+        const bool l2 = g->plv.rows2 > 0;        // end of the survivor pass, start and end of the second bound level
+        if (g->plv.rows1 > 0) g->plv.ms1 = ev_ms(pe[0], pe[1]);
+        if (l2) g->plv.ms2 = ev_ms(pe[4], pe[5]);
+        g->pst.bound_ms = ev_ms(pe[0], pe[1]) + g->plv.ms2;
         g->pst.threshold_ms = ev_ms(pe[1], pe[2]);
-        g->pst.survivor_ms = g->pst.pruned ? ev_ms(pe[2], pe[3]) : 0.0;
+        g->pst.survivor_ms = g->pst.pruned ? ev_ms(pe[l2 ? 5 : 2], pe[3]) : 0.0;
     }
     return ABO_OK;
 }
@@ -2148,6 +2210,13 @@ int32_t abo_get_n(abo_gp* g, int64_t* N, int32_t* d) {
 int32_t abo_get_prune_stats(abo_gp* g, abo_prune_stats* out) {
     if (!g || !out) return fail(ABO_EINVAL, "abo_get_prune_stats: null argument");
     *out = g->pst;
+    return ABO_OK;
+}
+
+int32_t abo_get_prune_levels(abo_gp* g, int64_t* out) {
+    if (!g || !out) return fail(ABO_EINVAL, "abo_get_prune_levels: null argument");
+    out[0] = g->plv.rows1; out[1] = g->plv.s1; out[2] = g->plv.rows2; out[3] = g->plv.s2;
+    out[4] = (int64_t)llround(g->plv.ms1 * 1e3); out[5] = (int64_t)llround(g->plv.ms2 * 1e3);      // whole microseconds
     return ABO_OK;
 }
 
@@ -3935,6 +4004,22 @@ int32_t abo_test_prune_force(int32_t rblocks, int32_t mode) {
     if (rblocks < 0 || mode < 0 || mode > 2) return fail(ABO_EINVAL, "abo_test_prune_force: rblocks = %d, mode = %d", rblocks, mode);
     g_prune_force_rblocks.store(rblocks);
     g_prune_force_mode.store(mode);
+    return ABO_OK;
+}
+
+int32_t abo_test_prune_levels(int32_t pre_rblocks, int64_t level2_min) {
+    if (pre_rblocks < -1 || level2_min < -1) return fail(ABO_EINVAL, "abo_test_prune_levels: pre_rblocks = %d, level2_min = %lld", pre_rblocks, (long long)level2_min);
+    g_prune_pre_rblocks.store(pre_rblocks);
+    g_prune_level2_min.store(level2_min);
+    return ABO_OK;
+}
+
+int32_t abo_test_prune_plan_levels(int64_t rows, int64_t M, int32_t k, int32_t want_scores, int32_t kind, double p0, int32_t p_out,
+                                   int32_t int8_fused, int32_t d, int64_t* out) {
+    if (!out) return fail(ABO_EINVAL, "abo_test_prune_plan_levels: null argument");
+    const PrunePlan pp = prune_plan(rows, M, k, want_scores != 0, kind, p0, p_out, int8_fused != 0, d);
+    if (pp.rblocks0 >= pp.rblocks) return fail(ABO_EINVAL, "abo_test_prune_plan_levels: a first bound level of %d row blocks is not below the bound pass's %d", pp.rblocks0, pp.rblocks);
+    out[0] = pp.eligible; out[1] = pp.rblocks; out[2] = pp.k0; out[3] = pp.max_survivors; out[4] = pp.rblocks0;
     return ABO_OK;
 }
 

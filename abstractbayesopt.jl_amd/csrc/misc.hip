@@ -841,6 +841,21 @@ hipError_t launch_prune_compact(const double* ub, int64_t M, const double* tau, 
     return hipGetLastError();
 }
 
+// both operands are guarded upper bounds of the same candidate's score, so their minimum is one; NaN (a candidate every level keeps) wins
+__global__ void prune_min_scatter_kernel(double* __restrict__ ub, const int64_t* __restrict__ sel, const double* __restrict__ ub2, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t j = sel[i];
+    const double a = ub[j], b = ub2[i];
+    ub[j] = (a != a || b != b) ? __builtin_nan("") : (b < a ? b : a);
+}
+
+hipError_t launch_prune_min_scatter(double* ub, const int64_t* sel, const double* ub2, int64_t n, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(prune_min_scatter_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ub, sel, ub2, n);
+    return hipGetLastError();
+}
+
 __global__ void prune_map_kernel(int64_t* top_idx, int k, const int64_t* sel, int64_t idx_base) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e < k && top_idx[e] >= 0) top_idx[e] = sel[top_idx[e]] + idx_base;

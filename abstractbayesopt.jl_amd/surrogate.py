@@ -139,6 +139,14 @@ class HipStandardGP(AbstractSurrogate):
         _lib.check(_lib.lib().abo_get_prune_stats(self._require(), C.byref(t)))
         return t.as_dict()
 
+    def prune_levels(self) -> dict:
+        """the bound levels of the same call (include/abo_hip.h: abo_get_prune_levels): rows and survivors of the first level over all
+        candidates and of the second over its survivors — rows 0: that level did not run —, and the ms each took"""
+        o = (C.c_int64 * 6)()
+        _lib.check(_lib.lib().abo_get_prune_levels(self._require(), o))
+        return {"level1_rows": o[0], "level1_survivors": o[1], "level2_rows": o[2], "level2_survivors": o[3],
+                "level1_ms": o[4] * 1e-3, "level2_ms": o[5] * 1e-3}
+
     # Checkpoint / resume: the reference has no serialisation code, a BOStruct is rebuilt from (xs, ys, hyper-
     # parameters) (bayesian_opt.jl:81).  A pickled model is exactly that — hyper-parameters plus the training data
     # read back from the device — and unpickling refits on the current device.

@@ -48,7 +48,7 @@ extern "C" {
                                   abo_paths_attach, abo_paths_detach, abo_paths_top, abo_paths_values, abo_paths_append_stats_get
                                   (struct abo_paths_append_stats is new); ABO_ACQ_LOGEI (kind 5 in every entry point that takes a kind
                                   or an abo_acq_term, and in the pruned top-k selection); ABO_ACQ_MES and abo_score_mes, abo_acq_mes,
-                                  abo_cand_acq_mes, abo_refine_mes, abo_optimize_acquisition_mes */
+                                  abo_cand_acq_mes, abo_refine_mes, abo_optimize_acquisition_mes; abo_get_prune_levels */
 
 /* status codes */
 enum {
@@ -170,14 +170,17 @@ typedef struct abo_timings {
  * least 4·K₀ candidates, does not compute σ² of every candidate: a bound pass over the first bound_rows rows of L⁻¹ gives σ²_R ≥ σ²
  * and so an upper bound of every score; the exact scores of the K₀ = max(4k, 1024) best-by-bound candidates set a threshold; only the
  * candidates whose bound reaches it (the survivors) go through the full contraction.  The k pairs returned are bit for bit those of
- * the full evaluation.  ABO_ACQ_PRUNE=0 in the environment turns the path off.  All zeros: the call was not eligible. */
+ * the full evaluation.  ABO_ACQ_PRUNE=0 in the environment turns the path off.  All zeros: the call was not eligible.
+ * From 3072 factor rows on the bound has two levels (abo_get_prune_levels): a first pass over N/32 rows on all candidates sets the
+ * threshold, and the pass over N/8 rows runs on its survivors only, when more than 4·K₀ of them are left. */
 typedef struct abo_prune_stats {
     int64_t pruned;        /* 1: the k pairs came from the survivor pass */
-    int64_t fallback;      /* 1: more than 7/8 of the candidates survived — the ordinary full pass ran behind the two passes below */
-    int64_t bound_rows;    /* rows of L⁻¹ the bound pass contracted (0: no bound pass ran) */
+    int64_t fallback;      /* 1: more than 7/8 of the candidates survived — the ordinary full pass ran behind the passes below */
+    int64_t bound_rows;    /* rows of L⁻¹ the bound pass over ALL candidates contracted (0: no bound pass ran) */
     int64_t k0;            /* candidates evaluated exactly for the threshold */
-    int64_t survivors;     /* candidates whose bound reached the threshold (the k0 that set it are re-evaluated among them) */
-    double bound_ms, threshold_ms, survivor_ms;      /* HIP events on the handle's stream around the three passes */
+    int64_t survivors;     /* candidates whose bound (of the last level that ran) reached the threshold: what went through the full
+                              contraction, or would have without the fallback (the k0 that set the threshold are re-evaluated among them) */
+    double bound_ms, threshold_ms, survivor_ms;      /* HIP events on the handle's stream around the passes (bound_ms: every bound pass) */
 } abo_prune_stats;
 
 /* --- lifetime -------------------------------------------------------------------------------
@@ -646,6 +649,12 @@ int32_t abo_get_n(abo_gp* gp, int64_t* N, int32_t* d);
 int32_t abo_get_data(abo_gp* gp, double* X, double* y);
 int32_t abo_get_timings(abo_gp* gp, abo_timings* out);
 int32_t abo_get_prune_stats(abo_gp* gp, abo_prune_stats* out);
+/* added within ABI 7: the bound levels of the same call.  out[6] = {rows of level 1 (0: the call had no first level — then all six are
+ * 0 and abo_prune_stats describes its one bound pass), S₁ = candidates whose level-1 bound reached the threshold, rows of level 2
+ * (0: skipped, S₁ ≤ 4·K₀ went straight to the full contraction), S₂ = of those S₁ the ones whose level-2 bound reached it too (0 when
+ * skipped), time of level 1, time of level 2} — the two times in whole MICROSECONDS (HIP events on the handle's stream; level 2's
+ * includes gathering its points and compacting again). */
+int32_t abo_get_prune_levels(abo_gp* gp, int64_t* out);
 
 /* --- multi-device handles (BASELINE configs 4 and 5: candidates sharded over the GPUs of one node) -----------------
  * One host process drives all devices: the Julia host has no process launcher, so the sharding of
@@ -768,14 +777,25 @@ int32_t abo_test_prune_plan(int64_t rows, int64_t M, int32_t k, int32_t want_sco
  * mode 1 = a threshold of −Inf (every candidate survives: the selection's worst case on any data), mode 2 = the path is off, as under
  * ABO_ACQ_PRUNE=0.  (0, 0) restores the defaults. */
 int32_t abo_test_prune_force(int32_t rblocks, int32_t mode);
+/* The same for the first bound level: pre_rblocks −1 = no first level (the call has one bound pass, over the rule's or the forced
+ * row blocks), 0 = the rule (N/32 where that is fewer blocks than the bound pass's and abo_test_prune_force forces none), > 0 = that
+ * many row blocks — an abo_acq whose bound pass has no more row blocks than that then fails with ABO_EINVAL.  level2_min −1 = the rule
+ * (level 2 runs on more than 4·K₀ survivors of level 1), ≥ 0 = on more than level2_min of them (0: always).  (0, −1) restores the defaults. */
+int32_t abo_test_prune_levels(int32_t pre_rblocks, int64_t level2_min);
+/* abo_test_prune_plan with out[5]: the same four values, then the 256-row blocks of the first level (0: none).  ABO_EINVAL for a forced
+ * first level that is not below the bound pass's row blocks.  No GPU needed. */
+int32_t abo_test_prune_plan_levels(int64_t rows, int64_t M, int32_t k, int32_t want_scores, int32_t kind, double p0, int32_t p_out,
+                                   int32_t int8_fused, int32_t d, int64_t* out);
 /* Moduli of the bound pass's residue plan, process-wide: 8, 9, 10 = a short plan with the guard of csrc/ozaki.hip ("the guarded
  * bound"), 14 = the handle's plan, exact; 0 restores ABO_PRUNE_BOUND_MODULI / the default (8). */
 int32_t abo_test_prune_bound_moduli(int32_t n);
 /* sexp_b[0..n_rows), delta[0..n_rows) (host) = the row scales s_i and the guards delta[i] of the short plan the last abo_acq on this
- * handle ran its bound pass on (n_rows ≤ 256 × its row blocks); an error when that pass ran on the handle's own plan */
+ * handle ran its LAST bound pass on (n_rows ≤ 256 × its row blocks; with two levels: the second when it ran); an error when that pass
+ * ran on the handle's own plan */
 int32_t abo_test_prune_bound_plan(abo_gp* gp, int32_t* sexp_b, double* delta, int64_t n_rows);
 /* out[0..M) (host) = the upper bounds the last abo_acq on this handle stored in its bound pass: the score at (μ̃ − ε, σ²_R) plus the
- * margins of prune_keep (csrc/misc.hip), so that each is ≥ the full pass's computed score of the candidate */
+ * margins of prune_keep (csrc/misc.hip), so that each is ≥ the full pass's computed score of the candidate.  With two levels: the
+ * first level's bound, lowered to the second level's where that pass looked at the candidate */
 int32_t abo_test_prune_bounds(abo_gp* gp, double* out, int64_t M);
 /* mu[0..M), eps[0..M) (host) = the mean μ̃ the last abo_acq on this handle computed in its bound pass (first row blocks' columns by the
  * full generator, the others by the shortened sequences of csrc/kgen_tail.hip) and the distance ε it proved to the full pass's mean:
