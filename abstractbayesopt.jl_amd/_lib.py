@@ -13,7 +13,7 @@ ABO_OK, ABO_ENOTPD, ABO_EDIM, ABO_EINVAL, ABO_EHIP, ABO_ENOMEM = range(6)
 HOST, DEVICE = 0, 1
 
 EXPORTS = ["abo_create", "abo_set_contraction", "abo_create_grad", "abo_predict_grad", "abo_predict_grad_cov", "abo_retain", "abo_destroy", "abo_fit", "abo_append", "abo_append_grad", "abo_cand_create", "abo_cand_destroy",
-           "abo_cand_refresh", "abo_cand_downdate", "abo_cand_save", "abo_cand_restore", "abo_cand_acq", "abo_cand_get", "abo_cand_point", "abo_cand_exclude", "abo_predict", "abo_acq", "abo_nlml", "abo_nlml_grad", "abo_lhs", "abo_score",
+           "abo_cand_refresh", "abo_cand_downdate", "abo_cand_save", "abo_cand_restore", "abo_cand_acq", "abo_cand_get", "abo_cand_point", "abo_cand_exclude", "abo_predict", "abo_acq", "abo_nlml", "abo_nlml_grad", "abo_nlml_grad_ard", "abo_lhs", "abo_score",
            "abo_get_factor", "abo_get_n", "abo_get_data", "abo_get_timings", "abo_get_prune_stats", "abo_get_prune_levels", "abo_last_error", "abo_abi_version", "abo_pool_trim",
            "abo_mgpu_create", "abo_mgpu_clone", "abo_mgpu_destroy", "abo_mgpu_info", "abo_mgpu_get", "abo_mgpu_fit",
            "abo_mgpu_predict", "abo_mgpu_acq", "abo_mgpu_acq_lhs", "abo_mgpu_append", "abo_mgpu_cand_create",
@@ -169,6 +169,7 @@ def lib():
     L.abo_acq.argtypes = [vp, vp, i64, i32, i32, i32, f64, f64, i64, vp, i32, vp, vp, i32]
     L.abo_nlml.argtypes = [vp, C.POINTER(f64)]
     L.abo_nlml_grad.argtypes = [vp, C.POINTER(f64), C.POINTER(f64), C.POINTER(f64)]
+    L.abo_nlml_grad_ard.argtypes = [vp, i32, C.POINTER(f64), C.POINTER(f64), C.POINTER(f64), C.POINTER(f64)]
     L.abo_lhs.argtypes = [i32, i64, i32, vp, vp, C.c_uint64, i64, i64, vp]
     L.abo_score.argtypes = [i32, vp, vp, i64, i32, f64, f64, vp]
     L.abo_fill_distance.argtypes = [i32, vp, i64, i32, i32, vp, i64, i32, C.POINTER(f64)]

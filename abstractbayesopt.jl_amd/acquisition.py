@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import DEVICE, HOST
-from .surrogate import AbstractSurrogate, HipStandardGP, _get_minimum, as_points
+from .surrogate import AbstractSurrogate, HipStandardGP, _get_minimum, as_points, from_model_space, to_model_space
 
 ACQ_EI, ACQ_UCB, ACQ_PI, ACQ_MEAN, ACQ_GRADNORM_UCB, ACQ_LOGEI, ACQ_MES = 0, 1, 2, 3, 4, 5, 6
 MAX_TERMS = 8
@@ -211,7 +211,7 @@ def evaluate(acq: AbstractAcquisition, surrogate: HipStandardGP, x, k: int = 0, 
             raise TypeError("this objective is not served by the fused acquisition call on this surrogate")
         return evaluate_terms(terms, surrogate, x, k=k, idx_base=idx_base, return_scores=return_scores)
     L = _lib.lib()
-    zp, m, d, zspace, keep = as_points(x)
+    zp, m, d, zspace, keep = as_points(to_model_space(surrogate, x))
     if hasattr(surrogate, "devices") and zspace == HOST and idx_base == 0 and not isinstance(acq, MaxValueEntropySearch):
         from . import multigpu                                               # HipShardedGP: sharded inside the library
         return multigpu.evaluate(acq, surrogate, keep, k=k, return_scores=return_scores)
@@ -251,6 +251,7 @@ def update_and_evaluate(acq: AbstractAcquisition, model: HipStandardGP, xs, ys, 
         new = _update(model, xs, ys)
         return (new,) + tuple(evaluate(update(acq, ys, new), new, x, k=k, return_scores=return_scores, idx_base=idx_base))
     L = _lib.lib()
+    xs, x = to_model_space(model, xs), to_model_space(model, x)
     xp, n, d, xspace, xkeep = as_points(xs)
     if _is_torch(ys):
         yt = ys.reshape(-1).contiguous()
@@ -363,7 +364,7 @@ def _term_array(terms):
 def evaluate_terms(terms, surrogate, x, k: int = 0, idx_base: int = 0, return_scores: bool = True):
     """`evaluate` for a weighted-sum objective (abo_acq_terms): scores and the stable reverse sort's first k in one call"""
     L = _lib.lib()
-    zp, m, d, zspace, keep = as_points(x)
+    zp, m, d, zspace, keep = as_points(to_model_space(surrogate, x))
     if zspace == DEVICE:
         import torch
         dev = keep.device
@@ -395,6 +396,13 @@ def _refine_opts(max_iter, g_tol, f_abstol, x_abstol, history):
                               f_abstol=float(f_abstol), x_abstol=float(x_abstol))
 
 
+def _back_into_box(surrogate, x, lower, upper):
+    """points the library returned in model space → the caller's coordinates; (x/ℓ)·ℓ can leave the box by an ulp at a bound, so an ARD
+    model's points are clipped back into it.  Any other model's points are returned as they came."""
+    y = from_model_space(surrogate, x, bounds=True)
+    return x if y is x else np.clip(y, np.asarray(lower, dtype=np.float64), np.asarray(upper, dtype=np.float64))
+
+
 def refine_starts(acqf: AbstractAcquisition, surrogate: HipStandardGP, starts, lower, upper, max_iter: int = 100,
                   g_tol: float = 1e-5, f_abstol: float = 2.2e-9, x_abstol: float = 1e-4, history: int = 10, return_iters: bool = False):
     """Local refinement stage of optimize_acquisition (acq_utils.jl:55-71): one box-constrained L-BFGS run per start in the
@@ -408,9 +416,12 @@ def refine_starts(acqf: AbstractAcquisition, surrogate: HipStandardGP, starts, l
     terms = None if mes else flatten_terms(acqf, surrogate)
     if terms is None and not mes:          # more than 8 members / a member the library does not know: the host loop
         return _refine_starts_fd(acqf, surrogate, starts, lower, upper, max_iter, g_tol, f_abstol, x_abstol, history)
-    lower = np.ascontiguousarray(np.asarray(lower, dtype=np.float64))
-    upper = np.ascontiguousarray(np.asarray(upper, dtype=np.float64))
-    st = np.ascontiguousarray(np.asarray(starts, dtype=np.float64))
+    # (an ARD model: box and starts go in divided by ℓ_c, the refined points come back multiplied; x_abstol is then a step in the
+    # scaled coordinates)
+    lower_box, upper_box = lower, upper
+    lower = np.ascontiguousarray(to_model_space(surrogate, np.asarray(lower, dtype=np.float64), bounds=True))
+    upper = np.ascontiguousarray(to_model_space(surrogate, np.asarray(upper, dtype=np.float64), bounds=True))
+    st = np.ascontiguousarray(to_model_space(surrogate, np.asarray(starts, dtype=np.float64), bounds=True))
     S, d = st.shape
     x, f, it = np.empty((S, d)), np.empty(S), np.zeros((S, 2), dtype=np.int32)
     opts = _refine_opts(max_iter, g_tol, f_abstol, x_abstol, history)
@@ -418,33 +429,36 @@ def refine_starts(acqf: AbstractAcquisition, surrogate: HipStandardGP, starts, l
         yp, ns = acqf._samples()
         _lib.check(_lib.lib().abo_refine_mes(_mes_handle(surrogate, "refine_starts"), yp, ns, lower.ctypes.data, upper.ctypes.data, d,
                                              st.ctypes.data, S, C.byref(opts), x.ctypes.data, f.ctypes.data, it.ctypes.data))
+        x = _back_into_box(surrogate, x, lower_box, upper_box)
         return (x, f, it) if return_iters else (x, f)
     h = surrogate.shard(0) if hasattr(surrogate, "devices") else surrogate._require()
     arr = _term_array(terms)
     _lib.check(_lib.lib().abo_refine_terms(h, arr, len(terms), lower.ctypes.data, upper.ctypes.data, d,
                                            st.ctypes.data, S, C.byref(opts), x.ctypes.data, f.ctypes.data, it.ctypes.data))
+    x = _back_into_box(surrogate, x, lower_box, upper_box)
     return (x, f, it) if return_iters else (x, f)
 
 
 def acquisition_value_and_grad(acqf: AbstractAcquisition, surrogate: HipStandardGP, x):
     """(f (M,), ∇f (M, d)) of EI / UCB / PI at the points x: the evaluation the on-device refinement is built on
     (abo_test_acq_grad) — analytic ∇μ, ∇σ² and the closed-form partials of the acquisition function."""
-    z = np.ascontiguousarray(np.asarray(x, dtype=np.float64))
+    z = np.asarray(x, dtype=np.float64)
     if z.ndim == 1:
         z = z[:, None]
+    z = np.ascontiguousarray(to_model_space(surrogate, z))
     f, g = np.empty(z.shape[0]), np.empty(z.shape)
     if isinstance(acqf, MaxValueEntropySearch):
         yp, ns = acqf._samples()
         _lib.check(_lib.lib().abo_test_acq_grad_mes(_mes_handle(surrogate, "acquisition_value_and_grad"), yp, ns, z.ctypes.data,
                                                     z.shape[0], z.shape[1], f.ctypes.data, g.ctypes.data))
-        return f, g
+        return f, to_model_space(surrogate, g)             # ∂/∂x_c = (∂/∂(x_c/ℓ_c))/ℓ_c
     terms = flatten_terms(acqf, surrogate)
     if terms is None:
         raise ValueError("the objective does not flatten into at most 8 library terms")
     arr = _term_array(terms)
     _lib.check(_lib.lib().abo_test_acq_grad_terms(surrogate._require(), arr, len(terms), z.ctypes.data, z.shape[0], z.shape[1],
                                                   f.ctypes.data, g.ctypes.data))
-    return f, g
+    return f, to_model_space(surrogate, g)                 # ∂/∂x_c = (∂/∂(x_c/ℓ_c))/ℓ_c
 
 
 def optimize_acquisition_device(acqf: AbstractAcquisition, surrogate: HipStandardGP, domain, n_grid: int = 10_000,
@@ -453,8 +467,10 @@ def optimize_acquisition_device(acqf: AbstractAcquisition, surrogate: HipStandar
     reduced to the n_local best, every start refined on the device, the best point returned.  Serves EI / UCB / PI, GradientNormUCB
     and EnsembleAcquisitions of them (abo_acq_term) on a HipStandardGP, a HipGradientGP (abo_optimize_acquisition_terms) and their
     sharded groups (abo_mgpu_optimize_acquisition_terms: grid and starts sharded over the group)."""
-    lower = np.ascontiguousarray(np.asarray(domain.lower, dtype=np.float64))
-    upper = np.ascontiguousarray(np.asarray(domain.upper, dtype=np.float64))
+    # an ARD model: the box goes in divided by ℓ_c (the Latin hypercube of the scaled box is the scaled design), every point comes back
+    # multiplied by ℓ_c
+    lower = np.ascontiguousarray(to_model_space(surrogate, np.asarray(domain.lower, dtype=np.float64), bounds=True))
+    upper = np.ascontiguousarray(to_model_space(surrogate, np.asarray(domain.upper, dtype=np.float64), bounds=True))
     d, k = lower.shape[0], min(int(n_local), int(n_grid))
     best, val = np.empty(d), C.c_double()
     sx, sv, rx, rv = np.empty((k, d)), np.empty(k), np.empty((k, d)), np.empty(k)
@@ -466,6 +482,7 @@ def optimize_acquisition_device(acqf: AbstractAcquisition, surrogate: HipStandar
                                                   upper.ctypes.data, d, int(n_grid), int(n_local), int(seed) & (2 ** 64 - 1), C.byref(o),
                                                   best.ctypes.data, C.byref(val), sx.ctypes.data, sv.ctypes.data, rx.ctypes.data,
                                                   rv.ctypes.data))
+        best, sx, rx = (_back_into_box(surrogate, a, domain.lower, domain.upper) for a in (best, sx, rx))
         return (best, val.value, sx, sv, rx, rv) if return_all else best
     terms = flatten_terms(acqf, surrogate)
     if terms is None:
@@ -478,6 +495,7 @@ def optimize_acquisition_device(acqf: AbstractAcquisition, surrogate: HipStandar
     _lib.check(fn(h, arr, len(terms), lower.ctypes.data, upper.ctypes.data, d, int(n_grid), int(n_local),
                   int(seed) & (2 ** 64 - 1), C.byref(o), best.ctypes.data, C.byref(val), sx.ctypes.data, sv.ctypes.data,
                   rx.ctypes.data, rv.ctypes.data))
+    best, sx, rx = (_back_into_box(surrogate, a, domain.lower, domain.upper) for a in (best, sx, rx))
     if return_all:
         return best, val.value, sx, sv, rx, rv
     return best

@@ -199,6 +199,9 @@ struct NlmlGradArgs {
     double sigma_f2;
 };
 hipError_t launch_nlml_grad(const NlmlGradArgs& a, hipStream_t s);
+// one length scale per coordinate (dp ≤ 32), the same sweep: a.partial is [Np/16][dp] here and
+// out_ard[c] = Σ_ij (Kinv − ααᵀ)_ij ∂K_ij/∂log ℓ_c for c < dp (exactly 0 for the padded c ≥ d); a.out[1..3] as above, a.out[0] = 0
+hipError_t launch_nlml_grad_ard(const NlmlGradArgs& a, double* out_ard, hipStream_t s);
 // same reductions with dK/dlog(ell) given as a matrix D (gradient-enhanced GP: D comes from kgen with dlogell = 1):
 // out[0] = sum_{i,k<N} (Kinv[i][k] - alpha_i alpha_k) D[i][k]  (lower 128-tiles, strictly-lower ones counted twice), out[1..3] as above
 hipError_t launch_nlml_grad_matrix(const NlmlGradArgs& a, const double* D, int64_t ldd, hipStream_t s);

@@ -2139,17 +2139,16 @@ int32_t abo_nlml(abo_gp* g, double* out) {
     return ABO_OK;
 }
 
-int32_t abo_nlml_grad(abo_gp* g, double* nlml, double* d_log_ell, double* d_log_sigma_f2) {
-    if (!g) return fail(ABO_EINVAL, "abo_nlml_grad: null handle");
-    if (!g->fitted) return fail(ABO_EINVAL, "surrogate is not conditioned on data yet (call abo_fit first)");
-    if (g->from_append || g->st->max_live() != g->N)
-        return fail(ABO_EINVAL, "abo_nlml_grad needs a freshly fitted model (hyper-parameter search refits anyway)");
+// abo_nlml_grad and abo_nlml_grad_ard behind their argument checks: K⁻¹ = WᵀW, the trace sweep (one ∂/∂log ℓ, or ard = one per
+// coordinate into d_log_ell[0 … d)), the scalars both derive from the finish step's sums
+static int32_t nlml_grad_impl(abo_gp* g, bool ard, double* nlml, double* d_log_ell, double* d_log_sigma_f2, double* d_log_noise) {
     HIPCHK(hipSetDevice(g->prm.device));
     hipStream_t s = g->stream;
     const int64_t Np = g->Np, ld = g->st->cap;
     const int N = (int)g->N;
     HIPCHK(g->T.ensure(sizeof(double) * Np * Np));
-    HIPCHK(g->partial.ensure(sizeof(double) * (Np / 16 + 8)));
+    const int64_t npart = ard ? Np / 16 * g->dp : Np / 16;       // ard: partial[block][c], the dp reduced traces behind them
+    HIPCHK(g->partial.ensure(sizeof(double) * (npart + (ard ? g->dp : 0) + 8)));
     HIPCHK(g->scal.ensure(sizeof(double) * 8));
     // K⁻¹ = WᵀW on the lower 128-tiles: Kinv[i][j] = Σ_{k ≥ i} WT[i][k]·WT[j][k]
     GemmArgs a{};
@@ -2165,7 +2164,9 @@ int32_t abo_nlml_grad(abo_gp* g, double* nlml, double* d_log_ell, double* d_log_
     ga.Xs = g->st->Xs.as<double>(); ga.Kinv = g->T.as<double>(); ga.alpha = g->alpha.as<double>();
     ga.delta = g->st->delta.as<double>(); ga.partial = g->partial.as<double>(); ga.out = g->scal.as<double>() + 4;
     ga.ld = Np; ga.N = N; ga.Np = (int)Np; ga.dp = g->dp; ga.family = g->prm.family; ga.sigma_f2 = g->prm.sigma_f2;
-    if (g->p_out > 1) {
+    if (ard) {
+        HIPCHK(launch_nlml_grad_ard(ga, g->partial.as<double>() + npart, s));
+    } else if (g->p_out > 1) {
         // gradient-enhanced GP: dK/dlog(ell) of the multi-output system as a matrix (same generator as K_XX with the
         // derivative triple), then the weighted sum against K^-1 - alpha alpha^T
         HIPCHK(g->Kxz.ensure(sizeof(double) * Np * Np));
@@ -2180,17 +2181,41 @@ int32_t abo_nlml_grad(abo_gp* g, double* nlml, double* d_log_ell, double* d_log_
         HIPCHK(launch_nlml_grad(ga, s));
     }
     HIPCHK(hipEventRecord(ev[2], s));
-    double o[4];
+    double o[4], oc[32];
     HIPCHK(hipMemcpyAsync(o, g->scal.as<double>() + 4, sizeof o, hipMemcpyDeviceToHost, s));
+    if (ard) HIPCHK(hipMemcpyAsync(oc, g->partial.as<double>() + npart, sizeof(double) * g->d, hipMemcpyDeviceToHost, s));
     HIPCHK(wait_stream(s));
     g->tm.nlml_kinv_ms = ev_ms(ev[0], ev[1]);
     g->tm.nlml_trace_ms = ev_ms(ev[1], ev[2]);
     // ∂NLML/∂θ = ½ tr((K⁻¹ − ααᵀ) ∂K/∂θ);  ∂K/∂log σ_f² = K − noise·I  and  K α = δ
     const double noise = g->st->noise_used;
     if (nlml) *nlml = 0.5 * ((double)g->N * std::log(2.0 * M_PI) + g->logdet + g->quad);
-    if (d_log_ell) *d_log_ell = 0.5 * o[0];
+    if (d_log_ell) {
+        if (ard) for (int c = 0; c < g->d; ++c) d_log_ell[c] = 0.5 * oc[c];
+        else *d_log_ell = 0.5 * o[0];
+    }
     if (d_log_sigma_f2) *d_log_sigma_f2 = 0.5 * ((double)N - noise * o[1] - o[3] + noise * o[2]);
+    if (d_log_noise) *d_log_noise = 0.5 * noise * (o[1] - o[2]);      // ∂K/∂log σ² = σ²·I
     return ABO_OK;
+}
+
+int32_t abo_nlml_grad(abo_gp* g, double* nlml, double* d_log_ell, double* d_log_sigma_f2) {
+    if (!g) return fail(ABO_EINVAL, "abo_nlml_grad: null handle");
+    if (!g->fitted) return fail(ABO_EINVAL, "surrogate is not conditioned on data yet (call abo_fit first)");
+    if (g->from_append || g->st->max_live() != g->N)
+        return fail(ABO_EINVAL, "abo_nlml_grad needs a freshly fitted model (hyper-parameter search refits anyway)");
+    return nlml_grad_impl(g, false, nlml, d_log_ell, d_log_sigma_f2, nullptr);
+}
+
+int32_t abo_nlml_grad_ard(abo_gp* g, int32_t d, double* nlml, double* d_log_ell, double* d_log_sigma_f2, double* d_log_noise) {
+    if (!g) return fail(ABO_EINVAL, "abo_nlml_grad_ard: null handle");
+    if (!g->fitted) return fail(ABO_EINVAL, "surrogate is not conditioned on data yet (call abo_fit first)");
+    if (d < 1 || d > 32) return fail(ABO_EINVAL, "abo_nlml_grad_ard: input dimension %d outside 1..32", d);
+    if (g->p_out > 1) return fail(ABO_EINVAL, "abo_nlml_grad_ard: gradient-enhanced models have no per-coordinate length scales");
+    if (d != g->d) return fail(ABO_EDIM, "DimensionMismatch: abo_nlml_grad_ard with d = %d, model dimension %d", d, g->d);
+    if (g->from_append || g->st->max_live() != g->N)
+        return fail(ABO_EINVAL, "abo_nlml_grad_ard needs a freshly fitted model (hyper-parameter search refits anyway)");
+    return nlml_grad_impl(g, true, nlml, d_log_ell, d_log_sigma_f2, d_log_noise);
 }
 
 // host vector of a gradient-enhanced model: the library's point-major order v[i·p + q] → the ABI's by-outputs order v[q·N + i]

@@ -252,6 +252,143 @@ hipError_t launch_nlml_grad_matrix(const NlmlGradArgs& a, const double* D, int64
     return hipGetLastError();
 }
 
+// ARD (one length scale per coordinate, all equal to the handle's at the point of evaluation): with e_c the scaled difference in
+// coordinate c and d2 = Σ_c e_c², ∂k/∂log ℓ_c = σ_f²·q(d2)·e_c², q = dkappa_dlogell(d2)/d2 in closed form — no division, finite at 0:
+//   SE   e^{−d2/2}      M32  3 e^{−√3 d}      M52  (5/3)(1+√5 d) e^{−√5 d}      M72  (7/5 + (7√7/5) d + (49/15) d2) e^{−√7 d}
+template <int FAM>
+__device__ __forceinline__ double dkappa_dlogell_over_d2(double d2) {
+    if constexpr (FAM == ABO_KERNEL_SE) {
+        return exp_nonpos(-0.5 * d2);
+    } else if constexpr (FAM == ABO_KERNEL_MATERN52) {
+        const double s5 = 2.23606797749978969640917366873128;
+        const double d = sqrt_pos(d2);
+        return (5.0 / 3.0) * fma(s5, d, 1.0) * exp_nonpos(-s5 * d);
+    } else if constexpr (FAM == ABO_KERNEL_MATERN72) {
+        const double s7 = 2.64575131106459059050161575363926;
+        const double d = sqrt_pos(d2);
+        return fma(d2, 49.0 / 15.0, fma(d, 7.0 * s7 / 5.0, 7.0 / 5.0)) * exp_nonpos(-s7 * d);
+    } else {
+        const double s3 = 1.73205080756887729352744634150587;
+        return 3.0 * exp_nonpos(-s3 * sqrt_pos(d2));
+    }
+}
+
+// partial[block][c] = σ_f²·Σ over the block's pairs of w_ij·(Kinv[i][j] − α_i α_j)·q(d2_ij)·e_c²: the d traces of the ARD gradient in
+// the one sweep nlml_grad_kernel makes — same rows per workgroup, same lane ↔ column map, same tiles, weights and masks.  The squared
+// distance is summed first (q needs it whole), then the differences are formed again from the registers and the LDS broadcast and
+// each lands in its own accumulator; padded coordinates have e_c = 0 in every pair and stay exactly 0.
+template <int FAM, int DP>
+__global__ void __launch_bounds__(256) nlml_grad_ard_kernel(NlmlGradArgs p) {
+    __shared__ double zs[JT][DP];
+    __shared__ double ai[JT];
+    __shared__ double red[4][DP];
+    const int t = threadIdx.x;
+    const int ib = blockIdx.x * JT;                    // first row of this workgroup
+    for (int idx = t; idx < JT * DP; idx += 256) zs[idx / DP][idx % DP] = p.Xs[(int64_t)(ib + idx / DP) * DP + idx % DP];
+    if (t < JT) ai[t] = p.alpha[ib + t];
+    __syncthreads();
+    const int kend = (ib / 128 + 1) * 128;             // columns up to the end of the row's diagonal tile
+    const int diag0 = (ib / 128) * 128;
+    double acc[DP];
+#pragma unroll
+    for (int c = 0; c < DP; ++c) acc[c] = 0.0;
+    for (int k0 = 0; k0 < kend; k0 += KSTEP) {
+        const int k = k0 + 2 * t;
+        if (k < kend) {
+            double x0[DP], x1[DP];
+            const double* xp = p.Xs + (int64_t)k * DP;
+#pragma unroll
+            for (int c = 0; c < DP; ++c) { x0[c] = xp[c]; x1[c] = xp[DP + c]; }
+            const double a0 = p.alpha[k], a1 = p.alpha[k + 1];
+            const double w = (k >= diag0) ? 1.0 : 2.0;
+            // the rows stay a loop: unrolled sixteen-fold (as in nlml_grad_kernel) the scheduler interleaves the rows' exponentials
+            // on top of the 2·DP point registers and DP accumulators, and every instantiation from DP = 8 on spills
+#pragma unroll 1
+            for (int jj = 0; jj < JT; ++jj) {
+                const int i = ib + jj;
+                double r0 = 0.0, r1 = 0.0;
+#pragma unroll
+                for (int c = 0; c < DP; ++c) {
+                    const double z = zs[jj][c];
+                    const double e0 = x0[c] - z, e1 = x1[c] - z;
+                    r0 = fma(e0, e0, r0);
+                    r1 = fma(e1, e1, r1);
+                }
+                const double* kr = p.Kinv + (int64_t)i * p.ld + k;
+                const double m0 = kr[0] - ai[jj] * a0, m1 = kr[1] - ai[jj] * a1;
+                const double g0 = (i < p.N && k < p.N) ? w * m0 * dkappa_dlogell_over_d2<FAM>(r0) : 0.0;
+                const double g1 = (i < p.N && k + 1 < p.N) ? w * m1 * dkappa_dlogell_over_d2<FAM>(r1) : 0.0;
+#pragma unroll
+                for (int c = 0; c < DP; ++c) {
+                    const double z = zs[jj][c];
+                    const double e0 = x0[c] - z, e1 = x1[c] - z;
+                    acc[c] = fma(g0, e0 * e0, acc[c]);
+                    acc[c] = fma(g1, e1 * e1, acc[c]);
+                }
+            }
+        }
+    }
+    const int lane = t & 63, wave = t >> 6;
+#pragma unroll
+    for (int c = 0; c < DP; ++c) {
+        double v = acc[c];
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+        if (lane == 0) red[wave][c] = v;
+    }
+    __syncthreads();
+    if (t < DP) p.partial[(int64_t)blockIdx.x * DP + t] = p.sigma_f2 * (((red[0][t] + red[1][t]) + red[2][t]) + red[3][t]);
+}
+
+// out[c] = Σ_b partial[b][c]: one workgroup per coordinate, fixed order (strided per-thread sums, then the tree of
+// nlml_grad_finish_kernel) — no atomics, the same bits on every call
+__global__ void __launch_bounds__(256) nlml_grad_ard_finish_kernel(const double* __restrict__ partial, double* __restrict__ out,
+                                                                   int nblocks, int dp) {
+    __shared__ double r[256];
+    const int c = blockIdx.x;
+    double s0 = 0.0;
+    for (int i = threadIdx.x; i < nblocks; i += 256) s0 += partial[(int64_t)i * dp + c];
+    r[threadIdx.x] = s0;
+    __syncthreads();
+    for (int o = 128; o >= 1; o >>= 1) {
+        if (threadIdx.x < o) r[threadIdx.x] += r[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[c] = r[0];
+}
+
+template <int FAM>
+static hipError_t launch_grad_ard_fam(const NlmlGradArgs& a, hipStream_t s) {
+    dim3 grid(a.Np / JT), block(256);
+    switch (a.dp) {
+        case 1: hipLaunchKernelGGL((nlml_grad_ard_kernel<FAM, 1>), grid, block, 0, s, a); break;
+        case 2: hipLaunchKernelGGL((nlml_grad_ard_kernel<FAM, 2>), grid, block, 0, s, a); break;
+        case 4: hipLaunchKernelGGL((nlml_grad_ard_kernel<FAM, 4>), grid, block, 0, s, a); break;
+        case 8: hipLaunchKernelGGL((nlml_grad_ard_kernel<FAM, 8>), grid, block, 0, s, a); break;
+        case 16: hipLaunchKernelGGL((nlml_grad_ard_kernel<FAM, 16>), grid, block, 0, s, a); break;
+        case 32: hipLaunchKernelGGL((nlml_grad_ard_kernel<FAM, 32>), grid, block, 0, s, a); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_nlml_grad_ard(const NlmlGradArgs& a, double* out_ard, hipStream_t s) {
+    hipError_t e;
+    switch (a.family) {
+        case ABO_KERNEL_SE: e = launch_grad_ard_fam<ABO_KERNEL_SE>(a, s); break;
+        case ABO_KERNEL_MATERN52: e = launch_grad_ard_fam<ABO_KERNEL_MATERN52>(a, s); break;
+        case ABO_KERNEL_MATERN72: e = launch_grad_ard_fam<ABO_KERNEL_MATERN72>(a, s); break;
+        case ABO_KERNEL_MATERN32: e = launch_grad_ard_fam<ABO_KERNEL_MATERN32>(a, s); break;
+        default: return hipErrorInvalidValue;
+    }
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(nlml_grad_ard_finish_kernel, dim3(a.dp), dim3(256), 0, s, a.partial, out_ard, a.Np / JT, a.dp);
+    // tr(Kinv), αᵀα, αᵀδ from the isotropic finish step itself (no partials to add: out[0] = 0), so that what the two entry
+    // points derive from them agrees bit for bit
+    hipLaunchKernelGGL(nlml_grad_finish_kernel, dim3(1), dim3(256), 0, s, a, 0);
+    return hipGetLastError();
+}
+
 // test hook: out[i] = kappa(family, d2[i])
 __global__ void kappa_test_kernel(int family, const double* d2, double* out, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -16,7 +16,7 @@ from . import _lib
 from ._lib import DEVICE, HOST
 from .acquisition import AbstractAcquisition
 from .kernels import Kernel, extract_scale_and_lengthscale, with_lengthscale
-from .surrogate import HipStandardGP, _Handle, _is_torch, as_points
+from .surrogate import HipStandardGP, _Handle, _is_torch, as_points, refuse_ard
 
 
 class gradConstMean:
@@ -39,6 +39,7 @@ class HipGradientGP(HipStandardGP):
                  chunk: int = 0, n_max: int = 0, contraction: str | None = None, incremental_update: bool = False):
         super().__init__(kernel, noise_var, mean=None, device=device, jitter=jitter, chunk=chunk, n_max=n_max,
                          contraction=contraction, incremental_update=incremental_update)
+        refuse_ard(self, "HipGradientGP")            # the derivative observations would need rescaling too
         self.p = int(p)
         self.mean = gradConstMean(np.zeros(self.p)) if mean is None else mean
         if len(self.mean.c) != self.p:

@@ -30,6 +30,21 @@ def nlml_and_grad(model: HipStandardGP, params, xs, ys):
     return v.value, np.array([d1.value, d2.value])
 
 
+def nlml_and_grad_ard(model: HipStandardGP, params, xs, ys):
+    """(nlml, [∂/∂log ℓ_1 … ∂/∂log ℓ_d, ∂/∂log scale]) at params = [log ℓ_1 … log ℓ_d, log scale] for the kernel with one length scale
+    per coordinate: ONE refit on the coordinates divided by ℓ_c (ell = 1 in the library) and one abo_nlml_grad_ard, whose d traces
+    come out of the single sweep over K⁻¹ − ααᵀ the isotropic gradient makes — central differences would take 2d refits."""
+    p = np.asarray(params, dtype=np.float64)
+    d = p.shape[0] - 1
+    k = math.exp(p[-1]) * with_lengthscale(get_kernel_constructor(model), np.exp(p[:-1]))
+    g = HipStandardGP(k, model.noise_var, mean=model.mean, device=model.device, jitter=model.jitter, contraction=model.contraction)
+    fitted = update(g, xs, ys)
+    v, d2 = C.c_double(), C.c_double()
+    d1 = (C.c_double * d)()
+    _lib.check(_lib.lib().abo_nlml_grad_ard(fitted._require(), d, C.byref(v), d1, C.byref(d2), None))
+    return v.value, np.array(list(d1) + [d2.value])
+
+
 class Dual:
     """value + partials — the shape of a ForwardDiff.Dual, which is what the reference's stock driver evaluates the objective
     on (`autodiff=:forward`, bayesian_opt.jl:276-285).  Only what the chain rule of `nlml_dual` needs: the Julia shim
@@ -103,13 +118,21 @@ def lengthscale_bounds(X_train, domain, min_frac: float = 0.1, max_frac: float =
 
 
 def optimize_hyperparameters(model: HipStandardGP, x_train, y_train, old_params, scale_std: float = 1.0,
-                             length_scale_only: bool = False, num_restarts: int = 1, domain=None, rng=None):
+                             length_scale_only: bool = False, num_restarts: int = 1, domain=None, rng=None, ard: bool = False):
     """optimize_hyperparameters (bayesian_opt.jl:196-328): box bounds (:214-242), starting point clamped
     into them (:247), `num_restarts − 1` extra uniform starts in log space (:263-266), the best converged
     run wins (:275-300), the old model is returned if every restart fails (:302-304), otherwise a NEW
-    un-conditioned model with the optimised kernel (:319-327)."""
+    un-conditioned model with the optimised kernel (:319-327).
+
+    ard=True searches one length scale per coordinate (the generalisation the reference leaves as a TODO, bayesian_opt.jl:193):
+    old_params = [log ℓ_1 … log ℓ_d, log scale], or the isotropic [log ℓ, log scale] whose ℓ is replicated; the bounds are
+    lengthscale_bounds' per-dimension vectors; value and all d + 1 partials come from one refit (nlml_and_grad_ard); the result is a
+    new un-conditioned ARD model.  Same L-BFGS-B options, restarts and failure handling."""
     from scipy.optimize import minimize
     rng = np.random.default_rng() if rng is None else rng
+    if ard:
+        return _optimize_hyperparameters_ard(model, x_train, y_train, old_params, scale_std, length_scale_only, num_restarts, domain,
+                                             rng, minimize)
     ls_lo, ls_hi = 1e-3, 1e3
     if domain is not None:
         lo_v, hi_v = lengthscale_bounds(x_train, domain, rng=rng, device=getattr(model, "device", None))
@@ -157,3 +180,52 @@ def optimize_hyperparameters(model: HipStandardGP, x_train, y_train, old_params,
     ell = math.exp(best_p[0])
     scale = get_scale(model)[0] if length_scale_only else math.exp(best_p[1])
     return rebuild(model, scale * with_lengthscale(get_kernel_constructor(model), ell))
+
+
+def _optimize_hyperparameters_ard(model, x_train, y_train, old_params, scale_std, length_scale_only, num_restarts, domain, rng, minimize):
+    from . import gradient_gp as G
+    if isinstance(model, G.HipGradientGP) or hasattr(model, "devices"):
+        raise TypeError("optimize_hyperparameters(ard=True) serves a single-device HipStandardGP only")
+    X = np.asarray(x_train, dtype=np.float64)
+    d = 1 if X.ndim == 1 else X.shape[1]
+    ls_lo, ls_hi = np.full(d, 1e-3), np.full(d, 1e3)
+    if domain is not None:
+        lo_v, hi_v = lengthscale_bounds(x_train, domain, rng=rng, device=getattr(model, "device", None))
+        ls_lo, ls_hi = np.maximum(np.asarray(lo_v, dtype=np.float64), 1e-6), np.asarray(hi_v, dtype=np.float64)
+        assert np.all(ls_lo < ls_hi)
+    sc_lo, sc_hi = 1e-3 / scale_std ** 2, 1e6 / scale_std ** 2
+    old = np.asarray(old_params, dtype=np.float64).reshape(-1)
+    if old.shape[0] == 2 and d != 1:
+        old = np.concatenate([np.full(d, old[0]), old[1:]])            # an isotropic start: its ℓ in every coordinate
+    if old.shape[0] != d + 1:
+        raise _lib.DimensionMismatch(f"old_params has {old.shape[0]} entries; ard=True takes d + 1 = {d + 1} (or the isotropic 2)")
+    eps2 = 2 * np.finfo(np.float64).eps
+    lower_full, upper_full = np.log(np.append(ls_lo, sc_lo)), np.log(np.append(ls_hi, sc_hi))
+    if length_scale_only:
+        # the fixed log-scale keeps its own box here (the isotropic path's clamp of it into the length-scale box mirrors a broadcast
+        # of 1-element bounds in the reference that has no d-vector counterpart)
+        lower, upper = lower_full[:d], upper_full[:d]
+    else:
+        lower, upper = lower_full, upper_full
+    start_full = np.clip(old, lower_full + eps2, upper_full - eps2)
+    xs, ys = prep_input(model, x_train), prep_output(model, y_train)
+
+    def obj(p):
+        full = np.append(p, start_full[d]) if length_scale_only else p
+        v, g = nlml_and_grad_ard(model, full, xs, ys)
+        return v, (g[:d] if length_scale_only else g)
+
+    inits = [start_full[:len(lower)].copy()] + [rng.uniform(lower, upper) for _ in range(num_restarts - 1)]
+    best_v, best_p = np.inf, None
+    for x0 in inits:
+        try:
+            res = minimize(obj, x0, jac=True, method="L-BFGS-B", bounds=list(zip(lower, upper)),
+                           options={"gtol": 1e-6, "ftol": 2.2e-9, "maxls": 20})
+        except (_lib.PosDefException, _lib.AboError, FloatingPointError):
+            continue                                  # a failed restart is skipped (bayesian_opt.jl:296-299)
+        if res.success and res.fun < best_v:
+            best_v, best_p = float(res.fun), res.x.copy()
+    if best_p is None:
+        return model                                  # all restarts failed (:302-304)
+    scale = get_scale(model)[0] if length_scale_only else math.exp(best_p[d])
+    return _update_model_parameters(model, scale * with_lengthscale(get_kernel_constructor(model), np.exp(best_p[:d])))

@@ -14,13 +14,14 @@ import numpy as np
 from . import _lib
 from ._lib import DEVICE, HOST
 from .acquisition import AbstractAcquisition, ExpectedImprovement
-from .surrogate import HipStandardGP, _Handle, as_points
+from .surrogate import HipStandardGP, _Handle, as_points, refuse_ard
 
 
 def append(model: HipStandardGP, x, y) -> HipStandardGP:
     """Condition on one more observation (x, y) in O(N²): returns a new model sharing the factor storage;
     `model` stays valid (free rollback).  Raises PosDefException(N+1) if the bordered pivot is ≤ 0.
     Give the model capacity with HipStandardGP(..., n_max=N_max) to avoid refit fallbacks."""
+    refuse_ard(model, "append")
     L = _lib.lib()
     xa = np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1))
     hp = C.c_void_p()
@@ -54,6 +55,7 @@ class ResidentCandidates:
     """M candidates kept on the GPU together with their posterior μ, σ² under `model`."""
 
     def __init__(self, model: HipStandardGP, Z):
+        refuse_ard(model, "ResidentCandidates")
         L = _lib.lib()
         zp, m, d, space, keep = as_points(Z)
         hp = C.c_void_p()
@@ -295,6 +297,7 @@ def greedy_qei(model: HipStandardGP, cands: ResidentCandidates, q: int, xi: floa
     block: None = the library's default (block form with T = 16 when the model and the set qualify), 0 / False = the plain loop
     (one bordered append and one O(N·M) pass over the resident K_ZX per pick), T = block form with T points per block.
     stats (a dict, optional) receives the batch's statistics (abo_qei_stats)."""
+    refuse_ard(model, "greedy_qei")
     use_block = (block is None or bool(block)) and not hasattr(model, "p") and 1 <= q <= 64
     sharded = False
     if group is not None or _dist_ready():
@@ -383,6 +386,7 @@ def mc_qei(model: HipStandardGP, cands: ResidentCandidates, q: int, xi: float, b
     Block form only: a set whose K_ZX is not resident or a gradient-enhanced model raises ValueError; a set sharded over
     torch.distributed raises NotImplementedError.
     Returns (batch points (q, d), their global indices, the joint q-EI of the first j + 1 picks)."""
+    refuse_ard(model, "mc_qei")
     if _world_size(group) > 1:
         raise NotImplementedError("mc_qei: the Monte-Carlo q-EI of a set sharded over torch.distributed is not implemented")
     if cands.model is not model and cands.model._require() != model._require():

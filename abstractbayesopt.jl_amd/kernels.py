@@ -14,7 +14,7 @@ _NAMES = {SE: "Squared Exponential Kernel", MATERN52: "Matern 5/2 Kernel", MATER
 @dataclass(frozen=True)
 class Kernel:
     family: int
-    lengthscale: object = None   # None = no ScaleTransform attached (defaults to 1.0)
+    lengthscale: object = None   # None = no ScaleTransform attached (defaults to 1.0); a tuple = one per coordinate (ARD)
     scale: object = None         # None = not a ScaledKernel (defaults to 1.0)
 
     def __rmul__(self, s):       # `scale * kernel`  → ScaledKernel(kernel, scale)
@@ -52,9 +52,19 @@ def Matern32Kernel():
     return Kernel(MATERN32)
 
 
-def with_lengthscale(k: Kernel, ell: float) -> Kernel:
-    """KernelFunctions.with_lengthscale(k, ℓ) = k ∘ ScaleTransform(1/ℓ)."""
+def with_lengthscale(k: Kernel, ell) -> Kernel:
+    """KernelFunctions.with_lengthscale(k, ℓ) = k ∘ ScaleTransform(1/ℓ); a sequence of d positive floats = k ∘ ARDTransform(1 ./ ℓ),
+    one length scale per coordinate (stored as a tuple)."""
+    if hasattr(ell, "__len__"):
+        ells = tuple(float(e) for e in ell)
+        if not ells or not all(e > 0.0 and e < float("inf") for e in ells):
+            raise ValueError(f"ARD length scales must be a non-empty sequence of positive finite floats, got {ell!r}")
+        return replace(k, lengthscale=ells)
     return replace(k, lengthscale=float(ell))
+
+
+def is_ard(k: Kernel) -> bool:
+    return isinstance(k.lengthscale, tuple)
 
 
 def ScaledKernel(k: Kernel, scale: float) -> Kernel:

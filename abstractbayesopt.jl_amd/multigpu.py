@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from .acquisition import AbstractAcquisition, ExpectedImprovement
-from .surrogate import AbstractSurrogate, HipStandardGP, _Handle, as_points
+from .surrogate import AbstractSurrogate, HipStandardGP, _Handle, as_points, refuse_ard
 
 
 class _GroupHandle:
@@ -55,6 +55,7 @@ class HipShardedGP(HipStandardGP):
                  incremental_update: bool = False):
         super().__init__(kernel, noise_var, mean=mean, device=int(devices[0]), jitter=jitter, chunk=chunk, n_max=n_max,
                          incremental_update=incremental_update)
+        refuse_ard(self, type(self).__name__)
         self.devices = [int(v) for v in devices]
         self._g = None
 

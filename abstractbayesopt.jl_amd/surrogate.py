@@ -16,7 +16,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import AboParams, AboTimings, DEVICE, HOST
-from .kernels import ConstMean, Kernel, ZeroMean, extract_scale_and_lengthscale, with_lengthscale
+from .kernels import ConstMean, Kernel, ZeroMean, extract_scale_and_lengthscale, is_ard, with_lengthscale
 
 
 class AbstractSurrogate:
@@ -55,6 +55,64 @@ def as_points(x, d_expected=None):
         raise _lib.DimensionMismatch("inputs must be (M,) or (M, d)")
     a = np.ascontiguousarray(a)
     return a.ctypes.data, a.shape[0], a.shape[1], HOST, a
+
+
+class ArdUnsupported(TypeError):
+    """an entry point that takes or returns coordinates and does not scale them was handed a model with per-coordinate length scales"""
+
+
+def ard_lengthscales(model):
+    """the d length scales of an ARD model as an array, None for a model with one scalar length scale"""
+    ell = getattr(getattr(model, "kernel", None), "lengthscale", None)
+    return np.asarray(ell, dtype=np.float64) if isinstance(ell, tuple) else None
+
+
+def refuse_ard(model, what: str) -> None:
+    """the one error of every entry point that would otherwise treat an ARD model as isotropic"""
+    if ard_lengthscales(model) is not None:
+        raise ArdUnsupported(f"{what} does not support ARD length scales (one per coordinate): its coordinates would cross the "
+                             "library unscaled; use a scalar length scale, or pre-divide the coordinates yourself")
+
+
+def _ard_scale(model, x, inverse: bool, bounds: bool):
+    ell = ard_lengthscales(model)
+    if ell is None or x is None:
+        return x
+    if np.isscalar(x):
+        x = [float(x)]
+    if not _is_torch(x):
+        try:
+            x = np.asarray(x, dtype=np.float64)
+        except ValueError as e:   # ragged vector-of-vectors
+            raise _lib.DimensionMismatch(f"input points differ in length: {e}") from None
+    nd = x.dim() if _is_torch(x) else x.ndim
+    # as_points' reading of the containers: a vector is M points of dimension 1 — unless it is a box bound or one point (bounds)
+    vector_of_scalars = nd == 1 and not bounds
+    d = 1 if vector_of_scalars else (x.shape[-1] if nd >= 1 else 0)
+    if d != ell.shape[0]:
+        raise _lib.DimensionMismatch(f"the model has {ell.shape[0]} length scales, the points have dimension {d}")
+    if _is_torch(x):
+        import torch
+        e = torch.as_tensor(ell, dtype=x.dtype, device=x.device)       # d values; the points stay where they are
+    else:
+        e = ell
+    if vector_of_scalars:
+        e = e[0]
+    return x * e if inverse else x / e
+
+
+def to_model_space(model, x, bounds: bool = False):
+    """Points in any container `as_points` reads — or, with bounds=True, a box bound / one point as a d-vector — → the coordinates the
+    library sees.  An ARD model (a kernel with
+    one length scale per coordinate) crosses the C-ABI as ell = 1 on coordinates divided by their ℓ_c (include/abo_hip.h:
+    abo_nlml_grad_ard); any other model's points pass through untouched.  NumPy in, NumPy out; a torch tensor is scaled with torch on
+    its own device."""
+    return _ard_scale(model, x, False, bounds)
+
+
+def from_model_space(model, x, bounds: bool = False):
+    """the inverse of `to_model_space`: what the library returns as coordinates, multiplied back by ℓ_c"""
+    return _ard_scale(model, x, True, bounds)
 
 
 class _Handle:
@@ -109,7 +167,9 @@ class HipStandardGP(AbstractSurrogate):
         return (self.mean, self.kernel)
 
     def _params(self) -> AboParams:
-        return AboParams(family=self.kernel.family, device=self.device, ell=float(self.kernel.lengthscale),
+        # ARD: the length scales live in the coordinates (to_model_space), the library sees ell = 1
+        ell = 1.0 if is_ard(self.kernel) else float(self.kernel.lengthscale)
+        return AboParams(family=self.kernel.family, device=self.device, ell=ell,
                          sigma_f2=float(self.kernel.scale), noise_var=float(self.noise_var),
                          mean_c=float(getattr(self.mean, "c", 0.0)), jitter=self.jitter, n_max=self.n_max, chunk=self.chunk)
 
@@ -212,6 +272,7 @@ def update(model: HipStandardGP, xs, ys) -> HipStandardGP:
     """update(model::StandardGP, xs, ys) (StandardGP.jl:79-83): full refit, returns a new model.
     Raises PosDefException(info) when K + σ²I is not positive definite (no jitter unless the model
     was built with jitter > 0) and DimensionMismatch on ragged / mismatched inputs."""
+    xs = to_model_space(model, xs)
     L = _lib.lib()
     xp, n, d, xspace, xkeep = as_points(xs)
     if _is_torch(ys):
@@ -257,9 +318,10 @@ def _with_path(model, path: int):
 
 # ---- posterior -----------------------------------------------------------------------------------
 def _predict(model, x, want_mu, want_var):
-    L = _lib.lib()
     if np.isscalar(x):                       # abstract.jl:67-69 scalar wrapper
         x = [float(x)]
+    x = to_model_space(model, x)
+    L = _lib.lib()
     zp, m, d, zspace, keep = as_points(x)
     if hasattr(model, "devices") and zspace == HOST:          # HipShardedGP: shard the batch over the group's devices
         from . import multigpu
@@ -314,6 +376,12 @@ def nlml(model: HipStandardGP, params, xs, ys) -> float:
     """nlml(model, params, xs, ys) (StandardGP.jl:99-114): params = [log ℓ, log scale]; rebuilds the
     kernel with exp.(params), keeps noise and mean, returns −logpdf (value only — ForwardDiff duals
     cannot cross a C-ABI; SURVEY.md §8(f) rank 2 tracks the analytic gradient)."""
+    if len(params) > 2:
+        # ARD: params = [log ℓ_1 … log ℓ_d, log scale] (hyperparams.nlml_and_grad_ard is the same with the gradient; at d = 1 the two
+        # parameter sets coincide)
+        k = math.exp(params[-1]) * with_lengthscale(get_kernel_constructor(model), [math.exp(p) for p in params[:-1]])
+        g = HipStandardGP(k, model.noise_var, mean=model.mean, device=model.device, jitter=model.jitter, contraction=model.contraction)
+        return nlml_fitted(update(g, xs, ys))
     log_ell, log_scale = params
     if hasattr(log_ell, "partials") or hasattr(log_scale, "partials"):
         # dual-number parameters (what Optim's autodiff=:forward feeds the objective, bayesian_opt.jl:276-285): value and
@@ -346,7 +414,7 @@ def std_y(model: HipStandardGP, ys, mu, sigma):
 
 
 def rescale_model(model: HipStandardGP, sigma):
-    ell = get_lengthscale(model)[0]
+    ell = model.kernel.lengthscale
     new_scale = get_scale(model)[0] / sigma ** 2
     new_kernel = new_scale * with_lengthscale(get_kernel_constructor(model), ell)
     mean = model.mean
@@ -364,8 +432,9 @@ def _update_model_parameters(model: HipStandardGP, kernel: Kernel):
 
 
 def get_lengthscale(model: HipStandardGP):
-    """1-element vector, as the reference returns (StandardGP.jl:261; test_surrogates.jl:32-33)."""
-    return [model.kernel.lengthscale]
+    """1-element vector, as the reference returns (StandardGP.jl:261; test_surrogates.jl:32-33); the d values of an ARD model."""
+    ell = model.kernel.lengthscale
+    return list(ell) if isinstance(ell, tuple) else [ell]
 
 
 def get_scale(model: HipStandardGP):
@@ -411,4 +480,4 @@ def training_data(model: HipStandardGP):
     p = getattr(model, "p", 1)
     X, y = np.empty((n.value, d.value)), np.empty(n.value * p)
     _lib.check(Lb.abo_get_data(model._require(), X.ctypes.data, y.ctypes.data))
-    return X, (y if p == 1 else np.ascontiguousarray(y.reshape(p, n.value).T))
+    return from_model_space(model, X), (y if p == 1 else np.ascontiguousarray(y.reshape(p, n.value).T))

@@ -12,7 +12,7 @@ import numpy as np
 from . import _lib
 from ._lib import DEVICE, HOST
 from .kernels import MATERN32, MATERN52, MATERN72, SE
-from .surrogate import HipStandardGP, _is_torch, as_points
+from .surrogate import HipStandardGP, _is_torch, as_points, refuse_ard
 
 _NU = {MATERN32: 1.5, MATERN52: 2.5, MATERN72: 3.5}
 
@@ -61,6 +61,7 @@ class SamplePaths:
     """S sample paths of one conditioned model.  Attributes omega (R × d), phase (R), w (S × R), eps (S × N): the base draws."""
 
     def __init__(self, model, omega, phase, w, eps):
+        refuse_ard(model, "SamplePaths")
         if hasattr(model, "devices"):
             raise TypeError("sample paths of a sharded model (HipShardedGP) are not implemented: draw them from a single-device "
                             "HipStandardGP conditioned on the same data")
@@ -208,6 +209,7 @@ def _model_shape(model):
 
 def sample_paths(model, S: int, R: int = 1024, rng=None) -> SamplePaths:
     """S posterior sample paths of `model` in R random Fourier features; the base draws come from `rng` (a seed or a Generator)"""
+    refuse_ard(model, "sample_paths")
     if hasattr(model, "devices"):
         raise TypeError("sample_paths: a sharded model (HipShardedGP) is not supported: draw the paths from a single-device "
                         "HipStandardGP conditioned on the same data")

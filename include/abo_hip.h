@@ -637,6 +637,22 @@ int32_t abo_nlml(abo_gp* gp, double* out);
  *   appended view).  Any output may be NULL. */
 int32_t abo_nlml_grad(abo_gp* gp, double* nlml, double* d_log_ell, double* d_log_sigma_f2);
 
+/* added within ABI 7: the same call for a kernel with one length scale per coordinate (ARD),
+ *   k(x,z) = sigma_f2·kappa(‖(x − z)./ℓ‖),  d_log_ell[c] = ½ tr((K⁻¹ − ααᵀ) ∂K/∂log ℓ_c)  for c < d,
+ * evaluated at ℓ_c = the handle's ell for every c, all d traces in the one sweep over K⁻¹ − ααᵀ that abo_nlml_grad makes
+ * (∂K_ij/∂log ℓ_c = sigma_f2·q(d2)·e_c², e = (x_i − x_j)/ell, d2 = Σ e_c², q = (∂kappa/∂log ell)/d2 in closed form).  Their sum is
+ * abo_nlml_grad's d_log_ell up to the rounding of a differently ordered sum; nlml and d_log_sigma_f2 are abo_nlml_grad's bit for bit.
+ * d_log_noise = ½·σ²·(tr K⁻¹ − αᵀα) with σ² the noise the factor was built with (0 when that is 0).
+ *
+ * The convention that makes this ARD: the library has ONE scalar ell, and an ARD model crosses this ABI as ell = 1 with every
+ * coordinate pre-divided by its ℓ_c — training points, candidates and box bounds alike (abo_lhs in the scaled box is the scaled
+ * design); returned points are multiplied back by ℓ_c.  On such a handle d_log_ell[c] is exactly ∂NLML/∂log ℓ_c.
+ *
+ * Needs a freshly fitted handle (not an appended view); d must be the model's (ABO_EDIM); a gradient-enhanced handle or d > 32 is
+ * ABO_EINVAL; the arguments are checked before any device work.  abo_timings.nlml_kinv_ms / nlml_trace_ms are filled as by
+ * abo_nlml_grad.  Any output may be NULL; d_log_ell holds d values.  Two calls on the same handle return the same bits. */
+int32_t abo_nlml_grad_ard(abo_gp* gp, int32_t d, double* nlml, double* d_log_ell, double* d_log_sigma_f2, double* d_log_noise);
+
 /* --- introspection (tests) ----------------------------------------------------------------------
  * L (N×N row-major, strictly-upper part zero), alpha (N), Linv = L⁻¹ (N×N row-major); any may be
  * NULL.  Host buffers. */

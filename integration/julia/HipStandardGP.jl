@@ -343,6 +343,16 @@ function nlml_and_grad(m::HipStandardGP, params, xs::AbstractVector, ys::Abstrac
     _check(@ccall LIBABO.abo_nlml_grad(f.gpx.ptr::Ptr{Cvoid}, v::Ptr{Float64}, g1::Ptr{Float64}, g2::Ptr{Float64})::Int32)
     v[], [g1[], g2[]]
 end
+# one length scale per coordinate (ARD; include/abo_hip.h): the model crosses the ABI as ℓ = 1 on coordinates pre-divided by ℓ_c, and
+# ONE refit yields value and gradient w.r.t. (log ℓ_1 … log ℓ_d, log σ_f²), params in that order
+function nlml_and_grad_ard(m::HipStandardGP, params, xs::AbstractVector, ys::AbstractVector)
+    d = length(params) - 1; ℓ = exp.(params[1:d])
+    v = Ref{Float64}(); gℓ = zeros(Float64, d); g2 = Ref{Float64}()
+    f = _fitted_with(m, 0.0, params[end], [x ./ ℓ for x in xs], ys)
+    GC.@preserve gℓ _check(@ccall LIBABO.abo_nlml_grad_ard(f.gpx.ptr::Ptr{Cvoid}, Int32(d)::Int32, v::Ptr{Float64}, gℓ::Ptr{Float64},
+                                                            g2::Ptr{Float64}, C_NULL::Ptr{Float64})::Int32)
+    v[], vcat(gℓ, g2[])
+end
 # The STOCK driver needs nothing else: optimize_hyperparameters (bayesian_opt.jl:253-285) hands `p -> nlml(model, p, xs, ys)` to
 # Optim with `autodiff=:forward`, i.e. it evaluates the objective on ForwardDiff.Dual parameters.  Duals cannot cross a C-ABI —
 # and need not: the library returns ∂NLML/∂(log ℓ, log σ_f²) analytically, so the Dual-typed methods evaluate at the VALUES and
