@@ -28,7 +28,12 @@ EXPORTS = ["abo_create", "abo_set_contraction", "abo_create_grad", "abo_predict_
            "abo_score_mes", "abo_acq_mes", "abo_cand_acq_mes", "abo_refine_mes", "abo_optimize_acquisition_mes"]
 TEST_EXPORTS = ["abo_test_gemm_nt", "abo_test_kappa", "abo_test_oz_plan", "abo_test_oz_contract", "abo_test_acq_grad",
                 "abo_test_acq_grad_terms", "abo_test_prune_plan", "abo_test_prune_force", "abo_test_prune_levels", "abo_test_prune_plan_levels", "abo_test_prune_bounds", "abo_test_prune_mean",
-                "abo_test_kappa_tail", "abo_test_prune_bound_moduli", "abo_test_prune_bound_plan", "abo_test_oz_contract_bound", "abo_test_acq_partials", "abo_test_mes_partials", "abo_test_acq_grad_mes"]
+                "abo_test_kappa_tail", "abo_test_prune_bound_moduli", "abo_test_prune_bound_plan", "abo_test_oz_contract_bound", "abo_test_acq_partials", "abo_test_mes_partials", "abo_test_acq_grad_mes",
+                "abo_test_gemm_args", "abo_test_gemm_path", "abo_test_gemm_swz_q", "abo_test_gemm_swz_map", "abo_test_qei_pass", "abo_test_splitk_reduce",
+                "abo_test_var_gemm"]
+# what launch_gemm_nt ran, as abo_test_gemm_args / abo_test_gemm_path report it (include/abo_hip.h: ABO_GEMM_PATH_*)
+GEMM_PATH_TILED, GEMM_PATH_SWIZZLED, GEMM_PATH_SMALL, GEMM_PATH_SKINNY, GEMM_PATH_SPLITK = range(5)
+K_FULL, K_A_LOWER, K_A_UPPER, K_B_LOWER, K_B_UPPER = range(5)
 ABI_VERSION = 7
 CONTRACT_AUTO, CONTRACT_FP64, CONTRACT_INT8 = 0, 1, 2
 # what abo_update / abo_mgpu_update ran (include/abo_hip.h)
@@ -201,6 +206,14 @@ def lib():
         L.abo_test_oz_contract_bound.argtypes = [i32, vp, i64, i32, i32, vp, i64, i32, f64, i32, i32, vp, i64, vp]
     if hooks:
         L.abo_test_gemm_nt.argtypes = [i32, vp, vp, vp, i32, i32, i32, i64, i64, i64, f64, f64]
+        L.abo_test_gemm_args.argtypes = [i32, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, i64, i32, i32, i32, i32, i32, i32, f64, f64, i32, i32,
+                                         vp, C.POINTER(i32)]
+        L.abo_test_gemm_path.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32)]
+        L.abo_test_gemm_swz_q.argtypes = [i32, i32, C.POINTER(i32)]
+        L.abo_test_gemm_swz_map.argtypes = [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]
+        L.abo_test_qei_pass.argtypes = [i32, vp, i64, i32, vp, i64, i64, i32, f64, vp, i64, i32, i32, i64]
+        L.abo_test_splitk_reduce.argtypes = [i32, vp, i64, i64, i32, i32, i32, i32, i32, i32, vp, i64]
+        L.abo_test_var_gemm.argtypes = [i32, vp, i64, i32, i32, vp, i64, i32, vp, i64, i32]
     L.abo_mgpu_create.argtypes = [C.POINTER(AboParams), i32, C.POINTER(i32), C.POINTER(vp)]
     L.abo_mgpu_create_grad.argtypes = [C.POINTER(AboParams), i32, vp, i32, C.POINTER(i32), C.POINTER(vp)]
     L.abo_mgpu_append_grad.argtypes = [vp, vp, i32, vp, C.POINTER(i64), vp]

@@ -43,6 +43,53 @@ struct GemmArgs {
     int swz_g = 4;        // tile rows per super-row of that map
 };
 hipError_t launch_gemm_nt(const GemmArgs& a, hipStream_t s);
+// Which kernel and launch shape launch_gemm_nt gives a product (== ABO_GEMM_PATH_* of include/abo_hip.h): the one place the choice is
+// made — pure host code, no GPU call; reads ABO_GEMM_SMALL (0 never / 1 always the small kernel) and ABO_GEMM_NO_SWIZZLE.
+enum GemmPath {
+    GEMM_PATH_INVALID = -2,    // split-k with batch != 1, beta != 0, a Ct or a ksplit that is no multiple of 128: launch_gemm_nt refuses it
+    GEMM_PATH_NONE = -1,       // M, N or batch ≤ 0: nothing to do
+    GEMM_PATH_TILED = 0,       // gemm_nt_kernel, 2-D grid of 128×128 tiles (× batch)
+    GEMM_PATH_SWIZZLED = 1,    // gemm_nt_kernel, 1-D XCD-aware launch over the lower tiles of a square SYRK
+    GEMM_PATH_SMALL = 2,       // gemm_nt_small_kernel: ≤ 64 tiles, K a multiple of 128, not in place
+    GEMM_PATH_SKINNY = 3,      // split-k, gemm_skinny_kernel<mrows/16>
+    GEMM_PATH_SPLITK = 4       // split-k, gemm_nt_kernel with one chunk per blockIdx.z
+};
+// tiles of the launch: Tm·Tn, or the tiles (ti, tj ≤ ti), tj < Tn under lower_only; × batch
+inline int64_t gemm_nt_tiles(const GemmArgs& a) {
+    const int64_t Tm = a.M / TB, Tn = a.N / TB;
+    int64_t tiles = Tm * Tn;
+    if (a.lower_only) {
+        const int64_t q = Tm < Tn ? Tm : Tn;
+        tiles = q * (q + 1) / 2 + (Tm - q) * Tn;
+    }
+    return tiles * a.batch;
+}
+int gemm_nt_path(const GemmArgs& a);
+// The swizzled launch's workgroup → tile map in its two steps (gemm_nt_kernel documents the intent).
+// Workgroup L of the padded 1-D grid of ⌈tiles/8⌉·8 → position Q in the tile sequence: XCD L & 7 takes the (L & 7)-th eighth; Q ≥ tiles: idle.
+__host__ __device__ inline int gemm_swz_q(int L, int tiles) {
+    const int per = (tiles + 7) >> 3;
+    return (L & 7) * per + (L >> 3);
+}
+// Position Q < T(T+1)/2 → lower tile (ti, tj ≤ ti) of a T×T tile grid: the sequence runs through super-rows of G tile rows column by column
+__host__ __device__ inline void gemm_swz_tile(int T, int G, int Q, int& ti, int& tj) {
+    int g = (int)((sqrt(8.0 * (double)Q + 1.0) - 1.0) / (2.0 * G));        // super-row: G·g·(G·g+1)/2 tiles lie before it
+    while ((G * (g + 1)) * (G * (g + 1) + 1) / 2 <= Q) ++g;
+    while ((G * g) * (G * g + 1) / 2 > Q) --g;
+    int w = Q - (G * g) * (G * g + 1) / 2;
+    const int r0 = G * g;
+    const int R = G < T - r0 ? G : T - r0;
+    if (w < R * (r0 + 1)) {                                              // full columns 0 … r0: R tiles each
+        tj = w / R;
+        ti = r0 + w - tj * R;
+    } else {                                                             // the triangle at the right end
+        w -= R * (r0 + 1);
+        int c = 1;
+        while (w >= R - c) { w -= R - c; ++c; }
+        tj = r0 + c;
+        ti = tj + w;
+    }
+}
 // out[r][c] = Σ_z P[z][r][c] over the chunks z that intersect the k range of column tile c/128 under `kmode` (K_FULL, K_B_LOWER,
 // K_B_UPPER); P: nz partial products of rows × cols (leading dimension ldp, stride sP), K the full k length
 hipError_t launch_splitk_reduce(const double* P, int64_t ldp, int64_t sP, int nz, int rows, int cols, int K, int ksplit, int kmode,
@@ -58,7 +105,9 @@ struct VarGemmArgs {
     int Np, Mc;           // multiples of 128
     int nvalid;           // rows ≥ nvalid (the view's N) are excluded from the norm
 };
-hipError_t launch_var_gemm(const VarGemmArgs& a, hipStream_t s);
+// variant 0: the 256-row kernel when Np is a multiple of 256, the 128-row kernel otherwise; 1: the 128-row kernel whatever Np (tests:
+// the two agree bit for bit)
+hipError_t launch_var_gemm(const VarGemmArgs& a, hipStream_t s, int variant = 0);
 
 // ---- the same contraction on the int8 matrix pipe (ozaki.hip): exact products of fixed-point images of W and K_XZ through
 // residues modulo n coprime moduli ≤ 256, Chinese-remainder reconstruction in fp64

@@ -4187,6 +4187,107 @@ int32_t abo_test_gemm_nt(int32_t device, const double* A, const double* B, doubl
     HIPCHK(wait_stream(nullptr));
     return ABO_OK;
 }
+
+// what the GEMM kernels assume of shapes and flags (no pointer is looked at): nullptr, or the text of the complaint
+static const char* gemm_args_complaint(const GemmArgs& a) {
+    if (a.M <= 0 || a.N <= 0 || a.M % TB || a.N % TB) return "M, N must be positive multiples of 128";
+    if (a.K <= 0 || a.K % 16) return "K must be a positive multiple of 16";
+    if (a.kmode < K_FULL || a.kmode > K_B_UPPER) return "unknown kmode";
+    if (a.batch < 1 || a.ksplit < 0 || a.mrows < 0) return "batch >= 1, ksplit >= 0, mrows >= 0";
+    if (a.ksplit && (a.K % 128 || a.ksplit % 128)) return "split-k: K and ksplit must be multiples of 128";
+    if (a.ksplit && (a.batch != 1 || a.beta != 0.0 || a.Ct)) return "split-k: batch == 1, beta == 0, no Ct";
+    return nullptr;
+}
+
+int32_t abo_test_gemm_path(int32_t M, int32_t N, int32_t K, int32_t kmode, int32_t lower_only, int32_t batch, int32_t ksplit,
+                           int32_t mrows, int32_t in_place, int32_t* path) {
+    if (!path) return fail(ABO_EINVAL, "abo_test_gemm_path: null argument");
+    static double op[3];                       // three distinct addresses; never dereferenced
+    GemmArgs a{};
+    a.A = &op[0]; a.B = &op[1]; a.C = in_place ? &op[0] : &op[2];
+    a.M = M; a.N = N; a.K = K; a.kmode = kmode; a.lower_only = lower_only; a.batch = batch; a.alpha = 1.0; a.ksplit = ksplit; a.mrows = mrows;
+    if (const char* why = gemm_args_complaint(a)) return fail(ABO_EINVAL, "abo_test_gemm_path: %s", why);
+    *path = gemm_nt_path(a);
+    return ABO_OK;
+}
+
+int32_t abo_test_gemm_swz_map(int32_t T, int32_t G, int32_t Q, int32_t* ti, int32_t* tj) {
+    if (!ti || !tj) return fail(ABO_EINVAL, "abo_test_gemm_swz_map: null argument");
+    if (T < 1 || T > 4096 || G < 1 || Q < 0 || Q >= T * (T + 1) / 2) return fail(ABO_EINVAL, "abo_test_gemm_swz_map: 1 <= T <= 4096, G >= 1, 0 <= Q < T(T+1)/2");
+    int i = -1, j = -1;
+    gemm_swz_tile(T, G, Q, i, j);
+    *ti = i; *tj = j;
+    return ABO_OK;
+}
+
+int32_t abo_test_gemm_swz_q(int32_t tiles, int32_t L, int32_t* Q) {
+    if (!Q) return fail(ABO_EINVAL, "abo_test_gemm_swz_q: null argument");
+    if (tiles < 1 || L < 0 || L >= (tiles + 7) / 8 * 8) return fail(ABO_EINVAL, "abo_test_gemm_swz_q: tiles >= 1, 0 <= L < ceil(tiles / 8) * 8");
+    *Q = gemm_swz_q(L, tiles);
+    return ABO_OK;
+}
+
+int32_t abo_test_gemm_args(int32_t device, const double* A, const double* B, double* C, double* Ct, int64_t lda, int64_t ldb, int64_t ldc,
+                           int64_t ldct, int64_t sA, int64_t sB, int64_t sC, int64_t sCt, int32_t M, int32_t N, int32_t K, int32_t kmode,
+                           int32_t lower_only, int32_t batch, double alpha, double beta, int32_t ksplit, int32_t mrows, const int64_t* info,
+                           int32_t* path) {
+    if (!A || !B || !C || !path) return fail(ABO_EINVAL, "abo_test_gemm_args: null argument");
+    GemmArgs a{};
+    a.A = A; a.B = B; a.C = C; a.Ct = Ct; a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.ldct = ldct; a.sA = sA; a.sB = sB; a.sC = sC; a.sCt = sCt;
+    a.M = M; a.N = N; a.K = K; a.kmode = kmode; a.lower_only = lower_only; a.batch = batch; a.alpha = alpha; a.beta = beta; a.info = info;
+    a.ksplit = ksplit; a.mrows = mrows;
+    if (const char* why = gemm_args_complaint(a)) return fail(ABO_EINVAL, "abo_test_gemm_args: %s", why);
+    if ((lda & 1) || (ldb & 1) || lda < K || ldb < K || ldc < N || (Ct && ldct < M) || ((sA | sB) & 1) || sA < 0 || sB < 0 || sC < 0 || sCt < 0)
+        return fail(ABO_EINVAL, "abo_test_gemm_args: lda, ldb even and >= K, ldc >= N, ldct >= M, batch strides >= 0 (those of A and B even)");
+    const int p = gemm_nt_path(a);
+    if (p == GEMM_PATH_SKINNY && (kmode == K_A_LOWER || kmode == K_A_UPPER))
+        return fail(ABO_EINVAL, "abo_test_gemm_args: the skinny split-k kernel knows K_FULL, K_B_LOWER and K_B_UPPER only");
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(launch_gemm_nt(a, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    *path = p;
+    return ABO_OK;
+}
+
+int32_t abo_test_qei_pass(int32_t device, const double* A, int64_t lda, int32_t rows16, const double* B, int64_t ldb, int64_t nB, int32_t K,
+                          double alpha, double* C, int64_t ldc, int32_t kmode, int32_t ksplit, int64_t sC) {
+    if (!A || !B || !C) return fail(ABO_EINVAL, "abo_test_qei_pass: null argument");
+    if (lda < K || ldb < K || ldc < nB || sC < 0) return fail(ABO_EINVAL, "abo_test_qei_pass: lda, ldb >= K, ldc >= nB, sC >= 0");
+    HIPCHK(hipSetDevice(device));
+    const hipError_t e = launch_qei_pass(A, lda, rows16, B, ldb, nB, K, alpha, C, ldc, nullptr, kmode, ksplit, sC);
+    if (e == hipErrorInvalidValue) return fail(ABO_EINVAL, "abo_test_qei_pass: launch_qei_pass refused rows16 = %d, nB = %lld, K = %d, lda = %lld, ldb = %lld, kmode = %d, ksplit = %d",
+                                                rows16, (long long)nB, K, (long long)lda, (long long)ldb, kmode, ksplit);
+    HIPCHK(e);
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_splitk_reduce(int32_t device, const double* P, int64_t ldp, int64_t sP, int32_t nz, int32_t rows, int32_t cols, int32_t K,
+                               int32_t ksplit, int32_t kmode, double* out, int64_t ldo) {
+    if (!P || !out) return fail(ABO_EINVAL, "abo_test_splitk_reduce: null argument");
+    if (rows <= 0 || cols <= 0 || (cols & 1) || (ldp & 1) || (ldo & 1) || (sP & 1) || ldp < cols || ldo < cols || sP < 0 || nz < 1 || K <= 0 ||
+        ksplit <= 0 || ksplit % 128 || (int64_t)nz * ksplit < K)
+        return fail(ABO_EINVAL, "abo_test_splitk_reduce: rows > 0, cols > 0 and even, ldp / ldo / sP even, ldp, ldo >= cols, ksplit a multiple of 128, nz chunks covering K");
+    if (kmode != K_FULL && kmode != K_B_LOWER && kmode != K_B_UPPER) return fail(ABO_EINVAL, "abo_test_splitk_reduce: kmode must be K_FULL, K_B_LOWER or K_B_UPPER");
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(launch_splitk_reduce(P, ldp, sP, nz, rows, cols, K, ksplit, kmode, out, ldo, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_var_gemm(int32_t device, const double* W, int64_t ldw, int32_t Np, int32_t nvalid, const double* Kxz, int64_t ldk, int32_t Mc,
+                          double* partial, int64_t ldp, int32_t variant) {
+    if (!W || !Kxz || !partial) return fail(ABO_EINVAL, "abo_test_var_gemm: null argument");
+    if (Np <= 0 || Np % TB || Mc <= 0 || Mc % TB || nvalid < 0 || nvalid > Np || ldw < Np || ldk < Np || (ldw & 1) || (ldk & 1) || ldp < Mc)
+        return fail(ABO_EINVAL, "abo_test_var_gemm: Np and Mc multiples of 128, nvalid <= Np, ldw / ldk even and >= Np, ldp >= Mc");
+    if (variant != 0 && variant != 1) return fail(ABO_EINVAL, "abo_test_var_gemm: variant 0 (the launcher's rule) or 1 (the 128-row kernel)");
+    HIPCHK(hipSetDevice(device));
+    VarGemmArgs va{};
+    va.W = W; va.Kxz = Kxz; va.partial = partial; va.ldw = ldw; va.ldk = ldk; va.ldp = ldp; va.Np = Np; va.Mc = Mc; va.nvalid = nvalid;
+    HIPCHK(launch_var_gemm(va, nullptr, variant));
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
 #endif  // ABO_TEST_HOOKS
 
 }  // extern "C"

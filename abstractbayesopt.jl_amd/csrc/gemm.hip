@@ -206,27 +206,10 @@ __global__ void __launch_bounds__(256, 2) gemm_nt_kernel(GemmArgs p) {
         // takes the x-th eighth of the tile sequence, and the sequence runs through super-rows of G tile rows column by column — the
         // 64 workgroups an XCD holds at a time are a patch of G rows × 64/G columns (G = 4: 20 operand panels for 64 tiles),
         // where the row-major 2-D launch had every XCD touch every panel of 8 tile rows (its L2 held none of them until reuse).
-        const int L = blockIdx.x;
-        const int per = (p.swz + 7) >> 3;
-        const int Q = (L & 7) * per + (L >> 3);
+        // The map itself: gemm_swz_q / gemm_swz_tile (abo_kernels.h), shared with the host so that it is testable without a launch.
+        const int Q = gemm_swz_q((int)blockIdx.x, p.swz);
         if (Q >= p.swz) return;
-        const int T = p.M / BM, G = p.swz_g;
-        int g = (int)((sqrt(8.0 * (double)Q + 1.0) - 1.0) / (2.0 * G));        // super-row: G·g·(G·g+1)/2 tiles lie before it
-        while ((G * (g + 1)) * (G * (g + 1) + 1) / 2 <= Q) ++g;
-        while ((G * g) * (G * g + 1) / 2 > Q) --g;
-        int w = Q - (G * g) * (G * g + 1) / 2;
-        const int r0 = G * g;
-        const int R = min(G, T - r0);
-        if (w < R * (r0 + 1)) {                                              // full columns 0 … r0: R tiles each
-            tj = w / R;
-            ti = r0 + w - tj * R;
-        } else {                                                             // the triangle at the right end
-            w -= R * (r0 + 1);
-            int c = 1;
-            while (w >= R - c) { w -= R - c; ++c; }
-            tj = r0 + c;
-            ti = tj + w;
-        }
+        gemm_swz_tile(p.M / BM, p.swz_g, Q, ti, tj);
     }
     if (p.lower_only && tj > ti) return;
     int kbeg = 0, kend = p.K;
@@ -501,45 +484,58 @@ hipError_t launch_qei_pass(const double* A, int64_t lda, int rows16, const doubl
     return hipGetLastError();
 }
 
-hipError_t launch_gemm_nt(const GemmArgs& a, hipStream_t s) {
-    if (a.M <= 0 || a.N <= 0 || a.batch <= 0) return hipSuccess;
-    const int64_t Tm = a.M / BM, Tn = a.N / BN;
-    int64_t tiles = Tm * Tn;
-    if (a.lower_only) {                                              // tiles (ti, tj ≤ ti), tj < Tn
-        const int64_t q = Tm < Tn ? Tm : Tn;
-        tiles = q * (q + 1) / 2 + (Tm - q) * Tn;
+int gemm_nt_path(const GemmArgs& a) {
+    if (a.M <= 0 || a.N <= 0 || a.batch <= 0) return GEMM_PATH_NONE;
+    if (a.ksplit) {
+        if (a.batch != 1 || a.beta != 0.0 || a.ksplit % 128 != 0 || a.Ct) return GEMM_PATH_INVALID;
+        return a.mrows >= 16 && a.mrows <= 64 && a.mrows % 16 == 0 && a.M == BM ? GEMM_PATH_SKINNY : GEMM_PATH_SPLITK;
     }
-    tiles *= a.batch;
     const char* fe = getenv("ABO_GEMM_SMALL");                      // A/B runs and tests: 0 never, 1 always
     const int force = fe ? atoi(fe) : -1;
-    const bool small = a.ksplit ? false : (force >= 0 ? force == 1 : tiles <= 64);      // measured crossover: small ≈ tiles·K·1.7 ns, tiled ≈ 6 µs + K·0.11 µs
+    const bool small = force >= 0 ? force == 1 : gemm_nt_tiles(a) <= 64;      // measured crossover: small ≈ tiles·K·1.7 ns, tiled ≈ 6 µs + K·0.11 µs
     const bool in_place = a.C == a.A || a.C == a.B;
-    if (a.ksplit) {
-        if (a.batch != 1 || a.beta != 0.0 || a.ksplit % 128 != 0 || a.Ct) return hipErrorInvalidValue;
-        dim3 grid(a.N / BN, a.M / BM, (a.K + a.ksplit - 1) / a.ksplit);
-        if (a.mrows >= 16 && a.mrows <= 64 && a.mrows % 16 == 0 && a.M == BM) {
+    if (small && !in_place && a.K % 128 == 0) return GEMM_PATH_SMALL;
+    if (a.lower_only && a.kmode == K_FULL && a.M == a.N && a.batch == 1 && a.M / BM >= 16 && !getenv("ABO_GEMM_NO_SWIZZLE")) return GEMM_PATH_SWIZZLED;
+    return GEMM_PATH_TILED;
+}
+
+hipError_t launch_gemm_nt(const GemmArgs& a, hipStream_t s) {
+    switch (gemm_nt_path(a)) {
+        case GEMM_PATH_NONE: return hipSuccess;
+        case GEMM_PATH_INVALID: return hipErrorInvalidValue;
+        case GEMM_PATH_SKINNY: {
+            dim3 grid(a.N / BN, a.M / BM, (a.K + a.ksplit - 1) / a.ksplit);
             switch (a.mrows / 16) {
                 case 1: hipLaunchKernelGGL((gemm_skinny_kernel<1>), grid, dim3(256), 0, s, a); break;
                 case 2: hipLaunchKernelGGL((gemm_skinny_kernel<2>), grid, dim3(256), 0, s, a); break;
                 case 3: hipLaunchKernelGGL((gemm_skinny_kernel<3>), grid, dim3(256), 0, s, a); break;
                 default: hipLaunchKernelGGL((gemm_skinny_kernel<4>), grid, dim3(256), 0, s, a); break;
             }
-            return hipGetLastError();
+            break;
         }
-        hipLaunchKernelGGL(gemm_nt_kernel, grid, dim3(256), 0, s, a);
-        return hipGetLastError();
-    }
-    if (small && !in_place && a.K % 128 == 0) {
-        dim3 grid(a.N / 32, a.M / 32, a.batch);
-        hipLaunchKernelGGL(gemm_nt_small_kernel, grid, dim3(256), 0, s, a);
-    } else if (a.lower_only && a.kmode == K_FULL && a.M == a.N && a.batch == 1 && Tm >= 16 && !getenv("ABO_GEMM_NO_SWIZZLE")) {
-        GemmArgs b = a;
-        b.swz = (int)tiles;
-        b.swz_g = 4;
-        hipLaunchKernelGGL(gemm_nt_kernel, dim3((unsigned)(((tiles + 7) / 8) * 8)), dim3(256), 0, s, b);
-    } else {
-        dim3 grid(a.N / BN, a.M / BM, a.batch);
-        hipLaunchKernelGGL(gemm_nt_kernel, grid, dim3(256), 0, s, a);
+        case GEMM_PATH_SPLITK: {
+            dim3 grid(a.N / BN, a.M / BM, (a.K + a.ksplit - 1) / a.ksplit);
+            hipLaunchKernelGGL(gemm_nt_kernel, grid, dim3(256), 0, s, a);
+            break;
+        }
+        case GEMM_PATH_SMALL: {
+            dim3 grid(a.N / 32, a.M / 32, a.batch);
+            hipLaunchKernelGGL(gemm_nt_small_kernel, grid, dim3(256), 0, s, a);
+            break;
+        }
+        case GEMM_PATH_SWIZZLED: {
+            const int64_t tiles = gemm_nt_tiles(a);
+            GemmArgs b = a;
+            b.swz = (int)tiles;
+            b.swz_g = 4;
+            hipLaunchKernelGGL(gemm_nt_kernel, dim3((unsigned)(((tiles + 7) / 8) * 8)), dim3(256), 0, s, b);
+            break;
+        }
+        default: {
+            dim3 grid(a.N / BN, a.M / BM, a.batch);
+            hipLaunchKernelGGL(gemm_nt_kernel, grid, dim3(256), 0, s, a);
+            break;
+        }
     }
     return hipGetLastError();
 }
@@ -794,8 +790,8 @@ __global__ void __launch_bounds__(512, 2) var_gemm256s_kernel(VarGemmArgs p) {
     }
 }
 
-hipError_t launch_var_gemm(const VarGemmArgs& a, hipStream_t s) {
-    if (a.Np % BM2 == 0) {
+hipError_t launch_var_gemm(const VarGemmArgs& a, hipStream_t s, int variant) {
+    if (variant != 1 && a.Np % BM2 == 0) {
         const int tiles2 = (a.Np / BM2) * (a.Mc / BN);
         if (tiles2 <= 0) return hipSuccess;
         hipLaunchKernelGGL(var_gemm256s_kernel, dim3(tiles2), dim3(512), 0, s, a);

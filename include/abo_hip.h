@@ -854,6 +854,48 @@ int32_t abo_test_kappa(int32_t device, int32_t family, const double* d2, double*
 int32_t abo_test_gemm_nt(int32_t device, const double* A, const double* B, double* C, int32_t M,
                          int32_t N, int32_t K, int64_t lda, int64_t ldb, int64_t ldc, double alpha,
                          double beta);
+/* --- the fp64 MFMA GEMM family (csrc/gemm.hip), mode by mode ---
+ * kmode: 0 = K_FULL, 1 = K_A_LOWER (tile row ti sums k < (ti+1)·128), 2 = K_A_UPPER (k ≥ ti·128), 3 = K_B_LOWER (tile column tj sums
+ * k < (tj+1)·128), 4 = K_B_UPPER (k ≥ tj·128); every range clipped to K.
+ * Path ids: what launch_gemm_nt ran. */
+#define ABO_GEMM_PATH_TILED 0    /* gemm_nt_kernel, 2-D grid of 128×128 tiles × batch */
+#define ABO_GEMM_PATH_SWIZZLED 1 /* gemm_nt_kernel, 1-D XCD-aware launch over the lower tiles of a square SYRK */
+#define ABO_GEMM_PATH_SMALL 2    /* gemm_nt_small_kernel (at most 64 tiles, K a multiple of 128, C neither A nor B) */
+#define ABO_GEMM_PATH_SKINNY 3   /* split-k: gemm_skinny_kernel<mrows/16> (M = 128, mrows in {16, 32, 48, 64}) */
+#define ABO_GEMM_PATH_SPLITK 4   /* split-k: gemm_nt_kernel, one k chunk per grid z */
+/* abo_test_gemm_nt with every field of the launcher's argument block: C[b] = alpha·A[b]·B[b]ᵀ + beta·C[b] over the k range of `kmode`,
+ * Ct[b][j][i] = C[b][i][j] when Ct is given, batch b at element offsets b·sA, b·sB, b·sC, b·sCt; lower_only = 1 leaves the tiles with
+ * tj > ti alone; *info != 0 (device memory, may be null) leaves everything alone.  ksplit > 0 (a multiple of 128; batch 1, beta 0, no Ct):
+ * chunk z of the k range goes to the partial product C + z·sC, and a chunk outside a tile's range writes nothing; with M = 128 and mrows
+ * in {16, 32, 48, 64} only the first mrows rows of A and of every partial exist.  M, N multiples of 128; K a multiple of 16 (of 128
+ * under split-k); lda, ldb even.  *path = the ABO_GEMM_PATH_* that ran. */
+int32_t abo_test_gemm_args(int32_t device, const double* A, const double* B, double* C, double* Ct, int64_t lda, int64_t ldb, int64_t ldc,
+                           int64_t ldct, int64_t sA, int64_t sB, int64_t sC, int64_t sCt, int32_t M, int32_t N, int32_t K, int32_t kmode,
+                           int32_t lower_only, int32_t batch, double alpha, double beta, int32_t ksplit, int32_t mrows, const int64_t* info,
+                           int32_t* path);
+/* The launcher's choice alone (no GPU needed): *path for that shape; in_place = 1: C is one of the operands.  Honours ABO_GEMM_SMALL
+ * (0 never / 1 always the small kernel) and ABO_GEMM_NO_SWIZZLE as read at the time of the call. */
+int32_t abo_test_gemm_path(int32_t M, int32_t N, int32_t K, int32_t kmode, int32_t lower_only, int32_t batch, int32_t ksplit,
+                           int32_t mrows, int32_t in_place, int32_t* path);
+/* The swizzled launch's map in its two steps (no GPU needed): workgroup L of the padded 1-D grid of ⌈tiles/8⌉·8 → position *Q in the
+ * tile sequence (*Q ≥ tiles: the workgroup idles), and position Q < T(T+1)/2 → lower tile (*ti, *tj ≤ *ti) of a T×T tile grid walked in
+ * super-rows of G tile rows (production: G = 4). */
+int32_t abo_test_gemm_swz_q(int32_t tiles, int32_t L, int32_t* Q);
+int32_t abo_test_gemm_swz_map(int32_t T, int32_t G, int32_t Q, int32_t* ti, int32_t* tj);
+/* launch_qei_pass: C[z][r][j] = alpha·Σ_{k in chunk z ∩ range} A[r][k]·B[j][k], r < rows16, j < nB; row blocks of B are 64 wide and the
+ * triangular range of block tj is that of the 128-row block tj/2.  ksplit = 0: one chunk.  ABO_EINVAL, and no launch, for what the
+ * launcher refuses: rows16 not in {16, 32, 48, 64}, nB or K no multiple of 128, odd lda / ldb, a K_A_* kmode, ksplit no multiple of 128 */
+int32_t abo_test_qei_pass(int32_t device, const double* A, int64_t lda, int32_t rows16, const double* B, int64_t ldb, int64_t nB, int32_t K,
+                          double alpha, double* C, int64_t ldc, int32_t kmode, int32_t ksplit, int64_t sC);
+/* launch_splitk_reduce: out[r][c] = Σ_z P[z][r][c] over exactly the chunks z that intersect the k range of column tile c/128 under
+ * kmode (0, 3 or 4), in chunk order; the other chunks are not read */
+int32_t abo_test_splitk_reduce(int32_t device, const double* P, int64_t ldp, int64_t sP, int32_t nz, int32_t rows, int32_t cols, int32_t K,
+                               int32_t ksplit, int32_t kmode, double* out, int64_t ldo);
+/* launch_var_gemm: partial[tb][j] = Σ_{i in 128-row block tb, i < nvalid} (Σ_{k ≤ i} W[i][k]·Kxz[j][k])² on the fp64 matrix pipe, for
+ * a lower-triangular W.  variant 0 = the launcher's rule (Np a multiple of 256: the 256-row kernel, which reads nothing of the 16×16
+ * sub-tiles above the diagonal), 1 = the 128-row kernel whatever Np (it sums k < (tb+1)·128: the whole diagonal block is read) */
+int32_t abo_test_var_gemm(int32_t device, const double* W, int64_t ldw, int32_t Np, int32_t nvalid, const double* Kxz, int64_t ldk, int32_t Mc,
+                          double* partial, int64_t ldp, int32_t variant);
 #endif /* ABO_TEST_HOOKS */
 
 #ifdef __cplusplus
