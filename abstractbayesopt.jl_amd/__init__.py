@@ -11,7 +11,8 @@ from .domains import ContinuousDomain
 from . import gradient_gp as _g
 from .gradient_gp import (GradientNormUCB, HipGradientGP, gradConstMean, posterior_grad_cov, posterior_grad_mean,
                           posterior_grad_var)
-from .hyperparams import lengthscale_bounds, monte_carlo_fill_distance, nlml_and_grad, nlml_and_grad_ard, optimize_hyperparameters
+from .hyperparams import (lengthscale_bounds, loo_and_grad, monte_carlo_fill_distance, nlml_and_grad, nlml_and_grad_ard,
+                          optimize_hyperparameters)
 from .incremental import ResidentCandidates, append, greedy_qei, mc_qei
 from .multigpu import HipShardedGP, HipShardedGradientGP, ShardedCandidates
 from .kernels import (ApproxMatern52Kernel, ApproxMatern72Kernel, ConstMean, Kernel, Matern32Kernel, Matern52Kernel,
@@ -20,7 +21,7 @@ from . import surrogate as _s
 from .thompson import SamplePaths, max_value_samples, sample_paths, spectral_frequencies, thompson_batch, thompson_step
 from .surrogate import (AbstractSurrogate, ArdUnsupported, HipStandardGP, _get_minimum, _update_model_parameters,
                         ard_lengthscales, from_model_space, to_model_space,
-                        get_factor, get_kernel_constructor, get_lengthscale, get_mean_std, get_scale, mean_and_var,
+                        get_factor, get_kernel_constructor, get_lengthscale, get_mean_std, get_scale, leave_one_out, mean_and_var,
                         nlml, nlml_fitted, nlml_ls, posterior_mean, posterior_var, prep_input, prep_output,
                         rescale_model, set_default_contraction, std_y, training_data, unstandardized_mean_and_var)
 

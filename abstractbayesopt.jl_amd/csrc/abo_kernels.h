@@ -254,6 +254,41 @@ hipError_t launch_nlml_grad_ard(const NlmlGradArgs& a, double* out_ard, hipStrea
 // same reductions with dK/dlog(ell) given as a matrix D (gradient-enhanced GP: D comes from kgen with dlogell = 1):
 // out[0] = sum_{i,k<N} (Kinv[i][k] - alpha_i alpha_k) D[i][k]  (lower 128-tiles, strictly-lower ones counted twice), out[1..3] as above
 hipError_t launch_nlml_grad_matrix(const NlmlGradArgs& a, const double* D, int64_t ldd, hipStream_t s);
+// D[i][k] = sigma_f2·∂kappa/∂log ℓ(‖Xs_i − Xs_k‖²) for i, k < N, 0 elsewhere: the full symmetric Np × Np matrix (leading dimension ldd)
+// of an ordinary model (the dlogell path of launch_kgen is the gradient-enhanced one); closed forms q(d2)·d2, finite at d2 = 0
+hipError_t launch_dkdlogell(const double* Xs, int N, int Np, int dp, int family, double sigma_f2, double* D, int64_t ldd, hipStream_t s);
+
+// ---- leave-one-out cross-validation (loo.hip) -------------------------------------------------
+struct LooArgs {
+    const double* WT;      // [≥ N][ld] upper-triangular: row i holds column i of W = L⁻¹
+    const double* alpha;   // [≥ N]
+    const double* delta;   // [≥ N]  y − mean_c
+    double* mu;            // [N] or nullptr   y_i − alpha_i/B_ii,  B_ii = Σ_{i ≤ k < N} WT[i][k]²
+    double* var;           // [N] or nullptr   1/B_ii
+    double* lpd;           // [N] or nullptr   −½ log var − (y − mu)²/(2 var) − ½ log 2π
+    double* partial;       // [loo_diag_blocks(N)]
+    double* nlpl;          // [1]  −Σ_i lpd[i], fixed order
+    int64_t ld;
+    int N;
+    double mean_c;
+};
+int loo_diag_blocks(int N);
+hipError_t launch_loo_diag(const LooArgs& a, hipStream_t s);
+// B[i][j] = B[j][i] on the 128-tiles above the diagonal of the Np × Np matrix B (lower tiles valid on the way in)
+hipError_t launch_loo_mirror(double* B, int64_t ld, int Np, hipStream_t s);
+// out[0..3) = ∂nlpl/∂(log ℓ, log sigma_f2, log noise) from the rows of T = B·∂K/∂log ℓ and B = K̃⁻¹ (both complete, [Np][ld])
+struct LooGradArgs {
+    const double* T;
+    const double* B;
+    const double* alpha;   // [Np]
+    double* partial;       // [3·loo_grad_blocks(N)]
+    double* out;           // [3]
+    int64_t ld;
+    int N;
+    double noise;          // the noise the factor was built with
+};
+int loo_grad_blocks(int N);
+hipError_t launch_loo_grad_rows(const LooGradArgs& a, hipStream_t s);
 // test hook: out[i] = kappa(family, d2[i]) with the device math the generator uses
 hipError_t launch_kappa_test(int family, const double* d2, double* out, int64_t n, hipStream_t s);
 // K[i][i] += noise for i < N; K[i][i] = 1 for N ≤ i < Np (identity padding keeps the factor PD)

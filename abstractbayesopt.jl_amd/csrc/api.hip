@@ -356,6 +356,7 @@ struct abo_gp {
     std::vector<double> ap_x;          // the point a one-row append added, as the host handed it over (abo_cand_downdate matches it against the q-EI chain)
     double ap_s2v[MAX_P] = {0}, ap_betav[MAX_P] = {0};   // gradient-enhanced append: the same per appended row (p_out of them)
     DevBuf alpha, vext, tvec, T, info, scal;
+    DevBuf loo_T;                      // abo_loo_grad: T = K̃⁻¹·∂K/∂log ℓ (K̃⁻¹ itself sits in T, ∂K/∂log ℓ in Kxz)
     // host landing zone of the fit's scalars ({log det, δᵀα} and the LAPACK-style info): read back by one asynchronous copy at
     // the end of the fit's launches and looked at after the NEXT stream synchronisation — the fit's own (abo_fit) or, for
     // abo_fit_acq, the one behind the acquisition launches that were queued right behind the fit
@@ -401,7 +402,7 @@ struct abo_gp {
         DevBuf* all[] = {&alpha, &vext, &tvec, &T, &info, &scal, &Zdev, &Kxz, &partial, &mu_c, &mu_all, &var_all,
                          &score_all, &tk_keys0, &tk_keys1, &tk_idx0, &tk_idx1, &top_val, &top_idx,
                          &oz_WR, &oz_sexp, &oz_badr, &oz_KR, &oz_U, &oz_badc, &pr_ub, &pr_z, &pr_sc, &pr_sel, &pr_blk, &pr_tv, &pr_ti,
-                         &pr_mut, &pr_eps, &pr_nrm, &pr_ub2, &pr_mut2, &pr_eps2, &ystar, &oz_WRb, &oz_sexpb, &oz_badrb, &oz_delta};
+                         &pr_mut, &pr_eps, &pr_nrm, &pr_ub2, &pr_mut2, &pr_eps2, &ystar, &oz_WRb, &oz_sexpb, &oz_badrb, &oz_delta, &loo_T};
         for (DevBuf* b : all) b->dev = dev;
     }
 
@@ -409,7 +410,7 @@ struct abo_gp {
         DevBuf* all[] = {&alpha, &vext, &tvec, &T, &info, &scal, &Zdev, &Kxz, &partial, &mu_c, &mu_all, &var_all,
                          &score_all, &tk_keys0, &tk_keys1, &tk_idx0, &tk_idx1, &top_val, &top_idx,
                          &oz_WR, &oz_sexp, &oz_badr, &oz_KR, &oz_U, &oz_badc, &pr_ub, &pr_z, &pr_sc, &pr_sel, &pr_blk, &pr_tv, &pr_ti,
-                         &pr_mut, &pr_eps, &pr_nrm, &pr_ub2, &pr_mut2, &pr_eps2, &ystar, &oz_WRb, &oz_sexpb, &oz_badrb, &oz_delta};
+                         &pr_mut, &pr_eps, &pr_nrm, &pr_ub2, &pr_mut2, &pr_eps2, &ystar, &oz_WRb, &oz_sexpb, &oz_badrb, &oz_delta, &loo_T};
         for (DevBuf* b : all) b->release();
         oz_N = -1;
         oz_ctr_clean = nullptr;
@@ -2216,6 +2217,92 @@ int32_t abo_nlml_grad_ard(abo_gp* g, int32_t d, double* nlml, double* d_log_ell,
     if (g->from_append || g->st->max_live() != g->N)
         return fail(ABO_EINVAL, "abo_nlml_grad_ard needs a freshly fitted model (hyper-parameter search refits anyway)");
     return nlml_grad_impl(g, true, nlml, d_log_ell, d_log_sigma_f2, d_log_noise);
+}
+
+// what abo_loo and abo_loo_grad check alike, before any device work
+static int32_t loo_check(abo_gp* g, const char* who) {
+    if (!g) return fail(ABO_EINVAL, "%s: null handle", who);
+    if (!g->fitted) return fail(ABO_EINVAL, "surrogate is not conditioned on data yet (call abo_fit first)");
+    if (g->p_out > 1) return fail(ABO_EINVAL, "%s: leaving out one output row of a gradient-enhanced point is not leave-one-out", who);
+    return ABO_OK;
+}
+
+// abo_loo behind its argument checks, and the value of abo_loo_grad (one implementation: the same bits): the view's own N rows of the
+// triangle of WT, read once
+static int32_t loo_value_impl(abo_gp* g, double* mu, double* var, double* lpd, double* nlpl, int32_t out_space) {
+    HIPCHK(hipSetDevice(g->prm.device));
+    hipStream_t s = g->stream;
+    const int N = (int)g->N;
+    const bool host = out_space != ABO_DEVICE;
+    LooArgs a{};
+    a.WT = g->st->WT.as<double>(); a.ld = g->st->cap; a.alpha = g->alpha.as<double>(); a.delta = g->st->delta.as<double>();
+    a.N = N; a.mean_c = g->prm.mean_c;
+    const int nb = loo_diag_blocks(N);
+    HIPCHK(g->partial.ensure(sizeof(double) * (nb + 8)));
+    a.partial = g->partial.as<double>(); a.nlpl = a.partial + nb;          // the sum lands behind the partials
+    if (mu) { if (host) { HIPCHK(g->mu_all.ensure(sizeof(double) * N)); a.mu = g->mu_all.as<double>(); } else a.mu = mu; }
+    if (var) { if (host) { HIPCHK(g->var_all.ensure(sizeof(double) * N)); a.var = g->var_all.as<double>(); } else a.var = var; }
+    if (lpd) { if (host) { HIPCHK(g->score_all.ensure(sizeof(double) * N)); a.lpd = g->score_all.as<double>(); } else a.lpd = lpd; }
+    HIPCHK(launch_loo_diag(a, s));
+    if (host) {
+        if (mu) HIPCHK(hipMemcpyAsync(mu, a.mu, sizeof(double) * N, hipMemcpyDeviceToHost, s));
+        if (var) HIPCHK(hipMemcpyAsync(var, a.var, sizeof(double) * N, hipMemcpyDeviceToHost, s));
+        if (lpd) HIPCHK(hipMemcpyAsync(lpd, a.lpd, sizeof(double) * N, hipMemcpyDeviceToHost, s));
+    }
+    double v = 0.0;
+    if (nlpl) HIPCHK(hipMemcpyAsync(&v, a.nlpl, sizeof v, hipMemcpyDeviceToHost, s));
+    HIPCHK(wait_stream(s));
+    if (nlpl) *nlpl = v;
+    return ABO_OK;
+}
+
+int32_t abo_loo(abo_gp* g, double* mu, double* var, double* lpd, double* nlpl, int32_t out_space) {
+    if (const int32_t rc = loo_check(g, "abo_loo")) return rc;
+    if (out_space != ABO_HOST && out_space != ABO_DEVICE) return fail(ABO_EINVAL, "abo_loo: out_space %d is neither ABO_HOST nor ABO_DEVICE", out_space);
+    return loo_value_impl(g, mu, var, lpd, nlpl, out_space);
+}
+
+int32_t abo_loo_grad(abo_gp* g, double* nlpl, double* d_log_ell, double* d_log_sigma_f2, double* d_log_noise) {
+    if (const int32_t rc = loo_check(g, "abo_loo_grad")) return rc;
+    if (g->from_append || g->st->max_live() != g->N)
+        return fail(ABO_EINVAL, "abo_loo_grad needs a freshly fitted model (hyper-parameter search refits anyway)");
+    if (const int32_t rc = loo_value_impl(g, nullptr, nullptr, nullptr, nlpl, ABO_HOST)) return rc;
+    if (!d_log_ell && !d_log_sigma_f2 && !d_log_noise) return ABO_OK;
+    hipStream_t s = g->stream;
+    const int64_t Np = g->Np, ld = g->st->cap;
+    const int N = (int)g->N;
+    HIPCHK(g->T.ensure(sizeof(double) * Np * Np));
+    HIPCHK(g->Kxz.ensure(sizeof(double) * Np * Np));
+    HIPCHK(g->loo_T.ensure(sizeof(double) * Np * Np));
+    const int nb = loo_grad_blocks(N);
+    HIPCHK(g->partial.ensure(sizeof(double) * (3 * (size_t)nb + 8)));
+    // B = K̃⁻¹ = WᵀW on the lower 128-tiles exactly as nlml_grad_impl forms it (N³/3 flop), mirrored into the upper tiles: the full
+    // product would read the tiles of WT below the diagonal, which nothing defines, and cost twice the flop.  A fresh fit's padding
+    // rows N … Np are the identity the factorisation left there, so B is finite throughout and D's zero padding removes them from T
+    GemmArgs a{};
+    a.A = g->st->WT.as<double>(); a.lda = ld; a.B = g->st->WT.as<double>(); a.ldb = ld;
+    a.C = g->T.as<double>(); a.ldc = Np; a.M = (int)Np; a.N = (int)Np; a.K = (int)Np;
+    a.kmode = K_A_UPPER; a.lower_only = 1; a.batch = 1; a.alpha = 1.0; a.beta = 0.0;
+    HIPCHK(launch_gemm_nt(a, s));
+    HIPCHK(launch_loo_mirror(g->T.as<double>(), Np, (int)Np, s));
+    // D = ∂K/∂log ℓ, T = B·D (D symmetric: the NT product is the product wanted)
+    HIPCHK(launch_dkdlogell(g->st->Xs.as<double>(), N, (int)Np, g->dp, g->prm.family, g->prm.sigma_f2, g->Kxz.as<double>(), Np, s));
+    GemmArgs b{};
+    b.A = g->T.as<double>(); b.lda = Np; b.B = g->Kxz.as<double>(); b.ldb = Np;
+    b.C = g->loo_T.as<double>(); b.ldc = Np; b.M = (int)Np; b.N = (int)Np; b.K = (int)Np;
+    b.kmode = K_FULL; b.lower_only = 0; b.batch = 1; b.alpha = 1.0; b.beta = 0.0;
+    HIPCHK(launch_gemm_nt(b, s));
+    LooGradArgs ga{};
+    ga.T = g->loo_T.as<double>(); ga.B = g->T.as<double>(); ga.alpha = g->alpha.as<double>(); ga.partial = g->partial.as<double>();
+    ga.out = ga.partial + 3 * (size_t)nb; ga.ld = Np; ga.N = N; ga.noise = g->st->noise_used;
+    HIPCHK(launch_loo_grad_rows(ga, s));
+    double o[3];
+    HIPCHK(hipMemcpyAsync(o, ga.out, sizeof o, hipMemcpyDeviceToHost, s));
+    HIPCHK(wait_stream(s));
+    if (d_log_ell) *d_log_ell = o[0];
+    if (d_log_sigma_f2) *d_log_sigma_f2 = o[1];
+    if (d_log_noise) *d_log_noise = ga.noise == 0.0 ? 0.0 : o[2];
+    return ABO_OK;
 }
 
 // host vector of a gradient-enhanced model: the library's point-major order v[i·p + q] → the ABI's by-outputs order v[q·N + i]

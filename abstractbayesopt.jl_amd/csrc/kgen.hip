@@ -273,6 +273,42 @@ __device__ __forceinline__ double dkappa_dlogell_over_d2(double d2) {
     }
 }
 
+// D = ∂K/∂log ℓ of an ordinary model as a matrix, D[i][k] = σ_f²·q(d2_ik)·d2_ik (zero for i or k ≥ N): the operand of the T = K̃⁻¹·D
+// product behind the leave-one-out gradient (loo.hip).  A lane owns a column k, a wave four rows: 512-byte row stores; the differences
+// are formed directly and summed in coordinate order on both sides of the diagonal, so D is symmetric bit for bit.
+template <int FAM>
+__global__ void __launch_bounds__(256) dkdlogell_kernel(const double* __restrict__ Xs, int N, int dp, double sigma_f2, double* __restrict__ D,
+                                                        int64_t ldd) {
+    const int k = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int i0 = blockIdx.y * JT + (threadIdx.x >> 6) * 4;
+    const double* xk = Xs + (int64_t)k * dp;
+    const double* xi = Xs + (int64_t)i0 * dp;
+    double d2[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int c = 0; c < dp; ++c) {
+        const double x = xk[c];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const double e = x - xi[(int64_t)r * dp + c];
+            d2[r] = fma(e, e, d2[r]);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+        D[(int64_t)(i0 + r) * ldd + k] = (i0 + r < N && k < N) ? sigma_f2 * (dkappa_dlogell_over_d2<FAM>(d2[r]) * d2[r]) : 0.0;
+}
+
+hipError_t launch_dkdlogell(const double* Xs, int N, int Np, int dp, int family, double sigma_f2, double* D, int64_t ldd, hipStream_t s) {
+    const dim3 grid(Np / 64, Np / JT), block(256);
+    switch (family) {
+        case ABO_KERNEL_SE: hipLaunchKernelGGL((dkdlogell_kernel<ABO_KERNEL_SE>), grid, block, 0, s, Xs, N, dp, sigma_f2, D, ldd); break;
+        case ABO_KERNEL_MATERN52: hipLaunchKernelGGL((dkdlogell_kernel<ABO_KERNEL_MATERN52>), grid, block, 0, s, Xs, N, dp, sigma_f2, D, ldd); break;
+        case ABO_KERNEL_MATERN72: hipLaunchKernelGGL((dkdlogell_kernel<ABO_KERNEL_MATERN72>), grid, block, 0, s, Xs, N, dp, sigma_f2, D, ldd); break;
+        case ABO_KERNEL_MATERN32: hipLaunchKernelGGL((dkdlogell_kernel<ABO_KERNEL_MATERN32>), grid, block, 0, s, Xs, N, dp, sigma_f2, D, ldd); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
 // partial[block][c] = σ_f²·Σ over the block's pairs of w_ij·(Kinv[i][j] − α_i α_j)·q(d2_ij)·e_c²: the d traces of the ARD gradient in
 // the one sweep nlml_grad_kernel makes — same rows per workgroup, same lane ↔ column map, same tiles, weights and masks.  The squared
 // distance is summed first (q needs it whole), then the differences are formed again from the registers and the LDS broadcast and

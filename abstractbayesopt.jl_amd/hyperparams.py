@@ -30,6 +30,19 @@ def nlml_and_grad(model: HipStandardGP, params, xs, ys):
     return v.value, np.array([d1.value, d2.value])
 
 
+def loo_and_grad(model: HipStandardGP, params, xs, ys):
+    """(nlpl, [∂/∂log ℓ, ∂/∂log scale]) at params = [log ℓ, log scale]: the negative leave-one-out log pseudo-likelihood (Rasmussen &
+    Williams §5.4.2) and its analytic gradient from ONE refit + abo_loo_grad — the alternative objective of the hyper-parameter search
+    when the kernel family is misspecified and NLML over-fits.  Same parameter convention as nlml_and_grad."""
+    log_ell, log_scale = params
+    k = math.exp(log_scale) * with_lengthscale(get_kernel_constructor(model), math.exp(log_ell))
+    g = HipStandardGP(k, model.noise_var, mean=model.mean, device=model.device, jitter=model.jitter, contraction=model.contraction)
+    fitted = update(g, xs, ys)
+    v, d1, d2 = C.c_double(), C.c_double(), C.c_double()
+    _lib.check(_lib.lib().abo_loo_grad(fitted._require(), C.byref(v), C.byref(d1), C.byref(d2), None))
+    return v.value, np.array([d1.value, d2.value])
+
+
 def nlml_and_grad_ard(model: HipStandardGP, params, xs, ys):
     """(nlml, [∂/∂log ℓ_1 … ∂/∂log ℓ_d, ∂/∂log scale]) at params = [log ℓ_1 … log ℓ_d, log scale] for the kernel with one length scale
     per coordinate: ONE refit on the coordinates divided by ℓ_c (ell = 1 in the library) and one abo_nlml_grad_ard, whose d traces
@@ -118,7 +131,8 @@ def lengthscale_bounds(X_train, domain, min_frac: float = 0.1, max_frac: float =
 
 
 def optimize_hyperparameters(model: HipStandardGP, x_train, y_train, old_params, scale_std: float = 1.0,
-                             length_scale_only: bool = False, num_restarts: int = 1, domain=None, rng=None, ard: bool = False):
+                             length_scale_only: bool = False, num_restarts: int = 1, domain=None, rng=None, ard: bool = False,
+                             objective: str = "nlml"):
     """optimize_hyperparameters (bayesian_opt.jl:196-328): box bounds (:214-242), starting point clamped
     into them (:247), `num_restarts − 1` extra uniform starts in log space (:263-266), the best converged
     run wins (:275-300), the old model is returned if every restart fails (:302-304), otherwise a NEW
@@ -127,8 +141,17 @@ def optimize_hyperparameters(model: HipStandardGP, x_train, y_train, old_params,
     ard=True searches one length scale per coordinate (the generalisation the reference leaves as a TODO, bayesian_opt.jl:193):
     old_params = [log ℓ_1 … log ℓ_d, log scale], or the isotropic [log ℓ, log scale] whose ℓ is replicated; the bounds are
     lengthscale_bounds' per-dimension vectors; value and all d + 1 partials come from one refit (nlml_and_grad_ard); the result is a
-    new un-conditioned ARD model.  Same L-BFGS-B options, restarts and failure handling."""
+    new un-conditioned ARD model.  Same L-BFGS-B options, restarts and failure handling.
+
+    objective="loo" minimises the negative leave-one-out log pseudo-likelihood (loo_and_grad) instead of the NLML: the same bounds,
+    starts, restarts and failure handling.  A single-device HipStandardGP with one length scale only: with ard=True it raises (the
+    per-coordinate LOO gradient would cost d products)."""
     from scipy.optimize import minimize
+    if objective not in ("nlml", "loo"):
+        raise ValueError(f"optimize_hyperparameters: objective must be \"nlml\" or \"loo\", got {objective!r}")
+    if objective == "loo" and ard:
+        raise ValueError("optimize_hyperparameters(objective=\"loo\") has no ARD form: the per-coordinate leave-one-out gradient is "
+                         "not implemented (ard=True serves objective=\"nlml\" only)")
     rng = np.random.default_rng() if rng is None else rng
     if ard:
         return _optimize_hyperparameters_ard(model, x_train, y_train, old_params, scale_std, length_scale_only, num_restarts, domain,
@@ -153,12 +176,14 @@ def optimize_hyperparameters(model: HipStandardGP, x_train, y_train, old_params,
         start_full = np.clip(old, lower + eps2, upper - eps2)
     from . import gradient_gp as G
     grad_model = isinstance(model, G.HipGradientGP)
+    if objective == "loo" and (grad_model or hasattr(model, "devices")):
+        raise TypeError("optimize_hyperparameters(objective=\"loo\") serves a single-device HipStandardGP only")
     if grad_model:                                   # GradientGP: xs stay points, ys stay (N, p) rows; update() packs them
         xs, ys = x_train, y_train
         value_and_grad, rebuild = G.nlml_and_grad, G._update_model_parameters
     else:
         xs, ys = prep_input(model, x_train), prep_output(model, y_train)
-        value_and_grad, rebuild = nlml_and_grad, _update_model_parameters
+        value_and_grad, rebuild = (loo_and_grad if objective == "loo" else nlml_and_grad), _update_model_parameters
 
     def obj(p):
         full = [p[0], start_full[1]] if length_scale_only else [p[0], p[1]]

@@ -393,6 +393,19 @@ def nlml(model: HipStandardGP, params, xs, ys) -> float:
     return nlml_fitted(update(g, xs, ys))
 
 
+def leave_one_out(model: HipStandardGP):
+    """(mu, var, lpd, nlpl): the leave-one-out predictive mean and variance of every observed target (noise included), its log
+    predictive density under them, and nlpl = −Σ lpd — from the fitted model's resident L⁻¹ in one pass (abo_loo; no refit).
+    NumPy arrays of the model's N.  An ARD model is served as it is: no coordinates cross the call."""
+    h = model._require()
+    n, d = C.c_int64(), C.c_int32()
+    _lib.check(_lib.lib().abo_get_n(h, C.byref(n), C.byref(d)))
+    mu, var, lpd = (np.empty(n.value, dtype=np.float64) for _ in range(3))
+    v = C.c_double()
+    _lib.check(_lib.lib().abo_loo(h, mu.ctypes.data, var.ctypes.data, lpd.ctypes.data, C.byref(v), HOST))
+    return mu, var, lpd, v.value
+
+
 def nlml_ls(model: HipStandardGP, log_ell, log_scale, xs, ys) -> float:
     """nlml_ls (StandardGP.jl:133-149)."""
     return nlml(model, (log_ell, log_scale), xs, ys)

@@ -48,7 +48,7 @@ extern "C" {
                                   abo_paths_attach, abo_paths_detach, abo_paths_top, abo_paths_values, abo_paths_append_stats_get
                                   (struct abo_paths_append_stats is new); ABO_ACQ_LOGEI (kind 5 in every entry point that takes a kind
                                   or an abo_acq_term, and in the pruned top-k selection); ABO_ACQ_MES and abo_score_mes, abo_acq_mes,
-                                  abo_cand_acq_mes, abo_refine_mes, abo_optimize_acquisition_mes; abo_get_prune_levels */
+                                  abo_cand_acq_mes, abo_refine_mes, abo_optimize_acquisition_mes; abo_get_prune_levels; abo_loo, abo_loo_grad */
 
 /* status codes */
 enum {
@@ -652,6 +652,24 @@ int32_t abo_nlml_grad(abo_gp* gp, double* nlml, double* d_log_ell, double* d_log
  * ABO_EINVAL; the arguments are checked before any device work.  abo_timings.nlml_kinv_ms / nlml_trace_ms are filled as by
  * abo_nlml_grad.  Any output may be NULL; d_log_ell holds d values.  Two calls on the same handle return the same bits. */
 int32_t abo_nlml_grad_ard(abo_gp* gp, int32_t d, double* nlml, double* d_log_ell, double* d_log_sigma_f2, double* d_log_noise);
+
+/* added within ABI 7: leave-one-out cross-validation (Rasmussen & Williams §5.4.2) from the resident W = L⁻¹ — no refit, no K⁻¹ product.
+ * LOO predictive distribution of the N observed targets under the fitted model (noise included: it predicts y_i, not f(x_i)):
+ *   B_ii = Σ_{k≥i} W_ki² (W = L⁻¹),  mu[i] = y_i − alpha_i/B_ii,  var[i] = 1/B_ii,
+ *   lpd[i] = −½ log var[i] − (y_i − mu[i])²/(2 var[i]) − ½ log 2π,   *nlpl = −Σ_i lpd[i].
+ * mu, var, lpd: N values in out_space (ABO_HOST / ABO_DEVICE), each may be NULL; nlpl: one host double, may be NULL.
+ * O(N²): one read of the triangle of L⁻ᵀ.  Works on appended views as well as fresh fits (the sums stop at the view's own N: a parent
+ * keeps returning its own values after a child was appended); the noise is the one the factor was built with, y_i the target as
+ * handed over.  A gradient-enhanced handle is ABO_EINVAL (leaving out one output row of a point is not LOO), as are a null or an
+ * unfitted handle; the arguments are checked before any device work.  Two calls on the same handle return the same bits. */
+int32_t abo_loo(abo_gp* gp, double* mu, double* var, double* lpd, double* nlpl, int32_t out_space);
+
+/* nlpl and its gradient with respect to (log ell, log sigma_f2, log noise); any output may be NULL.
+ *   ∂(−nlpl)/∂θ = Σ_i [α_i r_i − ½(1 + α_i²/B_ii) s_i]/B_ii,  r = B (∂K/∂θ) α,  s_i = [B (∂K/∂θ) B]_ii,  B = K⁻¹ (all of it: the lower
+ * 128-tiles of WᵀW on the fp64 MFMA GEMM, mirrored), ∂K/∂log ell generated as a matrix and multiplied once (one full N³ product);
+ * the sigma_f2 and noise partials take no product (∂K = K − noise·I and noise·I).  d_log_noise is exactly 0 when the factor was built
+ * without noise.  nlpl is abo_loo's bit for bit.  Needs a freshly fitted handle (not an appended view), as abo_nlml_grad does. */
+int32_t abo_loo_grad(abo_gp* gp, double* nlpl, double* d_log_ell, double* d_log_sigma_f2, double* d_log_noise);
 
 /* --- introspection (tests) ----------------------------------------------------------------------
  * L (N×N row-major, strictly-upper part zero), alpha (N), Linv = L⁻¹ (N×N row-major); any may be

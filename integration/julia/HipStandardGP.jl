@@ -580,6 +580,9 @@ include("LogExpectedImprovement.jl")
 # max-value entropy search (ABO_ACQ_MES): the type, its samples from the paths above, and the abo_*_mes calls
 include("MaxValueEntropySearch.jl")
 
+# leave-one-out cross-validation (abo_loo, abo_loo_grad): leave_one_out and loo_and_grad
+include("LeaveOneOut.jl")
+
 # path s takes its best index not taken by paths 1 … s − 1 (idx: k × q orderings, 0 = no candidate)
 function _distinct_picks(idx::AbstractMatrix{Int64})
     picks = Int64[]
