@@ -22,8 +22,8 @@ from .thompson import SamplePaths, max_value_samples, sample_paths, spectral_fre
 from .surrogate import (AbstractSurrogate, ArdUnsupported, HipStandardGP, _get_minimum, _update_model_parameters,
                         ard_lengthscales, from_model_space, to_model_space,
                         get_factor, get_kernel_constructor, get_lengthscale, get_mean_std, get_scale, leave_one_out, mean_and_var,
-                        nlml, nlml_fitted, nlml_ls, posterior_mean, posterior_var, prep_input, prep_output,
-                        rescale_model, set_default_contraction, std_y, training_data, unstandardized_mean_and_var)
+                        mean_and_cov, nlml, nlml_fitted, nlml_ls, posterior_cov, posterior_mean, posterior_var, prep_input, prep_output,
+                        rescale_model, sample_joint, set_default_contraction, std_y, training_data, unstandardized_mean_and_var)
 
 StandardGP = HipStandardGP   # drop-in aliases
 GradientGP = HipGradientGP

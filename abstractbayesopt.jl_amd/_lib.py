@@ -26,7 +26,7 @@ EXPORTS = ["abo_create", "abo_set_contraction", "abo_create_grad", "abo_predict_
            "abo_paths_create", "abo_paths_destroy", "abo_paths_eval", "abo_paths_eval_cand", "abo_paths_stats_get",
            "abo_paths_append", "abo_paths_attach", "abo_paths_detach", "abo_paths_top", "abo_paths_values", "abo_paths_append_stats_get",
            "abo_score_mes", "abo_acq_mes", "abo_cand_acq_mes", "abo_refine_mes", "abo_optimize_acquisition_mes",
-           "abo_loo", "abo_loo_grad"]
+           "abo_loo", "abo_loo_grad", "abo_predict_cov"]
 TEST_EXPORTS = ["abo_test_gemm_nt", "abo_test_kappa", "abo_test_oz_plan", "abo_test_oz_contract", "abo_test_acq_grad",
                 "abo_test_acq_grad_terms", "abo_test_prune_plan", "abo_test_prune_force", "abo_test_prune_levels", "abo_test_prune_plan_levels", "abo_test_prune_bounds", "abo_test_prune_mean",
                 "abo_test_kappa_tail", "abo_test_prune_bound_moduli", "abo_test_prune_bound_plan", "abo_test_oz_contract_bound", "abo_test_acq_partials", "abo_test_mes_partials", "abo_test_acq_grad_mes",
@@ -178,7 +178,8 @@ def lib():
     L.abo_nlml_grad_ard.argtypes = [vp, i32, C.POINTER(f64), C.POINTER(f64), C.POINTER(f64), C.POINTER(f64)]
     L.abo_loo.argtypes = [vp, vp, vp, vp, C.POINTER(f64), i32]
     L.abo_loo_grad.argtypes = [vp, C.POINTER(f64), C.POINTER(f64), C.POINTER(f64), C.POINTER(f64)]
-    L.abo_lhs.argtypes = [i32, i64, i32, vp, vp, C.c_uint64, i64, i64, vp]
+    L.abo_predict_cov.argtypes = [vp, vp, i64, vp, i64, i32, i32, vp, vp, vp, i32]
+    L.abo_lhs.argtypes =[i32, i64, i32, vp, vp, C.c_uint64, i64, i64, vp]
     L.abo_score.argtypes = [i32, vp, vp, i64, i32, f64, f64, vp]
     L.abo_fill_distance.argtypes = [i32, vp, i64, i32, i32, vp, i64, i32, C.POINTER(f64)]
     L.abo_get_factor.argtypes = [vp, vp, vp, vp]

@@ -289,6 +289,16 @@ struct LooGradArgs {
 };
 int loo_grad_blocks(int N);
 hipError_t launch_loo_grad_rows(const LooGradArgs& a, hipStream_t s);
+
+// ---- joint posterior covariance between point sets (cov.hip) ----------------------------------
+// C[i][j] = sigma_f2·kappa(‖As_i − Bs_j‖²) for i < Ma, j < Mb and 0 in the padding of the pad128(Ma) × pad128(Mb) block C (leading
+// dimension ldc); As / Bs: the points scaled by 1/ell, zero padded to [pad128(M)][dp] (launch_scale_points).  Differences formed
+// directly and summed in coordinate order: As == Bs gives a block that is symmetric bit for bit with exactly sigma_f2 on its
+// diagonal.  sym = 1 (As == Bs): only the 128-tiles with tj ≤ ti are written.
+hipError_t launch_cov_prior(const double* As, const double* Bs, int Ma, int Mb, int dp, int family, double sigma_f2, int sym, double* C,
+                            int64_t ldc, hipStream_t s);
+// out[i·Mb + j] = C[i][j] for i < Ma, j < Mb; sym = 1: + 1e-18 on the diagonal (abo_predict's latent-variance jitter)
+hipError_t launch_cov_pack(const double* C, int64_t ldc, int Ma, int Mb, int sym, double* out, hipStream_t s);
 // test hook: out[i] = kappa(family, d2[i]) with the device math the generator uses
 hipError_t launch_kappa_test(int family, const double* d2, double* out, int64_t n, hipStream_t s);
 // K[i][i] += noise for i < N; K[i][i] = 1 for N ≤ i < Np (identity padding keeps the factor PD)

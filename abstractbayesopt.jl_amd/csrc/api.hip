@@ -357,6 +357,7 @@ struct abo_gp {
     double ap_s2v[MAX_P] = {0}, ap_betav[MAX_P] = {0};   // gradient-enhanced append: the same per appended row (p_out of them)
     DevBuf alpha, vext, tvec, T, info, scal;
     DevBuf loo_T;                      // abo_loo_grad: T = K̃⁻¹·∂K/∂log ℓ (K̃⁻¹ itself sits in T, ∂K/∂log ℓ in Kxz)
+    DevBuf cov_Zs, cov_V, cov_C;       // abo_predict_cov: the scaled points of both sets, V_a / V_b = K_ZX·L⁻ᵀ, the padded covariance block
     // host landing zone of the fit's scalars ({log det, δᵀα} and the LAPACK-style info): read back by one asynchronous copy at
     // the end of the fit's launches and looked at after the NEXT stream synchronisation — the fit's own (abo_fit) or, for
     // abo_fit_acq, the one behind the acquisition launches that were queued right behind the fit
@@ -402,7 +403,7 @@ struct abo_gp {
         DevBuf* all[] = {&alpha, &vext, &tvec, &T, &info, &scal, &Zdev, &Kxz, &partial, &mu_c, &mu_all, &var_all,
                          &score_all, &tk_keys0, &tk_keys1, &tk_idx0, &tk_idx1, &top_val, &top_idx,
                          &oz_WR, &oz_sexp, &oz_badr, &oz_KR, &oz_U, &oz_badc, &pr_ub, &pr_z, &pr_sc, &pr_sel, &pr_blk, &pr_tv, &pr_ti,
-                         &pr_mut, &pr_eps, &pr_nrm, &pr_ub2, &pr_mut2, &pr_eps2, &ystar, &oz_WRb, &oz_sexpb, &oz_badrb, &oz_delta, &loo_T};
+                         &pr_mut, &pr_eps, &pr_nrm, &pr_ub2, &pr_mut2, &pr_eps2, &ystar, &oz_WRb, &oz_sexpb, &oz_badrb, &oz_delta, &loo_T, &cov_Zs, &cov_V, &cov_C};
         for (DevBuf* b : all) b->dev = dev;
     }
 
@@ -410,7 +411,7 @@ struct abo_gp {
         DevBuf* all[] = {&alpha, &vext, &tvec, &T, &info, &scal, &Zdev, &Kxz, &partial, &mu_c, &mu_all, &var_all,
                          &score_all, &tk_keys0, &tk_keys1, &tk_idx0, &tk_idx1, &top_val, &top_idx,
                          &oz_WR, &oz_sexp, &oz_badr, &oz_KR, &oz_U, &oz_badc, &pr_ub, &pr_z, &pr_sc, &pr_sel, &pr_blk, &pr_tv, &pr_ti,
-                         &pr_mut, &pr_eps, &pr_nrm, &pr_ub2, &pr_mut2, &pr_eps2, &ystar, &oz_WRb, &oz_sexpb, &oz_badrb, &oz_delta, &loo_T};
+                         &pr_mut, &pr_eps, &pr_nrm, &pr_ub2, &pr_mut2, &pr_eps2, &ystar, &oz_WRb, &oz_sexpb, &oz_badrb, &oz_delta, &loo_T, &cov_Zs, &cov_V, &cov_C};
         for (DevBuf* b : all) b->release();
         oz_N = -1;
         oz_ctr_clean = nullptr;
@@ -2302,6 +2303,100 @@ int32_t abo_loo_grad(abo_gp* g, double* nlpl, double* d_log_ell, double* d_log_s
     if (d_log_ell) *d_log_ell = o[0];
     if (d_log_sigma_f2) *d_log_sigma_f2 = o[1];
     if (d_log_noise) *d_log_noise = ga.noise == 0.0 ? 0.0 : o[2];
+    return ABO_OK;
+}
+
+// Joint posterior covariance between two point sets (include/abo_hip.h).  Per set: K_ZX from the generator (the mean falls out of the
+// same pass: abo_predict's bits), V = K_ZX·L⁻ᵀ on the fp64 GEMM against the lower-triangular W (k ≤ i: half the product), its columns
+// ≥ N zeroed — rows ≥ N of shared factor storage may hold a discarded appended branch, and a 128-tile of W reaches past the view's N.
+// Then the prior block (cov.hip), the product subtracted in place (C = −V_a·V_bᵀ + C), and the compact copy-out.  Zb == NULL: the lower
+// 128-tiles only, mirrored.  Always the fp64 engine: the int8-residue contraction squares one operand, a signed cross product is outside
+// its error analysis.
+constexpr int64_t COV_MAX_POINTS = 8192;
+int32_t abo_predict_cov(abo_gp* g, const double* Za, int64_t Ma, const double* Zb, int64_t Mb, int32_t d, int32_t z_space, double* mu_a,
+                        double* mu_b, double* cov, int32_t out_space) {
+    if (!g) return fail(ABO_EINVAL, "abo_predict_cov: null handle");
+    if (!g->fitted) return fail(ABO_EINVAL, "surrogate is not conditioned on data yet (call abo_fit first)");
+    if (g->p_out > 1)
+        return fail(ABO_EINVAL, "abo_predict_cov: a gradient-enhanced model has p outputs per point (abo_predict_grad_cov gives the block of one point)");
+    if (d != g->d) return fail(ABO_EDIM, "DimensionMismatch: abo_predict_cov with d = %d, model dimension %d", d, g->d);
+    if ((z_space != ABO_HOST && z_space != ABO_DEVICE) || (out_space != ABO_HOST && out_space != ABO_DEVICE))
+        return fail(ABO_EINVAL, "abo_predict_cov: z_space %d / out_space %d is neither ABO_HOST nor ABO_DEVICE", z_space, out_space);
+    if (Ma < 1 || Ma > COV_MAX_POINTS) return fail(ABO_EINVAL, "abo_predict_cov: Ma = %lld outside 1..%lld", (long long)Ma, (long long)COV_MAX_POINTS);
+    if (!Za) return fail(ABO_EINVAL, "abo_predict_cov: Za is NULL");
+    const bool sym = Zb == nullptr;
+    if (sym) {
+        if (Mb != 0 && Mb != Ma) return fail(ABO_EINVAL, "abo_predict_cov: Zb is NULL (the symmetric form), Mb = %lld is neither 0 nor Ma = %lld", (long long)Mb, (long long)Ma);
+        if (mu_b) return fail(ABO_EINVAL, "abo_predict_cov: Zb is NULL (the symmetric form) but mu_b is given; the means are mu_a");
+        Mb = Ma;
+    } else if (Mb < 1 || Mb > COV_MAX_POINTS) {
+        return fail(ABO_EINVAL, "abo_predict_cov: Mb = %lld outside 1..%lld", (long long)Mb, (long long)COV_MAX_POINTS);
+    }
+    if (!mu_a && !mu_b && !cov) return ABO_OK;
+    HIPCHK(hipSetDevice(g->prm.device));
+    hipStream_t s = g->stream;
+    const int64_t Np = g->Np, ld = g->st->cap;
+    const int N = (int)g->N, dp = g->dp;
+    const int64_t Map = pad_up(Ma, TB), Mbp = pad_up(Mb, TB);
+    const int nsets = sym ? 1 : 2;
+    const int64_t Ms[2] = {Ma, Mb}, Mps[2] = {Map, Mbp};
+    const double* Zin[2] = {Za, Zb};
+    const bool host_out = out_space == ABO_HOST;
+    // every workspace before the first launch: a buffer that grew between two launches would go back to the pool with work queued on it
+    if (z_space == ABO_HOST) HIPCHK(g->Zdev.ensure(sizeof(double) * (size_t)(Ma + (sym ? 0 : Mb)) * d));
+    HIPCHK(g->mu_all.ensure(sizeof(double) * (size_t)(Map + Mbp)));
+    if (cov) {
+        const size_t kx = (size_t)(Map > Mbp ? Map : Mbp) * Np, pk = host_out ? (size_t)Ma * Mb : 0;    // K_ZX of one set, later the compact block
+        HIPCHK(g->Kxz.ensure(sizeof(double) * (kx > pk ? kx : pk)));
+        HIPCHK(g->cov_Zs.ensure(sizeof(double) * (size_t)(Map + (sym ? 0 : Mbp)) * dp));
+        HIPCHK(g->cov_V.ensure(sizeof(double) * (size_t)(Map + (sym ? 0 : Mbp)) * Np));
+        HIPCHK(g->cov_C.ensure(sizeof(double) * (size_t)Map * Mbp));
+    }
+    double* Vset[2] = {g->cov_V.as<double>(), g->cov_V.as<double>() + (cov ? Map * Np : 0)};
+    double* Zsset[2] = {g->cov_Zs.as<double>(), g->cov_Zs.as<double>() + (cov ? Map * dp : 0)};
+    double* muset[2] = {g->mu_all.as<double>(), g->mu_all.as<double>() + Map};
+    double* const mu_out[2] = {mu_a, mu_b};
+    for (int q = 0; q < nsets; ++q) {
+        if (!cov && !mu_out[q]) continue;
+        const double* Zd = Zin[q];
+        if (z_space == ABO_HOST) {
+            double* stage = g->Zdev.as<double>() + (q ? Ma * d : 0);
+            HIPCHK(hipMemcpyAsync(stage, Zin[q], sizeof(double) * (size_t)Ms[q] * d, hipMemcpyHostToDevice, s));
+            Zd = stage;
+        }
+        KgenArgs ka{};
+        ka.Xs = g->st->Xs.as<double>(); ka.Z = Zd; ka.alpha = g->alpha.as<double>(); ka.Kout = cov ? g->Kxz.as<double>() : nullptr;
+        ka.mu = muset[q]; ka.ldk = Np; ka.M = Ms[q]; ka.j0 = 0; ka.Mc = (int)Mps[q]; ka.N = (int)g->npts;
+        ka.Np = (int)Np; ka.d = g->d; ka.dp = dp; ka.family = g->prm.family; ka.s = 1.0 / g->prm.ell;
+        ka.sigma_f2 = g->prm.sigma_f2; ka.mean_c = g->prm.mean_c; ka.mean_vec[0] = g->mean_vec[0];
+        HIPCHK(launch_kgen(ka, s));
+        if (!cov) continue;
+        HIPCHK(launch_scale_points(Zd, Zsset[q], (int)Ms[q], (int)Mps[q], g->d, dp, 1.0 / g->prm.ell, s));
+        GemmArgs a{};               // V[j][i] = Σ_{k ≤ i} Kzx[j][k]·W[i][k] = (L⁻¹k(X, z_j))[i]; padded rows j ≥ M are zero as those of Kzx are
+        a.A = g->Kxz.as<double>(); a.lda = Np; a.B = g->st->W.as<double>(); a.ldb = ld;
+        a.C = Vset[q]; a.ldc = Np; a.M = (int)Mps[q]; a.N = (int)Np; a.K = (int)Np;
+        a.kmode = K_B_LOWER; a.batch = 1; a.alpha = 1.0; a.beta = 0.0;
+        HIPCHK(launch_gemm_nt(a, s));
+        HIPCHK(launch_qei_zero_tail(Vset[q], Np, N, (int)Np, (int)Mps[q], s));
+    }
+    if (cov) {
+        double* Cp = g->cov_C.as<double>();
+        HIPCHK(launch_cov_prior(Zsset[0], Zsset[sym ? 0 : 1], (int)Ma, (int)Mb, dp, g->prm.family, g->prm.sigma_f2, sym ? 1 : 0, Cp, Mbp, s));
+        GemmArgs b{};               // C −= V_a·V_bᵀ
+        b.A = Vset[0]; b.lda = Np; b.B = Vset[sym ? 0 : 1]; b.ldb = Np; b.C = Cp; b.ldc = Mbp;
+        b.M = (int)Map; b.N = (int)Mbp; b.K = (int)Np; b.kmode = K_FULL; b.lower_only = sym ? 1 : 0; b.batch = 1; b.alpha = -1.0; b.beta = 1.0;
+        HIPCHK(launch_gemm_nt(b, s));
+        if (sym) HIPCHK(launch_loo_mirror(Cp, Mbp, (int)Map, s));
+        double* packed = host_out ? g->Kxz.as<double>() : cov;
+        HIPCHK(launch_cov_pack(Cp, Mbp, (int)Ma, (int)Mb, sym ? 1 : 0, packed, s));
+        if (host_out) HIPCHK(hipMemcpyAsync(cov, packed, sizeof(double) * (size_t)Ma * Mb, hipMemcpyDeviceToHost, s));
+    }
+    for (int q = 0; q < nsets; ++q) {
+        if (!mu_out[q]) continue;
+        const int32_t rc = copy_out(mu_out[q], muset[q], sizeof(double) * (size_t)Ms[q], out_space, s);
+        if (rc) return rc;
+    }
+    HIPCHK(wait_stream(s));
     return ABO_OK;
 }
 

@@ -152,6 +152,7 @@ class HipStandardGP(AbstractSurrogate):
         # off = always the refit, the reference's arithmetic
         self.incremental_update = bool(incremental_update)
         self.update_path = None   # what the update that made this model ran: "shared" / "appended" / "refit"
+        self._d = None            # input dimension of the data the model is conditioned on (set by update; None: ask the library)
         if device is None:
             device = _current_device()
         self.device = int(device)
@@ -180,6 +181,7 @@ class HipStandardGP(AbstractSurrogate):
         m.contraction = getattr(self, "contraction", None)
         m.incremental_update = getattr(self, "incremental_update", False)
         m.update_path = getattr(self, "update_path", None)
+        m._d = getattr(self, "_d", None)
         m._h = handle
         return m
 
@@ -300,7 +302,7 @@ def update(model: HipStandardGP, xs, ys) -> HipStandardGP:
         if getattr(model, "contraction", None) is not None:
             _lib.check(L.abo_set_contraction(h.ptr, *parse_contraction(model.contraction)))
         del xkeep, ykeep
-        return _with_path(model._clone(h), path.value)
+        return _with_path(model._clone(h), path.value, d)
     _lib.check(L.abo_create(C.byref(prm), C.byref(hp)))
     h = _Handle(hp.value)
     if getattr(model, "contraction", None) is not None:
@@ -308,11 +310,13 @@ def update(model: HipStandardGP, xs, ys) -> HipStandardGP:
     st = L.abo_fit(h.ptr, xp, n, d, yp, xspace, C.byref(info))
     _lib.check(st, info.value)
     del xkeep, ykeep
-    return _with_path(model._clone(h), _lib.UPDATE_REFIT)
+    return _with_path(model._clone(h), _lib.UPDATE_REFIT, d)
 
 
-def _with_path(model, path: int):
+def _with_path(model, path: int, d=None):
     model.update_path = _lib.UPDATE_PATHS[path]
+    if d is not None:
+        model._d = int(d)
     return model
 
 
@@ -362,6 +366,102 @@ def unstandardized_mean_and_var(model: HipStandardGP, xs, params):
     mu, sigma = params
     m, v = mean_and_var(model, xs)
     return m * sigma + mu, v * sigma ** 2
+
+
+# ---- joint posterior covariance (abo_predict_cov) ------------------------------------------------------
+COV_MAX_POINTS = 8192
+
+
+def _cov_model(model, what: str):
+    """the models abo_predict_cov serves: a single-device HipStandardGP — refused on the host, before anything is staged"""
+    if hasattr(model, "devices"):
+        raise TypeError(f"{what}: a sharded model (HipShardedGP) is not supported: the factor is spread over its devices; "
+                        "use a single-device HipStandardGP")
+    if hasattr(model, "p"):
+        raise TypeError(f"{what}: a gradient-enhanced model (HipGradientGP) has p outputs per point; posterior_grad_cov gives the "
+                        "p × p block of one point")
+    if not isinstance(model, HipStandardGP):
+        raise TypeError(f"{what} needs a HipStandardGP, not {type(model).__name__}")
+
+
+def _cov_points(model, x, name: str):
+    if np.isscalar(x):
+        x = [float(x)]
+    p, m, d, space, keep = as_points(to_model_space(model, x))
+    want = getattr(model, "_d", None)
+    if want is not None and d != want:
+        raise _lib.DimensionMismatch(f"DimensionMismatch: {name} has dimension {d}, model dimension {want}")
+    if not 1 <= m <= COV_MAX_POINTS:
+        raise ValueError(f"{name} holds {m} points; abo_predict_cov takes 1 to {COV_MAX_POINTS} per set")
+    return p, m, d, space, keep
+
+
+def _predict_cov(model, xa, xb, want_mu: bool, what: str):
+    """(mu_a, cov) through one abo_predict_cov; xb None: the symmetric form.  Host inputs give NumPy arrays, tensors on the model's GPU
+    give tensors there."""
+    _cov_model(model, what)
+    pa, ma, d, space, keep_a = _cov_points(model, xa, "xa")
+    pb, mb, keep_b = None, ma, None
+    if xb is not None:
+        pb, mb, db, space_b, keep_b = _cov_points(model, xb, "xb")
+        if db != d:
+            raise _lib.DimensionMismatch(f"DimensionMismatch: xa has dimension {d}, xb has dimension {db}")
+        if space_b != space:
+            raise ValueError("xa and xb must both be host arrays or both be tensors on the model's GPU")
+    h = model._require()
+    if space == DEVICE:
+        import torch
+        cov = torch.empty((ma, mb), dtype=torch.float64, device=keep_a.device)
+        mu = torch.empty(ma, dtype=torch.float64, device=keep_a.device) if want_mu else None
+        st = _lib.lib().abo_predict_cov(h, pa, ma, pb, mb if xb is not None else 0, d, DEVICE, mu.data_ptr() if want_mu else None, None,
+                                        cov.data_ptr(), DEVICE)
+    else:
+        cov = np.empty((ma, mb), dtype=np.float64)
+        mu = np.empty(ma, dtype=np.float64) if want_mu else None
+        st = _lib.lib().abo_predict_cov(h, pa, ma, pb, mb if xb is not None else 0, d, HOST, mu.ctypes.data if want_mu else None, None,
+                                        cov.ctypes.data, HOST)
+    _lib.check(st)
+    del keep_a, keep_b
+    return mu, cov
+
+
+def posterior_cov(model: HipStandardGP, xa, xb=None):
+    """[upstream AbstractGPs] cov(model.gpx(xa)) and cov(model.gpx(xa), model.gpx(xb)): the (Ma, Mb) joint latent posterior covariance
+    (no observation noise).  xb None: the symmetric form — symmetric bit for bit, its diagonal posterior_var's (with the 1e-18).
+    1 to 8192 points per set.  An ARD model is served through `to_model_space`; a covariance needs no back-scaling."""
+    return _predict_cov(model, xa, xb, False, "posterior_cov")[1]
+
+
+def mean_and_cov(model: HipStandardGP, x):
+    """[upstream AbstractGPs] mean_and_cov(model.gpx(x)) → (mu, cov) from one call."""
+    return _predict_cov(model, x, None, True, "mean_and_cov")
+
+
+def sample_joint(model: HipStandardGP, x, n: int, rng=None, jitter=None):
+    """[upstream AbstractGPs] rand(model.gpx(x), n), transposed: (n, M) exact draws of the latent posterior at the M points x —
+    mu + L·ξ with L the host Cholesky factor of cov + jitter·I (an M × M factorisation: host work by design).  jitter None: the ladder
+    1e-12·σ_f² … 1e-6·σ_f², × 10 per failed factorisation, then PosDefException; a number: that jitter alone.  rng: a
+    numpy.random.Generator (or a seed)."""
+    n = int(n)
+    if n < 0:
+        raise ValueError("sample_joint: n must be non-negative")
+    mu, cov = mean_and_cov(model, x)
+    if _is_torch(cov):
+        mu, cov = mu.cpu().numpy(), cov.cpu().numpy()
+    sf2 = float(model.kernel.scale)
+    ladder = [float(jitter)] if jitter is not None else [sf2 * 10.0 ** e for e in range(-12, -5)]
+    m = cov.shape[0]
+    for j in ladder:
+        try:
+            chol = np.linalg.cholesky(cov + j * np.eye(m))
+        except np.linalg.LinAlgError:
+            continue
+        if not np.all(np.isfinite(chol)):
+            continue
+        rng = rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)
+        return mu[None, :] + rng.standard_normal((n, m)) @ chol.T
+    raise _lib.PosDefException(0, f"sample_joint: the {m} × {m} posterior covariance is not positive definite with a jitter of up to "
+                                  f"{ladder[-1]:.3e}")
 
 
 # ---- NLML ----------------------------------------------------------------------------------------

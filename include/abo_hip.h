@@ -48,7 +48,8 @@ extern "C" {
                                   abo_paths_attach, abo_paths_detach, abo_paths_top, abo_paths_values, abo_paths_append_stats_get
                                   (struct abo_paths_append_stats is new); ABO_ACQ_LOGEI (kind 5 in every entry point that takes a kind
                                   or an abo_acq_term, and in the pruned top-k selection); ABO_ACQ_MES and abo_score_mes, abo_acq_mes,
-                                  abo_cand_acq_mes, abo_refine_mes, abo_optimize_acquisition_mes; abo_get_prune_levels; abo_loo, abo_loo_grad */
+                                  abo_cand_acq_mes, abo_refine_mes, abo_optimize_acquisition_mes; abo_get_prune_levels; abo_loo, abo_loo_grad;
+                                  abo_predict_cov */
 
 /* status codes */
 enum {
@@ -670,6 +671,25 @@ int32_t abo_loo(abo_gp* gp, double* mu, double* var, double* lpd, double* nlpl, 
  * the sigma_f2 and noise partials take no product (∂K = K − noise·I and noise·I).  d_log_noise is exactly 0 when the factor was built
  * without noise.  nlpl is abo_loo's bit for bit.  Needs a freshly fitted handle (not an appended view), as abo_nlml_grad does. */
 int32_t abo_loo_grad(abo_gp* gp, double* nlpl, double* d_log_ell, double* d_log_sigma_f2, double* d_log_noise);
+
+/* added within ABI 7: joint posterior covariance between two point sets — cov(gpx(Za), gpx(Zb)) and mean_and_cov of AbstractGPs (the
+ * reference itself calls cov(model.gpx(…)) in posterior_grad_cov, GradientGP.jl:966-971):
+ *   cov[i][j] = sigma_f2·kappa(‖za_i − zb_j‖/ell) − Σ_k V_a[k][i]·V_b[k][j],   V = L⁻¹K_XZ,
+ * row-major Ma × Mb, the LATENT covariance (no observation noise: abo_predict's convention); mu_a (Ma) and mu_b (Mb) are abo_predict's
+ * means, bit for bit.  mu_a, mu_b and cov may each be NULL.  Za / Zb in z_space, the outputs in out_space (ABO_HOST / ABO_DEVICE).
+ * Zb == NULL is the symmetric form cov(Za, Za): Mb must be 0 or Ma and mu_b NULL (ABO_EINVAL otherwise); the result is symmetric bit for
+ * bit (the lower 128-tiles are computed — half the flop — and mirrored) and its diagonal carries abo_predict's + 1e-18.  The rectangular
+ * form with Zb = Za agrees with it to rounding and carries no jitter.
+ * 1 ≤ Ma, Mb ≤ 8192; d must be the model's (ABO_EDIM); a null, an unfitted or a gradient-enhanced handle is ABO_EINVAL (its per-point
+ * block is abo_predict_grad_cov's); every argument is checked before any device work.
+ * The call ALWAYS runs on the fp64 MFMA kernels, whatever abo_set_contraction says: the int8-residue engine contracts the squares of
+ * one operand (the column norms of V), and its error analysis — row scales against the L1 norm of each row of L⁻¹, a non-negative
+ * sum — does not cover the signed cross products V_aᵀV_b.  The same bits under either engine setting, and on every call.
+ * Works on appended views and on a parent after a child was appended: the columns of V beyond the view's own N are zeroed before the
+ * product (rows ≥ N of shared factor storage may hold a discarded branch).  Cost: (Ma + Mb)·N² flop for the V's (half of that skipped
+ * in the triangle) and 2·Ma·Mb·N for the product; workspace (Ma + Mb)·N + Ma·Mb doubles (padded to 128), cached on the handle. */
+int32_t abo_predict_cov(abo_gp* gp, const double* Za, int64_t Ma, const double* Zb, int64_t Mb, int32_t d, int32_t z_space, double* mu_a,
+                        double* mu_b, double* cov, int32_t out_space);
 
 /* --- introspection (tests) ----------------------------------------------------------------------
  * L (N×N row-major, strictly-upper part zero), alpha (N), Linv = L⁻¹ (N×N row-major); any may be

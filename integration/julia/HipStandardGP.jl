@@ -583,6 +583,9 @@ include("MaxValueEntropySearch.jl")
 # leave-one-out cross-validation (abo_loo, abo_loo_grad): leave_one_out and loo_and_grad
 include("LeaveOneOut.jl")
 
+# joint posterior covariance between point sets (abo_predict_cov): posterior_cov and mean_and_cov
+include("PosteriorCov.jl")
+
 # path s takes its best index not taken by paths 1 … s − 1 (idx: k × q orderings, 0 = no candidate)
 function _distinct_picks(idx::AbstractMatrix{Int64})
     picks = Int64[]
