@@ -31,7 +31,7 @@ TEST_EXPORTS = ["abo_test_gemm_nt", "abo_test_kappa", "abo_test_oz_plan", "abo_t
                 "abo_test_acq_grad_terms", "abo_test_prune_plan", "abo_test_prune_force", "abo_test_prune_levels", "abo_test_prune_plan_levels", "abo_test_prune_bounds", "abo_test_prune_mean",
                 "abo_test_kappa_tail", "abo_test_prune_bound_moduli", "abo_test_prune_bound_plan", "abo_test_oz_contract_bound", "abo_test_acq_partials", "abo_test_mes_partials", "abo_test_acq_grad_mes",
                 "abo_test_gemm_args", "abo_test_gemm_path", "abo_test_gemm_swz_q", "abo_test_gemm_swz_map", "abo_test_qei_pass", "abo_test_splitk_reduce",
-                "abo_test_var_gemm"]
+                "abo_test_var_gemm", "abo_test_kgen", "abo_test_cand_newcol"]
 # what launch_gemm_nt ran, as abo_test_gemm_args / abo_test_gemm_path report it (include/abo_hip.h: ABO_GEMM_PATH_*)
 GEMM_PATH_TILED, GEMM_PATH_SWIZZLED, GEMM_PATH_SMALL, GEMM_PATH_SKINNY, GEMM_PATH_SPLITK = range(5)
 K_FULL, K_A_LOWER, K_A_UPPER, K_B_LOWER, K_B_UPPER = range(5)
@@ -108,6 +108,16 @@ class AboRefineOpts(C.Structure):
 class AboAcqTerm(C.Structure):
     """one term of a weighted-sum objective (include/abo_hip.h: abo_acq_term)"""
     _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("p0", C.c_double), ("best_y", C.c_double), ("weight", C.c_double)]
+
+
+class AboTestKgenArgs(C.Structure):
+    """every field of the generator's argument block, for abo_test_kgen (include/abo_hip.h: abo_test_kgen_args; test build only)"""
+    _fields_ = [(n, C.c_void_p) for n in ("Xs", "Z", "alpha", "Kout", "mu")] + [(n, C.c_int64) for n in ("ldk", "M", "j0")] + \
+               [(n, C.c_int32) for n in ("Mc", "N", "Np", "d", "dp", "family")] + [("s", C.c_double), ("sigma_f2", C.c_double),
+                                                                                  ("mean_vec", C.c_void_p)] + \
+               [(n, C.c_int32) for n in ("pt", "pc", "point_major", "dlogell", "rvalid", "n_mean")] + \
+               [("res", C.c_void_p), ("res_ld", C.c_int64), ("res_plane", C.c_int64), ("res_bad", C.c_void_p)] + \
+               [(n, C.c_int32) for n in ("res_n", "res_sK", "res_ktg", "res_kmax")]
 
 
 class PosDefException(Exception):
@@ -218,6 +228,8 @@ def lib():
         L.abo_test_qei_pass.argtypes = [i32, vp, i64, i32, vp, i64, i64, i32, f64, vp, i64, i32, i32, i64]
         L.abo_test_splitk_reduce.argtypes = [i32, vp, i64, i64, i32, i32, i32, i32, i32, i32, vp, i64]
         L.abo_test_var_gemm.argtypes = [i32, vp, i64, i32, i32, vp, i64, i32, vp, i64, i32]
+        L.abo_test_kgen.argtypes = [i32, C.POINTER(AboTestKgenArgs)]
+        L.abo_test_cand_newcol.argtypes = [i32, vp, vp, vp, i64, i64, i32, i32, i32, i32, i32, i32, i32, f64, f64]
     L.abo_mgpu_create.argtypes = [C.POINTER(AboParams), i32, C.POINTER(i32), C.POINTER(vp)]
     L.abo_mgpu_create_grad.argtypes = [C.POINTER(AboParams), i32, vp, i32, C.POINTER(i32), C.POINTER(vp)]
     L.abo_mgpu_append_grad.argtypes = [vp, vp, i32, vp, C.POINTER(i64), vp]

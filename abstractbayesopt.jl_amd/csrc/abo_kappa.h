@@ -35,7 +35,8 @@ __device__ __forceinline__ double exp_nonpos(double x) {
 }
 
 // sqrt(x) for finite x ≥ 0: v_rsq_f64 seed + two coupled Newton steps (Goldschmidt form) + one residual
-// correction; x below 1e-290 (kernel value indistinguishable from κ(0)) returns 0 instead of 0·inf.
+// correction; x below 1e-290 (kernel value indistinguishable from κ(0)) returns 0 instead of 0·inf.  NaN stays NaN (the compare is
+// false for it and g is NaN already): a candidate with a non-finite coordinate must not come out with a finite kernel value.
 __device__ __forceinline__ double sqrt_pos(double x) {
     const double y = __builtin_amdgcn_rsq(x);
     double g = x * y, h = 0.5 * y;
@@ -47,7 +48,7 @@ __device__ __forceinline__ double sqrt_pos(double x) {
     h = fma(h, r, h);
     const double e = fma(-g, g, x);
     g = fma(e, h, g);
-    return x > 1e-290 ? g : 0.0;
+    return x <= 1e-290 ? 0.0 : g;
 }
 
 // ---- the μ-only tail of the pruned selection's bound pass (kgen_tail.hip) ----------------------------------------------------------

@@ -4470,6 +4470,40 @@ int32_t abo_test_var_gemm(int32_t device, const double* W, int64_t ldw, int32_t 
     HIPCHK(wait_stream(nullptr));
     return ABO_OK;
 }
+
+// launch_kgen with every field of KgenArgs as the caller gives it: no decision about shape, engine or dispatch is taken here
+int32_t abo_test_kgen(int32_t device, const abo_test_kgen_args* t) {
+    if (!t || !t->Xs || !t->Z) return fail(ABO_EINVAL, "abo_test_kgen: null argument");
+    if (t->n_mean < 0 || t->n_mean > MAX_P || (t->n_mean > 0 && !t->mean_vec)) return fail(ABO_EINVAL, "abo_test_kgen: n_mean in [0, %d] with mean_vec given", MAX_P);
+    KgenArgs a{};
+    a.Xs = t->Xs; a.Z = t->Z; a.alpha = t->alpha; a.Kout = t->Kout; a.mu = t->mu; a.ldk = t->ldk; a.M = t->M; a.j0 = t->j0; a.Mc = t->Mc;
+    a.N = t->N; a.Np = t->Np; a.d = t->d; a.dp = t->dp; a.family = t->family; a.s = t->s; a.sigma_f2 = t->sigma_f2;
+    for (int q = 0; q < t->n_mean; ++q) a.mean_vec[q] = t->mean_vec[q];
+    a.mean_c = t->n_mean > 0 ? t->mean_vec[0] : 0.0;
+    a.pt = t->pt; a.pc = t->pc; a.point_major = t->point_major; a.dlogell = t->dlogell; a.rvalid = t->rvalid;
+    a.res = t->res; a.res_ld = t->res_ld; a.res_plane = t->res_plane; a.res_bad = t->res_bad; a.res_n = t->res_n; a.res_sK = t->res_sK;
+    a.res_ktg = t->res_ktg; a.res_kmax = t->res_kmax;
+    HIPCHK(hipSetDevice(device));
+    const hipError_t e = launch_kgen(a, nullptr);
+    if (e == hipErrorInvalidValue)
+        return fail(ABO_EINVAL, "abo_test_kgen: launch_kgen refused family = %d, dp = %d, pt = %d, dlogell = %d, res_n = %d, res_kmax = %d, Np = %d",
+                    a.family, a.dp, a.pt, a.dlogell, a.res ? a.res_n : 0, a.res_kmax, a.Np);
+    HIPCHK(e);
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_cand_newcol(int32_t device, const double* Xs, const double* Z, double* Kzx, int64_t ld, int64_t M, int32_t col, int32_t grad,
+                             int32_t pt, int32_t q, int32_t d, int32_t dp, int32_t family, double s, double sigma_f2) {
+    if (!Xs || !Z || !Kzx) return fail(ABO_EINVAL, "abo_test_cand_newcol: null argument");
+    HIPCHK(hipSetDevice(device));
+    const hipError_t e = grad ? launch_cand_newcol_grad(Xs, Z, Kzx, ld, M, col, pt, q, d, dp, family, s, sigma_f2, nullptr)
+                              : launch_cand_newcol(Xs, Z, Kzx, ld, M, col, d, dp, family, s, sigma_f2, nullptr);
+    if (e == hipErrorInvalidValue) return fail(ABO_EINVAL, "abo_test_cand_newcol: the launcher refused family = %d (grad = %d)", family, grad);
+    HIPCHK(e);
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
 #endif  // ABO_TEST_HOOKS
 
 }  // extern "C"

@@ -527,13 +527,14 @@ __global__ void __launch_bounds__(256) kgen_wide_kernel(KgenArgs p) {
 template <int FAM>
 static hipError_t launch_fam(const KgenArgs& a, hipStream_t s) {
     dim3 grid(a.Mc / JT), block(256);
+    // planes the fused output is not built for (the wide kernel writes none: d > 32 included): the caller was told not to ask
+    if (a.res && !kgen_writes_residues(a, a.res_n)) return hipErrorInvalidValue;
     if (a.dp > 32) {
         if (a.dp % SLAB) return hipErrorInvalidValue;
         hipLaunchKernelGGL((kgen_wide_kernel<FAM>), grid, block, 0, s, a);
         return hipGetLastError();
     }
     if (a.res) {
-        if (!kgen_writes_residues(a, a.res_n)) return hipErrorInvalidValue;      // the caller was told not to ask
         if (a.res_n == 8) return launch_kgen_res_short8(a, s);                    // the bound pass's short plans: partial launch only
         if (a.res_n == 9) return launch_kgen_res_short9(a, s);
         if (a.res_n == 10) return launch_kgen_res_short10(a, s);

@@ -934,6 +934,29 @@ int32_t abo_test_splitk_reduce(int32_t device, const double* P, int64_t ldp, int
  * sub-tiles above the diagonal), 1 = the 128-row kernel whatever Np (it sums k < (tb+1)·128: the whole diagonal block is read) */
 int32_t abo_test_var_gemm(int32_t device, const double* W, int64_t ldw, int32_t Np, int32_t nvalid, const double* Kxz, int64_t ldk, int32_t Mc,
                           double* partial, int64_t ldp, int32_t variant);
+/* --- the kernel-matrix generators (csrc/kgen_core.h, kgen_grad_core.h, kgen.hip), instantiation by instantiation ---
+ * Every field of the launcher's argument block (csrc/abo_kernels.h: KgenArgs), in this fixed layout; all pointers DEVICE memory except
+ * mean_vec (host, n_mean ≤ 129 entries: the prior mean per output, the first one the mean of an ordinary model; n_mean = 0: zeros).
+ * Xs is ALREADY scaled by s and zero padded [Np][dp] (a gradient-enhanced model: one row per training POINT, Np pads N·pt factor
+ * rows); Z are the raw candidates [M][d].  Kout, mu, alpha, res may each be null as in KgenArgs. */
+typedef struct abo_test_kgen_args {
+    const double* Xs; const double* Z; const double* alpha; double* Kout; double* mu;
+    int64_t ldk, M, j0;
+    int32_t Mc, N, Np, d, dp, family;
+    double s, sigma_f2;
+    const double* mean_vec;
+    int32_t pt, pc, point_major, dlogell, rvalid, n_mean;
+    int8_t* res; int64_t res_ld, res_plane; int32_t* res_bad;
+    int32_t res_n, res_sK, res_ktg, res_kmax;
+} abo_test_kgen_args;
+/* launch_kgen on the null stream with exactly these fields (no decision about shape, engine or dispatch is taken by the hook);
+ * ABO_EINVAL, and no launch, where launch_kgen refuses: an unknown family, a dp outside the dispatch table, planes for a shape or a
+ * moduli count the fused output is not built for, a res_kmax that is no multiple of 128 or exceeds Np */
+int32_t abo_test_kgen(int32_t device, const abo_test_kgen_args* args);
+/* launch_cand_newcol (grad = 0: column `col` of a resident K_ZX, Xs row `col`) or launch_cand_newcol_grad (grad = 1: training row
+ * (point pt, output q) against the function value of every candidate, written to column `col`) */
+int32_t abo_test_cand_newcol(int32_t device, const double* Xs, const double* Z, double* Kzx, int64_t ld, int64_t M, int32_t col, int32_t grad,
+                             int32_t pt, int32_t q, int32_t d, int32_t dp, int32_t family, double s, double sigma_f2);
 #endif /* ABO_TEST_HOOKS */
 
 #ifdef __cplusplus

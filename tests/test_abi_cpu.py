@@ -47,6 +47,9 @@ def test_shipped_library_exports_the_documented_surface_and_nothing_else():
     abo_syms = sorted(s for s in syms if s.startswith("abo_"))
     assert abo_syms == shipped, (sorted(set(abo_syms) - set(shipped)), sorted(set(shipped) - set(abo_syms)))
     assert not any(h in syms for h in hooks)
+    # the generators' pass-through hooks among them: declared, in the test build, absent from the shipped library
+    for h in ("abo_test_kgen", "abo_test_cand_newcol"):
+        assert h in hooks and h in abo._lib.TEST_EXPORTS and h not in syms
     out_t = subprocess.run(["nm", "-D", "--defined-only", abo._lib.LIB_TEST_PATH], capture_output=True, text=True, check=True).stdout
     syms_t = {ln.split()[-1] for ln in out_t.splitlines() if ln.strip()}
     assert sorted(s for s in syms_t if s.startswith("abo_")) == sorted(shipped + hooks)
