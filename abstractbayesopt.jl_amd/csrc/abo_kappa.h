@@ -125,6 +125,67 @@ __device__ __forceinline__ double kappa_tail(double d2) {
     }
 }
 
+// ---- the same tail in fp32, for the M-wide first bound level (kgen_tail32.hip) ------------------------------------------------------
+// Two pairs at a time in the halves of a packed register pair: v_sqrt_f32 and v_exp_f32 per half, the Matérn polynomial and the
+// products in packed fp32.  Nothing that is returned to a caller is computed with it either.
+//
+// TAIL32_ETA_EVAL bounds |kappa_tail32(q) − κ(√q)| for one fp32 number 0 ≤ q < 2·TAIL_W_MAX handed to both as the squared distance,
+// in units of κ(0) = 1, v = 2⁻²⁴ (fp32 unit roundoff; products of two of the errors below, ≤ (16v)², are covered by the slack left):
+//   d̃ = v_sqrt_f32(q) = √q·(1 + δ_s), |δ_s| ≤ 2v: the ISA documents 1 ulp, and an ulp is at most 2⁻²³ of the value.
+//   p̃  the Matérn polynomial, every term positive, so its relative error is at most the worst term's: each fma and each constant
+//      rounded to fp32 gives v, a factor d̃ gives 2v, the cubic term is (q·d̃)·c₃ (ONE factor d̃, one more product):
+//      ν = 3/2: 1 + c·d̃: 4v;  ν = 5/2: the linear term through two fmas: 5v;  ν = 7/2: the linear term through three: 6v;  SE: no p.
+//   t̃ = fl(c̃·d̃), c̃ = fl(−√(2ν)·log₂e): t̃ = t·(1 + θ), |θ| ≤ 2v + v + v = 4v (SE: t̃ = fl(c̃·q): 2v).  With a = √(2ν)·√q (SE: q/2),
+//      2^t̃ = e⁻ᵃ·e^{−aθ}: the value moves by at most a·κ·|θ|, and a·κ(a) ≤ 0.84 (ν = 3/2), 1.18 (5/2), 1.45 (7/2), 0.37 (SE).
+//      The clamp at TAIL32_T_MIN changes nothing: 2^t is below 2⁻¹⁴⁹ there, 0 in fp32 on either side of it.
+//   Ẽ = v_exp_f32(t̃) = 2^t̃·(1 + δ_e), |δ_e| ≤ 2v (1 ulp again).  The instruction flushes a denormal result: an absolute 2⁻¹²⁶ times
+//      p̃ < 2⁶² — nothing.  A denormal q is flushed by v_sqrt_f32 (d̃ = 0, κ̃ = 1, κ ≥ 1 − 2⁻⁶³): nothing either.
+//   κ̃ = fl(p̃·Ẽ): one more v.
+// |κ̃ − κ| ≤ κ·(θ_p + 2v + v) + a·κ·4v: 4 + 3 + 3.4 = 10.4v (ν = 3/2), 5 + 3 + 4.7 = 12.7v (5/2), 6 + 3 + 5.8 = 14.8v (7/2), 2 + 0.74 = 2.8v (SE):
+// below 16v = 2⁻²⁰ for every family.
+// The distance the kernel hands over is an fp32 r̃² whose root is off by a relative and an absolute amount (kgen_tail32.hip), so the
+// guard needs κ's sensitivity to r, not to r²: |r·dκ/dr| ≤ 0.74 (SE 2/e; ν = 3/2: 0.55, 5/2: 0.61, 7/2: 0.64) and |dκ/dr| ≤ 0.64 (SE e^{−1/2} =
+// 0.607; ν = 3/2: √3/e = 0.638, 5/2: 0.627, 7/2: 0.622).  tests/test_kgen_tail32_cpu.py checks all of these figures numerically.
+constexpr double TAIL32_ETA_EVAL = 0x1p-20;
+constexpr double TAIL32_REL_R = 0.74;
+constexpr double TAIL32_LIP_R = 0.64;
+constexpr double TAIL32_R_ABS = 0x1p-59;       // absolute slack of r̃ for fp32 underflow anywhere in the distance (kgen_tail32.hip)
+constexpr float TAIL32_T_MIN = -150.0f;        // clamp of the exponent handed to v_exp_f32
+
+typedef float f2_t __attribute__((ext_vector_type(2)));
+
+// 2^t per half, t ≤ 0 (NaN is taken for TAIL32_T_MIN: the caller answers for non-finite input)
+__device__ __forceinline__ f2_t exp2_tail32(f2_t t) {
+    return f2_t{__builtin_amdgcn_exp2f(__builtin_fmaxf(t[0], TAIL32_T_MIN)), __builtin_amdgcn_exp2f(__builtin_fmaxf(t[1], TAIL32_T_MIN))};
+}
+
+// κ(√q) per half without σ_f², q the squared distance of the difference form (never negative)
+template <int FAM>
+__device__ __forceinline__ f2_t kappa_tail32(f2_t q) {
+    constexpr double L2E = 1.44269504088896340736;          // (the constants: rounded ONCE to fp32)
+    if constexpr (FAM == ABO_KERNEL_SE) {
+        constexpr float c = (float)(-0.5 * L2E);
+        return exp2_tail32(q * f2_t{c, c});
+    } else {
+        const f2_t d{__builtin_amdgcn_sqrtf(q[0]), __builtin_amdgcn_sqrtf(q[1])};
+        const f2_t one{1.0f, 1.0f};
+        if constexpr (FAM == ABO_KERNEL_MATERN52) {
+            constexpr float s5 = 2.23606797749978969640917366873128f, c = (float)(-2.23606797749978969640917366873128 * L2E), c2 = (float)(5.0 / 3.0);
+            const f2_t p = __builtin_elementwise_fma(q, f2_t{c2, c2}, __builtin_elementwise_fma(d, f2_t{s5, s5}, one));
+            return p * exp2_tail32(d * f2_t{c, c});
+        } else if constexpr (FAM == ABO_KERNEL_MATERN72) {
+            constexpr float s7 = 2.64575131106459059050161575363926f, c = (float)(-2.64575131106459059050161575363926 * L2E), c2 = (float)(14.0 / 5.0);
+            constexpr float c3 = (float)(7.0 * 2.64575131106459059050161575363926 / 15.0);
+            const f2_t p = __builtin_elementwise_fma(q * d, f2_t{c3, c3},
+                                                     __builtin_elementwise_fma(q, f2_t{c2, c2}, __builtin_elementwise_fma(d, f2_t{s7, s7}, one)));
+            return p * exp2_tail32(d * f2_t{c, c});
+        } else {
+            constexpr float s3 = 1.73205080756887729352744634150587f, c = (float)(-1.73205080756887729352744634150587 * L2E);
+            return __builtin_elementwise_fma(d, f2_t{s3, s3}, one) * exp2_tail32(d * f2_t{c, c});
+        }
+    }
+}
+
 template <int FAM>
 __device__ __forceinline__ double kappa_eval(double d2) {
     if constexpr (FAM == ABO_KERNEL_SE) {

@@ -31,6 +31,7 @@
 #include "../../include/abo_hip.h"
 #include "abo_internal.h"
 #include "abo_kernels.h"
+#include "kgen_core.h"
 
 using namespace abo;
 
@@ -866,6 +867,7 @@ int32_t oz_planes_of_w(abo_gp* g) {
 // columns past those blocks are summed by the cheaper launch_kgen_tail, which also proves ε ≥ |μ̃ − μ| (kgen_tail.hip).
 // more: a further pass of the same call — its events and counts are kept next to those of the passes before it.
 // level2: a bound pass over the survivors of a first one — μ̃ and ε go to buffers of their own.
+// tail32: the tail of a bound pass by launch_kgen_tail32 (fp32 pairs, a wider proven ε: kgen_tail32.hip) — the M-wide first level.
 constexpr int32_t PRUNE_UNAVAILABLE = -100;
 
 #ifdef ABO_TEST_HOOKS
@@ -889,7 +891,7 @@ int prune_bound_moduli() {
 
 int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0, double best_y, double* mu_out,
                   double* var_out, double* score_out, int pc = 1, int point_major = 0, double* kstore = nullptr,
-                  int64_t ldstore = 0, int rblocks = 0, bool more = false, bool level2 = false) {
+                  int64_t ldstore = 0, int rblocks = 0, bool more = false, bool level2 = false, bool tail32 = false) {
     const int64_t M = Mpts * pc;                         // candidate rows
     hipStream_t s = g->stream;
     const int64_t Np = g->Np;
@@ -988,7 +990,7 @@ int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0
             kt.mu_tail = mut.as<double>(); kt.eps = eps.as<double>();
             kt.M = Mpts; kt.j0 = j0; kt.Mc = mcp; kt.N = (int)g->npts; kt.Np = (int)Np; kt.k0 = ka.res_kmax; kt.d = g->d; kt.dp = g->dp; kt.family = ka.family;
             kt.s = ka.s; kt.sigma_f2 = ka.sigma_f2; kt.mean_c = ka.mean_c;
-            HIPCHK(launch_kgen_tail(kt, s));
+            HIPCHK(tail32 ? launch_kgen_tail32(kt, s) : launch_kgen_tail(kt, s));
         }
         PHASE_EVENT(e[1], s);
         if (oz) {
@@ -1814,6 +1816,7 @@ struct PrunePlan {
     int64_t max_survivors;  // more than this: the ordinary full pass runs instead of the survivor pass
     int rblocks0;           // 256-row blocks of a first, narrower bound level over all candidates (0: none — one bound pass, at rblocks)
     int64_t level2_min;     // the pass at rblocks runs on the first level's survivors when there are more than this many
+    bool tail32;            // the first level's tail of the mean in fp32 (kgen_tail32.hip); nothing without a first level
 };
 
 #ifdef ABO_TEST_HOOKS
@@ -1821,7 +1824,18 @@ std::atomic<int> g_prune_force_rblocks{0};      // abo_test_prune_force: row blo
 std::atomic<int> g_prune_force_mode{0};         // of −Inf (every candidate survives: the worst case, on any data), 2 = as ABO_ACQ_PRUNE=0
 std::atomic<int> g_prune_pre_rblocks{0};        // abo_test_prune_levels: row blocks of the first level (−1 = none, 0 = the rule)
 std::atomic<int64_t> g_prune_level2_min{-1};    // … and the survivor count above which the second runs (−1 = the rule)
+std::atomic<int> g_prune_tail32{-1};            // abo_test_prune_tail32: 0 / 1 = the first level's tail in fp64 / fp32, −1 = the environment's
 #endif
+
+// The mean's tail of the M-wide FIRST bound level in fp32 (kgen_tail32.hip).  ABO_PRUNE_TAIL32=0 (read once) keeps the fp64 tail
+// there, for A/B runs.  Every other bound pass — the second level, a single level — has the fp64 tail either way.
+bool prune_tail32() {
+    static const bool on = [] { const char* e = getenv("ABO_PRUNE_TAIL32"); return !(e && e[0] == '0'); }();
+#ifdef ABO_TEST_HOOKS
+    if (g_prune_tail32.load() >= 0) return g_prune_tail32.load() != 0;
+#endif
+    return on;
+}
 
 bool prune_enabled() {
     static const bool on = [] { const char* e = getenv("ABO_ACQ_PRUNE"); return !(e && e[0] == '0'); }();
@@ -1860,6 +1874,7 @@ PrunePlan prune_plan(int64_t rows, int64_t M, int k, bool want_scores, int kind,
     else if (pre < 0 || forced || rb0 >= rb) rb0 = 0;
     pp.rblocks = rb;
     pp.rblocks0 = rb0;
+    pp.tail32 = rb0 > 0 && prune_tail32();
     pp.k0 = k > 0 ? ((int64_t)4 * k > 1024 ? (int64_t)4 * k : 1024) : 0;
     // below 4·K0 survivors the full pass on them costs less than the ≈ 16 launches of another bound pass
     pp.level2_min = 4 * pp.k0;
@@ -1902,7 +1917,9 @@ int32_t prune_select(abo_gp* g, const double* Zd, int64_t M, const AcqTerms& t, 
     // 1. bound pass: the chunk pipeline on the first row blocks of W — those of the first level where the plan has one
     const bool two_levels = pp.rblocks0 > 0;
     HIPCHK(hipEventRecord(g->evs()[PE], s));
-    int32_t rc = posterior(g, Zd, M, kind, p0, best_y, nullptr, nullptr, ub, 1, 0, nullptr, 0, two_levels ? pp.rblocks0 : pp.rblocks, false);
+    // (a first level's looser mean costs survivors alone, and the second level is there when they are many; a single level has no such net)
+    int32_t rc = posterior(g, Zd, M, kind, p0, best_y, nullptr, nullptr, ub, 1, 0, nullptr, 0, two_levels ? pp.rblocks0 : pp.rblocks, false, false,
+                           pp.tail32);
     if (rc == PRUNE_UNAVAILABLE) return ABO_OK;
     if (rc) return rc;
     g->pst.bound_rows = g->passes.back().rows;
@@ -4221,6 +4238,12 @@ int32_t abo_test_prune_levels(int32_t pre_rblocks, int64_t level2_min) {
     return ABO_OK;
 }
 
+int32_t abo_test_prune_tail32(int32_t mode) {
+    if (mode < -1 || mode > 1) return fail(ABO_EINVAL, "abo_test_prune_tail32: mode = %d (-1 = the environment's, 0 = fp64, 1 = fp32)", mode);
+    g_prune_tail32.store(mode);
+    return ABO_OK;
+}
+
 int32_t abo_test_prune_plan_levels(int64_t rows, int64_t M, int32_t k, int32_t want_scores, int32_t kind, double p0, int32_t p_out,
                                    int32_t int8_fused, int32_t d, int64_t* out) {
     if (!out) return fail(ABO_EINVAL, "abo_test_prune_plan_levels: null argument");
@@ -4272,6 +4295,15 @@ int32_t abo_test_kappa_tail(int32_t device, int32_t family, const double* d2, do
     if (family < ABO_KERNEL_SE || family > ABO_KERNEL_MATERN32) return fail(ABO_EINVAL, "abo_test_kappa_tail: unknown family");
     HIPCHK(hipSetDevice(device));
     HIPCHK(launch_kappa_tail_test(family, d2, out, n, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_kappa_tail32(int32_t device, int32_t family, const double* d2, double* out, int64_t n) {
+    if (!d2 || !out || n < 0) return fail(ABO_EINVAL, "abo_test_kappa_tail32: bad argument");
+    if (family < ABO_KERNEL_SE || family > ABO_KERNEL_MATERN32) return fail(ABO_EINVAL, "abo_test_kappa_tail32: unknown family");
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(launch_kappa_tail32_test(family, d2, out, n, nullptr));
     HIPCHK(wait_stream(nullptr));
     return ABO_OK;
 }

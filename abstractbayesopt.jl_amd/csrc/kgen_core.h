@@ -170,6 +170,12 @@ hipError_t launch_kgen_res_short8(const KgenArgs& a, hipStream_t s);
 hipError_t launch_kgen_res_short9(const KgenArgs& a, hipStream_t s);
 hipError_t launch_kgen_res_short10(const KgenArgs& a, hipStream_t s);
 
+// kgen_tail32.hip: launch_kgen_tail (abo_kernels.h) with the pair arithmetic in packed fp32 and the guard that goes with it — the
+// same arguments, outputs and conditions; the tail of the M-wide first bound level
+hipError_t launch_kgen_tail32(const KgenTailArgs& a, hipStream_t s);
+// test hook: out[i] = kappa_tail32(family, fl32(d2[i])) (abo_kappa.h)
+hipError_t launch_kappa_tail32_test(int family, const double* d2, double* out, int64_t n, hipStream_t s);
+
 template <int RES>
 static hipError_t launch_kgen_res_short(const KgenArgs& a, hipStream_t s) {
     switch (a.family) {

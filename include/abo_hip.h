@@ -836,6 +836,9 @@ int32_t abo_test_prune_force(int32_t rblocks, int32_t mode);
  * many row blocks — an abo_acq whose bound pass has no more row blocks than that then fails with ABO_EINVAL.  level2_min −1 = the rule
  * (level 2 runs on more than 4·K₀ survivors of level 1), ≥ 0 = on more than level2_min of them (0: always).  (0, −1) restores the defaults. */
 int32_t abo_test_prune_levels(int32_t pre_rblocks, int64_t level2_min);
+/* The tail of the mean in the FIRST bound level (csrc/kgen_tail32.hip), process-wide: 1 = in fp32, 0 = in fp64 as every other bound
+ * pass has it (ABO_PRUNE_TAIL32=0), −1 restores the environment's choice.  Nothing in a call without a first level. */
+int32_t abo_test_prune_tail32(int32_t mode);
 /* abo_test_prune_plan with out[5]: the same four values, then the 256-row blocks of the first level (0: none).  ABO_EINVAL for a forced
  * first level that is not below the bound pass's row blocks.  No GPU needed. */
 int32_t abo_test_prune_plan_levels(int64_t rows, int64_t M, int32_t k, int32_t want_scores, int32_t kind, double p0, int32_t p_out,
@@ -857,6 +860,9 @@ int32_t abo_test_prune_bounds(abo_gp* gp, double* out, int64_t M);
 int32_t abo_test_prune_mean(abo_gp* gp, double* mu, double* eps, int64_t M);
 /* out[i] = kappa_tail(family, d2[i]): the shortened kernel evaluation of that pass (csrc/abo_kappa.h), without sigma_f2 */
 int32_t abo_test_kappa_tail(int32_t device, int32_t family, const double* d2, double* out, int64_t n);
+/* out[i] = kappa_tail32(family, d2[i] rounded to fp32): the fp32 evaluation of the first level's tail (csrc/abo_kappa.h), without
+ * sigma_f2; NaN where the two halves of the packed pair disagree */
+int32_t abo_test_kappa_tail32(int32_t device, int32_t family, const double* d2, double* out, int64_t n);
 /* The int8-residue engine's host constants for n moduli (no GPU needed): p[16] moduli, tables[4][16] = {1/p, 2^26 mod p
  * (symmetric), head and tail of (P/p)·((P/p)⁻¹ mod p)}, scal[3] = {head of P, tail of P, 1/P}, *eP with 2^eP ≤ P/4. */
 int32_t abo_test_oz_plan(int32_t n, int32_t* p, double* tables, double* scal, int32_t* eP);
