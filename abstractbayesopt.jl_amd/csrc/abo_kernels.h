@@ -235,6 +235,32 @@ struct KgenTailArgs {
 hipError_t launch_kgen_tail(const KgenTailArgs& a, hipStream_t s);
 // test hook: out[i] = kappa_tail(family, d2[i]) (abo_kappa.h)
 hipError_t launch_kappa_tail_test(int family, const double* d2, double* out, int64_t n, hipStream_t s);
+// ---- the head of the M-wide first bound level in one fused kernel (kgen_head32.hip) ----
+// For every candidate gj < M, over the first R = 256·rblocks training points / rows of W (R ≤ N):
+//   head[gj] = mean_c + sigma_f2·Σ_{k<R} alpha_k·κ(r²_jk)   in fp64, the generator's arithmetic per pair
+//   ssq[gj]  ≤ the full pass's computed Σ_i v_ij² (V = W·K_XZ): (1 − c)·Σ_{i<R} max(|Ṽ_ij| − delta[i], 0)², Ṽ = fl32(W)·fl32(K) on the fp32
+//              matrix pipe; NaN for a candidate with a non-finite kernel value
+// A preparation launch in front writes Wf (R·R floats, fragment order), l1[i] = ‖W_i‖₁ and delta[i] ≥ |Ṽ_ij − v_ij| (+Inf: a flagged
+// row, which contributes 0).  eP_full / sK_full / rec_full: the full pass's residue plan (its exponent budget, the scale of its image of
+// K and its reconstruction error in integer units), which delta covers.  Nothing behind M or R is written.
+struct KgenHead32Args {
+    const double* Xs;     // [Np][dp]  only the rows k < R are read
+    const double* Z;      // [M][d]
+    const double* alpha;  // [Np]      only the entries k < R are read
+    const double* W;      // [Np][ldw] only the rows i < R, columns k ≤ i
+    int64_t ldw;
+    float* Wf;            // scratch [R·R]
+    double* delta;        // [R]
+    double* l1;           // [R]
+    double* head;         // [M]
+    double* ssq;          // [M]
+    int64_t M;
+    int N, Np, R, d, dp, family;
+    double s, sigma_f2, mean_c;
+    int eP_full, sK_full;
+    double rec_full;
+};
+hipError_t launch_kgen_head32(const KgenHead32Args& a, hipStream_t s);
 // NLML gradient reduction: Σ_ij (Kinv − ααᵀ)_ij ∂K_ij/∂log ℓ over the lower tiles, plus tr(Kinv), αᵀα, αᵀδ
 struct NlmlGradArgs {
     const double* Xs;      // [Np][dp]
@@ -389,6 +415,10 @@ struct FinalizeArgs {
     // μ̃ = head + tail on the way out, mu_eps [M] the proven |μ̃ − μ| — var / score are taken at μ̃ − ε
     double* mu_tail = nullptr;
     const double* mu_eps = nullptr;
+    // … with the fused first-level head (kgen_head32.hip): the head of the mean and the guarded sum of squares by GLOBAL index, in
+    // place of mu_in and of the row blocks of partial
+    const double* head_g = nullptr;
+    const double* ssq_g = nullptr;
 };
 hipError_t launch_finalize(const FinalizeArgs& a, hipStream_t s);
 

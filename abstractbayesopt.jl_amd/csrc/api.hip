@@ -382,10 +382,13 @@ struct abo_gp {
     int64_t oz_N = -1;
     // the posterior passes of the current call, in launch order (their per-chunk events are read back with them): the pruned top-k
     // selection of abo_acq runs up to five (two bound levels, threshold, survivors or the fallback's full pass), everything else one
-    struct PostPass { int64_t chunk0, nchunk, M, rows; int nmod; };   // first chunk's event slot, chunks, candidate rows, rows of W contracted, moduli launched
+    struct PostPass { int64_t chunk0, nchunk, M, rows; int nmod; bool head32 = false; };   // first chunk's event slot, chunks, candidate rows, rows of W contracted, moduli launched
+                                                                                       // (0 and head32: the fused fp32 head of a first bound level, one launch, timed in its first chunk's contraction slot)
     std::vector<PostPass> passes;
     DevBuf pr_ub, pr_z, pr_sc, pr_sel, pr_blk, pr_tv, pr_ti;   // pruned selection: bounds, gathered points, their scores, survivor list, scan scratch, threshold pairs
     DevBuf pr_mut, pr_eps, pr_nrm;                             // its bound pass: μ̃ and ε of every candidate, the norms ε is built from (kgen_tail.hip)
+    DevBuf pr_head, pr_ssq, pr_wf, pr_hdl;                     // the fused first-level head (kgen_head32.hip): head of μ̃ and S̃ of every candidate, fp32 fragments of W's head, δ and ‖W_i‖₁
+    int ph_rows = 0;                                           // rows of the last fused head (0: the last bound pass ran none)
     DevBuf pr_ub2, pr_mut2, pr_eps2;                           // second bound level: bounds, μ̃ and ε of the first level's survivors, in list order
     abo_prune_stats pst{};
     struct PruneLevels { int64_t rows1, s1, rows2, s2; double ms1, ms2; } plv{};      // abo_get_prune_levels
@@ -868,6 +871,8 @@ int32_t oz_planes_of_w(abo_gp* g) {
 // more: a further pass of the same call — its events and counts are kept next to those of the passes before it.
 // level2: a bound pass over the survivors of a first one — μ̃ and ε go to buffers of their own.
 // tail32: the tail of a bound pass by launch_kgen_tail32 (fp32 pairs, a wider proven ε: kgen_tail32.hip) — the M-wide first level.
+// head32 (with tail32 only): the head of that pass — head of the mean and guarded sum of squares — by ONE launch of kgen_head32.hip over
+// all candidates in place of head generator, residue GEMM and reconstruction per chunk; the chunk loop then runs tail and epilogue alone.
 constexpr int32_t PRUNE_UNAVAILABLE = -100;
 
 #ifdef ABO_TEST_HOOKS
@@ -891,7 +896,7 @@ int prune_bound_moduli() {
 
 int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0, double best_y, double* mu_out,
                   double* var_out, double* score_out, int pc = 1, int point_major = 0, double* kstore = nullptr,
-                  int64_t ldstore = 0, int rblocks = 0, bool more = false, bool level2 = false, bool tail32 = false) {
+                  int64_t ldstore = 0, int rblocks = 0, bool more = false, bool level2 = false, bool tail32 = false, bool head32 = false) {
     const int64_t M = Mpts * pc;                         // candidate rows
     hipStream_t s = g->stream;
     const int64_t Np = g->Np;
@@ -930,7 +935,8 @@ int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0
     // the bound pass on a short plan: its own planes of the first 256·rblocks rows of W, row scales and guards — rebuilt every call (one
     // row-scale and one quantiser launch over R × R; appends, abo_update, a changed R and shared factor storage would all have to
     // invalidate a cache)
-    const int nb = rblocks > 0 ? prune_bound_moduli() : 0;
+    head32 = head32 && tail32 && rblocks > 0 && oz && (int64_t)256 * rblocks <= g->npts && 256 * rblocks <= 2048;
+    const int nb = rblocks > 0 && !head32 ? prune_bound_moduli() : 0;
     const bool shortp = nb > 0 && nb != g->oz_plan.n;
     const double sf2k = g->p_out > 1 ? (pc > 1 ? 2.0 : 1.5) * g->prm.sigma_f2 : g->prm.sigma_f2;
     if (shortp) {
@@ -948,12 +954,34 @@ int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0
                                   oz_k_scale(sf2k), sf2k * (1.0 + 0x1p-40), g->oz_WRb.as<int8_t>(), g->oz_sexpb.as<int>(), g->oz_badrb.as<int>(),
                                   g->oz_delta.as<double>(), s));
     } else if (rblocks > 0) g->pb_rows = 0;
+    if (rblocks > 0) g->ph_rows = head32 ? 256 * rblocks : 0;
     const OzPlan& plan = shortp ? g->oz_plan_b : g->oz_plan;
-    g->passes.push_back({chunk0, nchunk, M, rblocks > 0 && (int64_t)256 * rblocks < g->N ? (int64_t)256 * rblocks : g->N, oz ? plan.n : 0});
+    g->passes.push_back({chunk0, nchunk, M, rblocks > 0 && (int64_t)256 * rblocks < g->N ? (int64_t)256 * rblocks : g->N, oz && !head32 ? plan.n : 0, head32});
     g->tm.contraction_engine = want_var ? (oz ? ABO_CONTRACT_INT8 : ABO_CONTRACT_FP64) : 0;
     g->tm.oz_nmod = oz ? g->oz_plan.n : 0;
     // (prune_plan: fewer row blocks than the model has, so the tail is never empty)
     if (rblocks > 0) HIPCHK(launch_tail_norms(g->st->Xs.as<double>(), g->alpha.as<double>(), (int)g->npts, g->dp, 256 * rblocks, g->pr_nrm.as<double>(), s));
+    if (head32) {
+        const int rows = 256 * rblocks;
+        HIPCHK(g->pr_head.ensure(sizeof(double) * M));
+        HIPCHK(g->pr_ssq.ensure(sizeof(double) * M));
+        HIPCHK(g->pr_wf.ensure(sizeof(float) * rows * rows));
+        HIPCHK(g->pr_hdl.ensure(sizeof(double) * 2 * rows));
+        KgenHead32Args ha{};
+        ha.Xs = g->st->Xs.as<double>(); ha.Z = Zd; ha.alpha = g->alpha.as<double>(); ha.W = g->st->W.as<double>(); ha.ldw = g->st->cap;
+        ha.Wf = g->pr_wf.as<float>(); ha.delta = g->pr_hdl.as<double>(); ha.l1 = g->pr_hdl.as<double>() + rows;
+        ha.head = g->pr_head.as<double>(); ha.ssq = g->pr_ssq.as<double>();
+        ha.M = M; ha.N = (int)g->npts; ha.Np = (int)Np; ha.R = rows; ha.d = g->d; ha.dp = g->dp; ha.family = g->prm.family;
+        ha.s = 1.0 / g->prm.ell; ha.sigma_f2 = g->prm.sigma_f2; ha.mean_c = g->prm.mean_c;
+        // what δ covers of the FULL pass: its plan's exponent budget, the scale of its image of K, its reconstruction error
+        ha.eP_full = g->oz_plan.eP; ha.sK_full = oz_k_scale(sf2k);
+        ha.rec_full = (128.0 * g->oz_plan.n * g->oz_plan.n + 256.0 * g->oz_plan.n) * std::ldexp(1.0, g->oz_plan.eP - 91);
+        hipEvent_t* e0 = &g->evs()[EV_BASE + EV_PER_CHUNK * chunk0];
+        PHASE_EVENT(e0[2], s);
+        HIPCHK(launch_kgen_head32(ha, s));
+        PHASE_EVENT(e0[3], s);
+        g->tm.var_gemm_launches += 1;
+    }
     for (int64_t c = 0; c < nchunk; ++c) {
         const int64_t j0 = c * Mc;
         const int64_t m = (M - j0) < Mc ? (M - j0) : Mc;
@@ -983,7 +1011,7 @@ int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0
             if (!kstore) ka.Kout = nullptr;
         } else ka.res_kmax = 0;
         PHASE_EVENT(e[0], s);
-        HIPCHK(launch_kgen(ka, s));
+        if (!head32) HIPCHK(launch_kgen(ka, s));
         if (rblocks > 0) {
             KgenTailArgs kt{};
             kt.Xs = ka.Xs; kt.Z = Zd; kt.alpha = ka.alpha; kt.norms = g->pr_nrm.as<double>();
@@ -993,7 +1021,9 @@ int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0
             HIPCHK(tail32 ? launch_kgen_tail32(kt, s) : launch_kgen_tail(kt, s));
         }
         PHASE_EVENT(e[1], s);
-        if (oz) {
+        if (head32) {
+            // (head and sum of squares of every candidate are there already)
+        } else if (oz) {
             OzVarArgs oa{};
             oa.plan = &plan; oa.Kxz = kchunk; oa.ldk = ldk; oa.WR = g->oz_WR.as<int8_t>(); oa.sexp = g->oz_sexp.as<int>();
             oa.bad_row = g->oz_badr.as<int>(); oa.KR = g->oz_KR.as<int8_t>(); oa.U = g->oz_U.as<int8_t>();
@@ -1025,10 +1055,11 @@ int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0
         FinalizeArgs fa{};
         fa.partial = g->partial.as<double>(); fa.mu_in = g->mu_c.as<double>(); fa.mu_out = mu_out;
         fa.var_out = var_out; fa.score_out = score_out; fa.ldp = Mc; fa.j0 = j0; fa.M = M;
-        fa.T = (var_out || score_out) ? (rblocks > 0 && 2 * rblocks < T ? 2 * rblocks : T) : 0; fa.Mc = mcp; fa.kind = kind; fa.sigma_f2 = g->prm.sigma_f2;
+        fa.T = (var_out || score_out) && !head32 ? (rblocks > 0 && 2 * rblocks < T ? 2 * rblocks : T) : 0; fa.Mc = mcp; fa.kind = kind; fa.sigma_f2 = g->prm.sigma_f2;
         fa.p0 = p0; fa.best_y = best_y;
         fa.prior_grad = grad_prior_var(g); fa.pc = pc; fa.point_major = point_major; fa.Mpts = Mpts;
         if (rblocks > 0) { fa.mu_tail = mut.as<double>(); fa.mu_eps = eps.as<double>(); }
+        if (head32) { fa.head_g = g->pr_head.as<double>(); fa.ssq_g = g->pr_ssq.as<double>(); }
         PHASE_EVENT(e[4], s);
         HIPCHK(launch_finalize(fa, s));
         PHASE_EVENT(e[5], s);
@@ -1126,8 +1157,9 @@ void collect_posterior_timings(abo_gp* g, bool with_var) {
         for (int64_t c = 0; phase_events() && c < ps.nchunk; ++c) {
             hipEvent_t* e = &g->evs()[EV_BASE + EV_PER_CHUNK * (ps.chunk0 + c)];
             kx += ev_ms(e[0], e[1]);
-            if (with_var) vg += ev_ms(e[2], e[3]);
-            if (oz) { oq += ev_ms(e[2], e[6]); og += ev_ms(e[6], e[7]); oc += ev_ms(e[7], e[3]); }
+            // (a fused first-level head: one launch, timed in the first chunk's slot — the other chunks' slots hold older calls' events)
+            if (with_var && (!ps.head32 || c == 0)) vg += ev_ms(e[2], e[3]);
+            if (oz && !ps.head32) { oq += ev_ms(e[2], e[6]); og += ev_ms(e[6], e[7]); oc += ev_ms(e[7], e[3]); }
             fi += ev_ms(e[4], e[5]);
         }
         work += (double)ps.rows * (double)ps.rows * (double)ps.M;
@@ -1817,6 +1849,7 @@ struct PrunePlan {
     int rblocks0;           // 256-row blocks of a first, narrower bound level over all candidates (0: none — one bound pass, at rblocks)
     int64_t level2_min;     // the pass at rblocks runs on the first level's survivors when there are more than this many
     bool tail32;            // the first level's tail of the mean in fp32 (kgen_tail32.hip); nothing without a first level
+    bool head32;            // … and its head — head of the mean, guarded sum of squares — by the fused fp32-MFMA kernel (kgen_head32.hip)
 };
 
 #ifdef ABO_TEST_HOOKS
@@ -1825,6 +1858,7 @@ std::atomic<int> g_prune_force_mode{0};         // of −Inf (every candidate su
 std::atomic<int> g_prune_pre_rblocks{0};        // abo_test_prune_levels: row blocks of the first level (−1 = none, 0 = the rule)
 std::atomic<int64_t> g_prune_level2_min{-1};    // … and the survivor count above which the second runs (−1 = the rule)
 std::atomic<int> g_prune_tail32{-1};            // abo_test_prune_tail32: 0 / 1 = the first level's tail in fp64 / fp32, −1 = the environment's
+std::atomic<int> g_prune_head32{-1};            // abo_test_prune_head32: 0 / 1 = the first level's head on the int8 engine / fused in fp32, −1 = the environment's
 #endif
 
 // The mean's tail of the M-wide FIRST bound level in fp32 (kgen_tail32.hip).  ABO_PRUNE_TAIL32=0 (read once) keeps the fp64 tail
@@ -1833,6 +1867,20 @@ bool prune_tail32() {
     static const bool on = [] { const char* e = getenv("ABO_PRUNE_TAIL32"); return !(e && e[0] == '0'); }();
 #ifdef ABO_TEST_HOOKS
     if (g_prune_tail32.load() >= 0) return g_prune_tail32.load() != 0;
+#endif
+    return on;
+}
+
+// The head of that first level by the fused kernel of kgen_head32.hip — only where the fp32 tail runs, and not under an explicit moduli
+// request (ABO_PRUNE_BOUND_MODULI set, or its hook): that asks for the int8 engine.  ABO_PRUNE_HEAD32=0 (read once) keeps the fp32 tail
+// and runs the int8 head (generator planes, residue GEMM, reconstruction), for A/B runs.
+bool prune_head32() {
+    static const bool on = [] { const char* e = getenv("ABO_PRUNE_HEAD32"); return !(e && e[0] == '0'); }();
+    static const bool moduli_env = getenv("ABO_PRUNE_BOUND_MODULI") != nullptr;
+    if (moduli_env) return false;
+#ifdef ABO_TEST_HOOKS
+    if (g_prune_bound_moduli.load() != 0) return false;
+    if (g_prune_head32.load() >= 0) return g_prune_head32.load() != 0;
 #endif
     return on;
 }
@@ -1875,6 +1923,7 @@ PrunePlan prune_plan(int64_t rows, int64_t M, int k, bool want_scores, int kind,
     pp.rblocks = rb;
     pp.rblocks0 = rb0;
     pp.tail32 = rb0 > 0 && prune_tail32();
+    pp.head32 = pp.tail32 && prune_head32();
     pp.k0 = k > 0 ? ((int64_t)4 * k > 1024 ? (int64_t)4 * k : 1024) : 0;
     // below 4·K0 survivors the full pass on them costs less than the ≈ 16 launches of another bound pass
     pp.level2_min = 4 * pp.k0;
@@ -1919,7 +1968,7 @@ int32_t prune_select(abo_gp* g, const double* Zd, int64_t M, const AcqTerms& t, 
     HIPCHK(hipEventRecord(g->evs()[PE], s));
     // (a first level's looser mean costs survivors alone, and the second level is there when they are many; a single level has no such net)
     int32_t rc = posterior(g, Zd, M, kind, p0, best_y, nullptr, nullptr, ub, 1, 0, nullptr, 0, two_levels ? pp.rblocks0 : pp.rblocks, false, false,
-                           pp.tail32);
+                           pp.tail32, pp.head32);
     if (rc == PRUNE_UNAVAILABLE) return ABO_OK;
     if (rc) return rc;
     g->pst.bound_rows = g->passes.back().rows;
@@ -4241,6 +4290,52 @@ int32_t abo_test_prune_levels(int32_t pre_rblocks, int64_t level2_min) {
 int32_t abo_test_prune_tail32(int32_t mode) {
     if (mode < -1 || mode > 1) return fail(ABO_EINVAL, "abo_test_prune_tail32: mode = %d (-1 = the environment's, 0 = fp64, 1 = fp32)", mode);
     g_prune_tail32.store(mode);
+    return ABO_OK;
+}
+
+int32_t abo_test_prune_head32(int32_t mode) {
+    if (mode < -1 || mode > 1) return fail(ABO_EINVAL, "abo_test_prune_head32: mode = %d (-1 = the environment's, 0 = int8 head, 1 = fused fp32 head)", mode);
+    g_prune_head32.store(mode);
+    return ABO_OK;
+}
+
+int32_t abo_test_bound_head32(abo_gp* g, const double* Z, int64_t M, int32_t rblocks, double* head, double* ssq, double* delta, double* l1) {
+    if (!g || !Z || !head || !ssq || !delta || !l1 || M <= 0 || rblocks <= 0) return fail(ABO_EINVAL, "abo_test_bound_head32: bad argument");
+    { int32_t rc = check_fitted(g, g->d); if (rc) return rc; }
+    if (g->p_out != 1) return fail(ABO_EINVAL, "abo_test_bound_head32: an ordinary model only");
+    const int rows = 256 * rblocks;
+    HIPCHK(hipSetDevice(g->prm.device));
+    hipStream_t s = g->stream;
+    // every output with one sentinel behind M / behind row R: the kernels write nothing there
+    ScratchBuf zd(g->prm.device, s), out(g->prm.device, s), wf(g->prm.device, s), dl(g->prm.device, s);
+    HIPCHK(zd.b.ensure(sizeof(double) * M * g->d));
+    HIPCHK(out.b.ensure(sizeof(double) * 2 * (M + 1)));
+    HIPCHK(wf.b.ensure(sizeof(float) * rows * rows));
+    HIPCHK(dl.b.ensure(sizeof(double) * 2 * (rows + 1)));
+    const std::vector<double> fill(2 * (size_t)(M + 1), -7.0), fill_r(2 * (size_t)(rows + 1), -7.0);
+    HIPCHK(hipMemcpyAsync(zd.b.p, Z, sizeof(double) * M * g->d, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(out.b.p, fill.data(), sizeof(double) * fill.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dl.b.p, fill_r.data(), sizeof(double) * fill_r.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(wait_stream(s));
+    OzPlan full;
+    if (!oz_make_plan(OZ_DEFAULT_NMOD, &full)) return fail(ABO_EINVAL, "abo_test_bound_head32: no plan");
+    KgenHead32Args ha{};
+    ha.Xs = g->st->Xs.as<double>(); ha.Z = zd.b.as<double>(); ha.alpha = g->alpha.as<double>(); ha.W = g->st->W.as<double>(); ha.ldw = g->st->cap;
+    ha.Wf = wf.b.as<float>(); ha.delta = dl.b.as<double>(); ha.l1 = dl.b.as<double>() + rows + 1;
+    ha.head = out.b.as<double>(); ha.ssq = out.b.as<double>() + M + 1;
+    ha.M = M; ha.N = (int)g->npts; ha.Np = (int)g->Np; ha.R = rows; ha.d = g->d; ha.dp = g->dp; ha.family = g->prm.family;
+    ha.s = 1.0 / g->prm.ell; ha.sigma_f2 = g->prm.sigma_f2; ha.mean_c = g->prm.mean_c;
+    ha.eP_full = full.eP; ha.sK_full = oz_k_scale(g->prm.sigma_f2);
+    ha.rec_full = (128.0 * full.n * full.n + 256.0 * full.n) * std::ldexp(1.0, full.eP - 91);
+    const hipError_t le = launch_kgen_head32(ha, s);
+    if (le == hipErrorInvalidValue) return fail(ABO_EINVAL, "abo_test_bound_head32: %d rows on a model of %lld points", rows, (long long)g->npts);
+    HIPCHK(le);
+    // head / ssq: M + 1 doubles each, delta / l1: rows + 1 — the last of each is the sentinel (−7) as the kernels left it
+    HIPCHK(hipMemcpyAsync(head, ha.head, sizeof(double) * (M + 1), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(ssq, ha.ssq, sizeof(double) * (M + 1), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(delta, ha.delta, sizeof(double) * (rows + 1), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(l1, ha.l1, sizeof(double) * (rows + 1), hipMemcpyDeviceToHost, s));
+    HIPCHK(wait_stream(s));
     return ABO_OK;
 }
 

@@ -20,7 +20,7 @@ __global__ void __launch_bounds__(256) finalize_kernel(FinalizeArgs p) {
     if (j >= p.Mc) return;
     const int64_t gj = p.j0 + j;
     if (gj >= p.M) return;
-    double q = 0.0;
+    double q = p.ssq_g ? p.ssq_g[gj] : 0.0;
 #pragma unroll 16
     for (int t = 0; t < p.T; ++t) q += p.partial[(int64_t)t * p.ldp + j];   // row blocks in order (loads hoisted, adds in order)
     double prior = p.sigma_f2;
@@ -29,7 +29,7 @@ __global__ void __launch_bounds__(256) finalize_kernel(FinalizeArgs p) {
         if (o > 0) prior = p.prior_grad;
     }
     const double var = prior - q + 1e-18;
-    double mu = p.mu_in[j];
+    double mu = p.head_g ? p.head_g[gj] : p.mu_in[j];
     if (p.mu_tail) {
         mu += p.mu_tail[gj];
         p.mu_tail[gj] = mu;

@@ -839,6 +839,14 @@ int32_t abo_test_prune_levels(int32_t pre_rblocks, int64_t level2_min);
 /* The tail of the mean in the FIRST bound level (csrc/kgen_tail32.hip), process-wide: 1 = in fp32, 0 = in fp64 as every other bound
  * pass has it (ABO_PRUNE_TAIL32=0), −1 restores the environment's choice.  Nothing in a call without a first level. */
 int32_t abo_test_prune_tail32(int32_t mode);
+/* The HEAD of that first level (csrc/kgen_head32.hip), process-wide: 1 = head of the mean and guarded sum of squares by the fused
+ * fp32-MFMA kernel, 0 = on the int8 engine (ABO_PRUNE_HEAD32=0), −1 restores the environment's choice.  The fused head runs only where
+ * the fp32 tail does, and never under an explicit moduli request (ABO_PRUNE_BOUND_MODULI, abo_test_prune_bound_moduli != 0). */
+int32_t abo_test_prune_head32(int32_t mode);
+/* Preparation and kernel of the fused head alone, on a fitted ordinary model, over its first 256·rblocks rows (≤ N) and the M HOST
+ * candidates Z [M][d]: head and ssq (M + 1 doubles each), delta and l1 (256·rblocks + 1 each).  The last entry of each is a sentinel (−7)
+ * the kernels must leave alone. */
+int32_t abo_test_bound_head32(abo_gp* g, const double* Z, int64_t M, int32_t rblocks, double* head, double* ssq, double* delta, double* l1);
 /* abo_test_prune_plan with out[5]: the same four values, then the 256-row blocks of the first level (0: none).  ABO_EINVAL for a forced
  * first level that is not below the bound pass's row blocks.  No GPU needed. */
 int32_t abo_test_prune_plan_levels(int64_t rows, int64_t M, int32_t k, int32_t want_scores, int32_t kind, double p0, int32_t p_out,
