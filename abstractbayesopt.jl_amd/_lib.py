@@ -26,7 +26,7 @@ EXPORTS = ["abo_create", "abo_set_contraction", "abo_create_grad", "abo_predict_
            "abo_paths_create", "abo_paths_destroy", "abo_paths_eval", "abo_paths_eval_cand", "abo_paths_stats_get",
            "abo_paths_append", "abo_paths_attach", "abo_paths_detach", "abo_paths_top", "abo_paths_values", "abo_paths_append_stats_get",
            "abo_score_mes", "abo_acq_mes", "abo_cand_acq_mes", "abo_refine_mes", "abo_optimize_acquisition_mes",
-           "abo_loo", "abo_loo_grad", "abo_predict_cov"]
+           "abo_loo", "abo_loo_grad", "abo_predict_cov", "abo_remove"]
 TEST_EXPORTS = ["abo_test_gemm_nt", "abo_test_kappa", "abo_test_oz_plan", "abo_test_oz_contract", "abo_test_acq_grad",
                 "abo_test_acq_grad_terms", "abo_test_prune_plan", "abo_test_prune_force", "abo_test_prune_levels", "abo_test_prune_plan_levels", "abo_test_prune_bounds", "abo_test_prune_mean",
                 "abo_test_kappa_tail", "abo_test_prune_tail32", "abo_test_prune_head32", "abo_test_bound_head32", "abo_test_kappa_tail32", "abo_test_prune_bound_moduli", "abo_test_prune_bound_plan", "abo_test_oz_contract_bound", "abo_test_acq_partials", "abo_test_mes_partials", "abo_test_acq_grad_mes",
@@ -40,6 +40,9 @@ CONTRACT_AUTO, CONTRACT_FP64, CONTRACT_INT8 = 0, 1, 2
 # what abo_update / abo_mgpu_update ran (include/abo_hip.h)
 UPDATE_SHARED, UPDATE_APPENDED, UPDATE_REFIT = 0, 1, 2
 UPDATE_PATHS = {UPDATE_SHARED: "shared", UPDATE_APPENDED: "appended", UPDATE_REFIT: "refit"}
+# what abo_remove ran
+REMOVE_REMOVED, REMOVE_REFIT = 0, 1
+REMOVE_PATHS = {REMOVE_REMOVED: "removed", REMOVE_REFIT: "refit"}
 
 
 class AboParams(C.Structure):
@@ -303,6 +306,7 @@ def lib():
                                                  vp, C.POINTER(f64), vp, vp, vp, vp]
     L.abo_mgpu_optimize_acquisition_terms.argtypes = L.abo_optimize_acquisition_terms.argtypes
     L.abo_update.argtypes = [vp, C.POINTER(AboParams), vp, vp, i64, i32, vp, i32, C.POINTER(i64), C.POINTER(i32), C.POINTER(vp)]
+    L.abo_remove.argtypes = [vp, vp, i32, C.POINTER(i32), C.POINTER(vp)]
     L.abo_mgpu_update.argtypes = [vp, C.POINTER(AboParams), vp, vp, i64, i32, vp, C.POINTER(i64), C.POINTER(i32), C.POINTER(vp)]
     L.abo_fit_acq.argtypes = [vp, vp, i64, i32, vp, i32, C.POINTER(i64), vp, i64, i32, i32, f64, f64, i64, vp, i32, vp, vp, i32]
     for name in EXPORTS + (TEST_EXPORTS if hooks else []):

@@ -651,4 +651,24 @@ int64_t topk_workspace_entries(int64_t M, int k);
 hipError_t launch_topk(const double* scores, int64_t M, int k, int64_t idx_base, TopkWork w,
                        double* top_val, int64_t* top_idx, hipStream_t s);
 
+// ---- removal of an observation (remove.hip; abo_remove) ----------------------------------------
+constexpr int REMOVE_SCAN_CHUNK = 256;   // elements of a row one scan step takes (four 64-lane sub-blocks)
+// Row j out of an N-row factor (N ≥ 2): L′ (lower triangle and the identity diagonal of the padding), WT′ and W′ = WT′ᵀ (the whole
+// pad128(N − 1)-square block, zeros outside the triangle, identity in the padding) and α′ [N − 1] into buffers of leading dimension
+// ldn ≥ pad128(N − 1); the source (leading dimension ld, rows and columns < N only) is read, never written.
+// work: 5·N doubles of scratch; scal = {ω = W[j][j], ρ_m² = B_jj/ω², α_j}: log det′ = log det + log(ω²ρ_m²), δ′ᵀα′ = δᵀα − α_j²/(ω²ρ_m²)
+struct RemoveArgs {
+    const double* L; const double* WT; const double* alpha;
+    int64_t ld;
+    double* Ln; double* Wn; double* WTn; double* alpha_n;
+    int64_t ldn;
+    int N, j;
+    double* work; double* scal;
+};
+hipError_t launch_remove_row(const RemoveArgs& a, hipStream_t s);
+// the per-point arrays without the k points idx (device, strictly increasing): Nn = the points that remain.  Xs_n / delta_n may be
+// null (then Xs / delta are not read)
+hipError_t launch_remove_gather(const int64_t* idx, int k, int64_t Nn, int d, int dp, const double* Xraw, const double* Xs, const double* y,
+                                const double* delta, double* Xraw_n, double* Xs_n, double* y_n, double* delta_n, hipStream_t s);
+
 }  // namespace abo

@@ -1510,6 +1510,83 @@ int32_t append_grad_impl(abo_gp* g, abo_gp* n, const double* x, const double* yv
     return ABO_OK;
 }
 
+// Crossover rule of abo_remove (header): k single removals against one refit of the R − k rows that remain.  Measured with
+// tools/remove_latency.py (profiles/remove_latency.txt): break-even between k = 4 and 8 for R = 1024, at k ≈ 16 for R = 8192.
+int64_t remove_kmax(int64_t R) {
+    const int64_t k = R / 512;
+    return k < 4 ? 4 : (k > 16 ? 16 : k);
+}
+
+// View `g` (N rows) without observation j → the fresh handle `n` on a storage of its own (remove.hip; DESIGN.md "Removing an
+// observation").  idx_d: j on the device.  g and its storage are only read, rows and columns < g->N of them: other views of the
+// storage, larger ones included, keep their bits.  Nothing here can fail numerically: K̃ without a row and a column stays positive
+// definite, and every pivot of the update is ρ_{k+1}/ρ_k ≥ 1 times the old one.
+int32_t remove_one_impl(abo_gp* g, abo_gp* n, int64_t j, const int64_t* idx_d) {
+    Storage* so = g->st;
+    const int d = g->d;
+    const int64_t N = g->N, Nn = N - 1;
+    hipStream_t s = n->stream;
+    Storage* st = new (std::nothrow) Storage();
+    if (!st) return fail(ABO_ENOMEM, "abo_remove: host allocation failed");
+    struct Drop { Storage* st; ~Drop() { if (st) storage_unref(st); } } drop{st};
+    st->set_device(g->prm.device);
+    st->d = d; st->dp = so->dp;
+    st->cap = pad_up(g->prm.n_max > Nn ? g->prm.n_max : Nn, TB);
+    const int64_t cap = st->cap, Npn = pad_up(Nn, TB);
+    hipError_t e = st->Xraw.ensure(sizeof(double) * cap * d);
+    if (e == hipSuccess) e = st->Xs.ensure(sizeof(double) * cap * st->dp);
+    if (e == hipSuccess) e = st->ybuf.ensure(sizeof(double) * cap);
+    if (e == hipSuccess) e = st->delta.ensure(sizeof(double) * cap);
+    if (e == hipSuccess) e = st->K.ensure(sizeof(double) * cap * cap);
+    if (e == hipSuccess) e = st->W.ensure(sizeof(double) * cap * cap);
+    if (e == hipSuccess) e = st->WT.ensure(sizeof(double) * cap * cap);
+    if (e == hipSuccess) e = n->alpha.ensure(sizeof(double) * cap);
+    if (e == hipSuccess) e = n->tvec.ensure(sizeof(double) * cap);
+    if (e == hipSuccess) e = n->info.ensure(sizeof(int64_t));
+    if (e == hipSuccess) e = n->scal.ensure(sizeof(double) * 8);
+    ScratchBuf work(g->prm.device, s);
+    if (e == hipSuccess) e = work.b.ensure(sizeof(double) * 5 * N);
+    if (e != hipSuccess)
+        return fail(e == hipErrorOutOfMemory ? ABO_ENOMEM : ABO_EHIP, "abo_remove: device allocation failed: %s", hipGetErrorString(e));
+    // what a fit leaves outside the view: zero padding of the per-point arrays and of α, zero rows with a unit diagonal behind the
+    // padded size of W / WT (a later append grows into them)
+    HIPCHK(hipMemsetAsync(st->Xs.p, 0, sizeof(double) * cap * st->dp, s));
+    HIPCHK(hipMemsetAsync(st->delta.p, 0, sizeof(double) * cap, s));
+    HIPCHK(hipMemsetAsync(n->alpha.p, 0, sizeof(double) * cap, s));
+    if (cap > Npn) {
+        HIPCHK(hipMemsetAsync(st->W.as<double>() + Npn * cap, 0, sizeof(double) * (cap - Npn) * cap, s));
+        HIPCHK(hipMemsetAsync(st->WT.as<double>() + Npn * cap, 0, sizeof(double) * (cap - Npn) * cap, s));
+        HIPCHK(launch_set_diag(st->W.as<double>(), cap, (int)Npn, (int)cap, 1.0, s));
+        HIPCHK(launch_set_diag(st->WT.as<double>(), cap, (int)Npn, (int)cap, 1.0, s));
+    }
+    HIPCHK(launch_remove_gather(idx_d, 1, Nn, d, st->dp, so->Xraw.as<double>(), so->Xs.as<double>(), so->ybuf.as<double>(),
+                                so->delta.as<double>(), st->Xraw.as<double>(), st->Xs.as<double>(), st->ybuf.as<double>(),
+                                st->delta.as<double>(), s));
+    RemoveArgs ra{};
+    ra.L = so->K.as<double>(); ra.WT = so->WT.as<double>(); ra.alpha = g->alpha.as<double>(); ra.ld = so->cap;
+    ra.Ln = st->K.as<double>(); ra.Wn = st->W.as<double>(); ra.WTn = st->WT.as<double>(); ra.alpha_n = n->alpha.as<double>();
+    ra.ldn = cap; ra.N = (int)N; ra.j = (int)j; ra.work = work.b.as<double>(); ra.scal = n->scal.as<double>();
+    HIPCHK(launch_remove_row(ra, s));
+    double sc[3];
+    PinStage pin(n->ctx);                            // the NEW handle's staging block: `g` may be in use by another thread
+    HIPCHK(pin.d2h(sc, n->scal.p, sizeof sc, s));
+    HIPCHK(wait_stream(s));
+    pin.flush();
+    const double bjj = sc[0] * sc[0] * sc[1];        // B_jj = (K̃⁻¹)_jj = ω²·ρ_m²
+    st->noise_used = so->noise_used;
+    st->add_view(Nn);
+    drop.st = nullptr;
+    storage_unref(n->st);
+    n->st = st;
+    n->N = Nn; n->npts = Nn; n->Np = Npn; n->d = d; n->dp = st->dp;
+    n->from_append = false;
+    n->ap_x.clear();
+    n->logdet = g->logdet + std::log(bjj);
+    n->quad = g->quad - sc[2] * sc[2] / bjj;
+    n->fitted = true;
+    return ABO_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1668,6 +1745,72 @@ int32_t abo_append_grad(abo_gp* g, const double* x, int32_t d, const double* y, 
     rc = append_grad_impl(g, n, x, y, info);
     if (rc) { abo_destroy(n); return rc; }
     *out = n;
+    return ABO_OK;
+}
+
+int32_t abo_remove(abo_gp* g, const int64_t* idx, int32_t k, int32_t* path, abo_gp** out) {
+    if (path) *path = ABO_REMOVE_REFIT;
+    if (!g || !idx || !out) return fail(ABO_EINVAL, "abo_remove: null argument");
+    if (k < 1) return fail(ABO_EINVAL, "abo_remove: k = %d, need at least one index", k);
+    if (!g->fitted) return fail(ABO_EINVAL, "abo_remove: surrogate is not conditioned on data yet (call abo_fit first)");
+    if (g->p_out > 1) return fail(ABO_EINVAL, "abo_remove: gradient-enhanced models are not supported (refit on the remaining points)");
+    const int64_t N = g->N;
+    for (int32_t t = 0; t < k; ++t) {
+        if (idx[t] < 0 || idx[t] >= N) return fail(ABO_EINVAL, "abo_remove: index %lld outside 0..%lld", (long long)idx[t], (long long)N - 1);
+        if (t > 0 && idx[t] <= idx[t - 1]) return fail(ABO_EINVAL, "abo_remove: indices must be strictly increasing (no duplicates)");
+    }
+    if (N - k < 1) return fail(ABO_EINVAL, "abo_remove: removing %d of %lld points leaves none", k, (long long)N);
+    HIPCHK(hipSetDevice(g->prm.device));
+    abo_gp* n = nullptr;
+    int32_t rc = abo_create(&g->prm, &n);
+    if (rc) return rc;
+    n->oz_engine = g->oz_engine; n->oz_nmod = g->oz_nmod;
+    hipStream_t s = n->stream;
+    const int d = g->d;
+    const int64_t Nn = N - k;
+    const bool refit = k > remove_kmax(N);
+    // the indices on the device, and (refit) the points and targets that remain
+    ScratchBuf buf(g->prm.device, s);
+    const size_t idx_bytes = (sizeof(int64_t) * (size_t)k + 15) & ~(size_t)15;
+    hipError_t e = buf.b.ensure(idx_bytes + (refit ? sizeof(double) * (size_t)Nn * (d + 1) : 0));
+    if (e != hipSuccess) {
+        abo_destroy(n);
+        return fail(e == hipErrorOutOfMemory ? ABO_ENOMEM : ABO_EHIP, "abo_remove: device allocation failed: %s", hipGetErrorString(e));
+    }
+    int64_t* idx_d = buf.b.as<int64_t>();
+    e = hipMemcpyAsync(idx_d, idx, sizeof(int64_t) * (size_t)k, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = wait_stream(s);          // the caller's array is free again when the call returns, whatever happens below
+    if (e != hipSuccess) { abo_destroy(n); return fail(ABO_EHIP, "abo_remove: staging the indices failed: %s", hipGetErrorString(e)); }
+    if (refit) {
+        Storage* so = g->st;
+        double* xb = reinterpret_cast<double*>(buf.b.as<char>() + idx_bytes);
+        double* yb = xb + (size_t)Nn * d;
+        e = launch_remove_gather(idx_d, k, Nn, d, so->dp, so->Xraw.as<double>(), nullptr, so->ybuf.as<double>(), nullptr, xb, nullptr, yb,
+                                 nullptr, s);
+        if (e != hipSuccess) { abo_destroy(n); return fail(ABO_EHIP, "abo_remove: gather launch failed: %s", hipGetErrorString(e)); }
+        int64_t inf = 0;
+        rc = fit_impl(n, xb, Nn, d, yb, ABO_DEVICE, &inf);
+        if (rc) { abo_destroy(n); return rc; }
+        *out = n;
+        return ABO_OK;
+    }
+    // k single removals, highest index first (the lower ones keep their positions), each into a storage of its own: the one before
+    // goes back to the pool with its handle, so two storages alternate
+    abo_gp* cur = g;
+    for (int32_t t = k - 1; t >= 0; --t) {
+        if (!n) {
+            rc = abo_create(&g->prm, &n);
+            if (rc) { if (cur != g) abo_destroy(cur); return rc; }
+            n->oz_engine = g->oz_engine; n->oz_nmod = g->oz_nmod;
+        }
+        rc = remove_one_impl(cur, n, idx[t], idx_d + t);
+        if (cur != g) abo_destroy(cur);
+        if (rc) { abo_destroy(n); return rc; }
+        cur = n;
+        n = nullptr;
+    }
+    if (path) *path = ABO_REMOVE_REMOVED;
+    *out = cur;
     return ABO_OK;
 }
 

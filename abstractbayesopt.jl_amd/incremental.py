@@ -38,6 +38,46 @@ def append(model: HipStandardGP, x, y) -> HipStandardGP:
     return model._clone(_Handle(hp.value))
 
 
+def remove_indices(idx) -> np.ndarray:
+    """the indices remove_points hands to abo_remove: an int or a sequence of ints in any order → sorted int64; a repeated index, a
+    non-integer or an empty sequence raises ValueError / TypeError here (the range is the library's check: it knows N)"""
+    a = np.asarray(idx)
+    if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+        if a.size == 0 and a.dtype == np.float64:
+            raise ValueError("remove_points: no index given")
+        raise TypeError(f"remove_points: indices must be integers, not {a.dtype}")
+    a = np.sort(a.reshape(-1).astype(np.int64))
+    if a.size == 0:
+        raise ValueError("remove_points: no index given")
+    if np.any(a[1:] == a[:-1]):
+        raise ValueError(f"remove_points: index {int(a[1:][a[1:] == a[:-1]][0])} is repeated")
+    return np.ascontiguousarray(a)
+
+
+def remove_points(model: HipStandardGP, idx) -> HipStandardGP:
+    """The model without the observations `idx` (an int or a sequence, any order, no duplicates; 0-based positions in
+    training_data(model)) in O(k·N²): a new model conditioned on the remaining points in their original order, with storage of its
+    own; `model` stays valid and unchanged.  The inverse of `append` (include/abo_hip.h: abo_remove).  The result's `remove_path`
+    says what ran: "removed", or "refit" beyond the library's crossover rule.  An ARD model is fine (only indices cross the library;
+    the result carries the same length scales).  Resident candidate sets and sample paths in sync with `model` stay with it: on the
+    new model a set needs `refresh`."""
+    if hasattr(model, "devices"):
+        raise TypeError("remove_points: a sharded model (HipShardedGP) is not supported: the factor is spread over its devices; "
+                        "use a single-device HipStandardGP")
+    if hasattr(model, "p"):
+        raise TypeError("remove_points: a gradient-enhanced model (HipGradientGP) is not supported: an observation is p factor rows; "
+                        "refit on the remaining points")
+    if not isinstance(model, HipStandardGP):
+        raise TypeError(f"remove_points needs a HipStandardGP, not {type(model).__name__}")
+    ix = remove_indices(idx)
+    hp = C.c_void_p()
+    path = C.c_int32(_lib.REMOVE_REFIT)
+    _lib.check(_lib.lib().abo_remove(model._require(), ix.ctypes.data, int(ix.shape[0]), C.byref(path), C.byref(hp)))
+    out = model._clone(_Handle(hp.value))
+    out.remove_path = _lib.REMOVE_PATHS[path.value]
+    return out
+
+
 class _CandHandle:
     def __init__(self, ptr):
         self.ptr = ptr

@@ -49,7 +49,7 @@ extern "C" {
                                   (struct abo_paths_append_stats is new); ABO_ACQ_LOGEI (kind 5 in every entry point that takes a kind
                                   or an abo_acq_term, and in the pruned top-k selection); ABO_ACQ_MES and abo_score_mes, abo_acq_mes,
                                   abo_cand_acq_mes, abo_refine_mes, abo_optimize_acquisition_mes; abo_get_prune_levels; abo_loo, abo_loo_grad;
-                                  abo_predict_cov */
+                                  abo_predict_cov; abo_remove, ABO_REMOVE_REMOVED / _REFIT */
 
 /* status codes */
 enum {
@@ -271,6 +271,28 @@ int32_t abo_append_grad(abo_gp* gp, const double* x, int32_t d, const double* y,
 enum { ABO_UPDATE_SHARED = 0, ABO_UPDATE_APPENDED = 1, ABO_UPDATE_REFIT = 2 };
 int32_t abo_update(abo_gp* prev, const abo_params* params, const double* mean_c, const double* X, int64_t N, int32_t d,
                    const double* y, int32_t space, int64_t* info, int32_t* path, abo_gp** out);
+
+/* The model without k of its observations, in O(k·N²): the inverse of abo_append (DESIGN.md "Removing an observation").  idx: k
+ * strictly increasing point indices in [0, N) (host array), 1 ≤ k, N − k ≥ 1.  *out is a new handle conditioned on the remaining
+ * points in their original order, on factor storage of its own, with gp's parameters, prior mean, the noise gp's factor was built
+ * with (a jittered factor stays jittered) and a capacity of n_max points; gp and every other view of its storage stay valid and
+ * keep their bits (only rows and columns < N of the storage are read).  Removing row j changes L by a rank-one update of the
+ * block behind j whose vector is read off column j of L⁻¹; L⁻¹, α, log det and δᵀα follow in closed form, so no step can fail:
+ * there is no ABO_ENOTPD.  One removal streams the triangles of L and L⁻ᵀ once and writes L, L⁻ᵀ and L⁻¹ of the new model.
+ * k > 1 runs as k single removals, highest index first.  The new handle counts as freshly fitted for every entry point
+ * (abo_append, abo_update as prev, abo_nlml(_grad, _grad_ard), abo_loo(_grad), abo_predict_cov, abo_acq* under both contraction
+ * engines, abo_cand_create, abo_paths_create).  Candidate sets and sample paths in sync with gp stay with gp: on the new model a
+ * set needs abo_cand_refresh.
+ * Crossover rule: k > kmax(N) = clamp(N / 512, 4, 16) gathers the remaining points on the device and refits them
+ * (*path = ABO_REMOVE_REFIT: abo_create + abo_fit on that data, bit for bit; a jittered gp goes through the jitter ladder again).
+ * Measured (profiles/remove_latency.txt, k single removals against one refit of the rest, d = 8, Matérn-5/2): ratio 0.69 at k = 4 and
+ * 1.36 at k = 8 for N = 1024 (rule: 4); 0.47 at k = 8, 0.96 at k = 16 and 1.9 at k = 32 for N = 8192 (rule: 16).  One removal
+ * against the refit: 0.10 vs 0.54 ms at N = 1024, 0.74 vs 11.3 ms at N = 8192, 2.49 vs 54.1 ms at N = 16384 (j = 0, the worst
+ * case).  The floor of 4 below N = 1024 and the cap of 16 above N = 8192 are not measured.
+ * *path (may be NULL): ABO_REMOVE_REMOVED / _REFIT = what ran.  ABO_EINVAL, before any device work: a null, unfitted or
+ * gradient-enhanced handle, k < 1, N − k < 1, indices unsorted, repeated or out of range. */
+enum { ABO_REMOVE_REMOVED = 0, ABO_REMOVE_REFIT = 1 };
+int32_t abo_remove(abo_gp* gp, const int64_t* idx, int32_t k, int32_t* path, abo_gp** out);
 
 /* --- posterior ------------------------------------------------------------------------------
  * posterior_mean / posterior_var (src/surrogates/StandardGP.jl:361-363, :377-379), fused as in

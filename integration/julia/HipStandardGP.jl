@@ -586,6 +586,9 @@ include("LeaveOneOut.jl")
 # joint posterior covariance between point sets (abo_predict_cov): posterior_cov and mean_and_cov
 include("PosteriorCov.jl")
 
+# a model without some of its observations in O(N²) (abo_remove): remove_points
+include("RemovePoints.jl")
+
 # path s takes its best index not taken by paths 1 … s − 1 (idx: k × q orderings, 0 = no candidate)
 function _distinct_picks(idx::AbstractMatrix{Int64})
     picks = Int64[]
