@@ -5,7 +5,7 @@ import os
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG, "lib", "libabo_hip.so")
-# the same library with the abo_test_* building blocks compiled in (-DABO_TEST_HOOKS; include/abo_hip.h, last section): what the test
+# the same objects plus csrc/test_hooks.hip, the abo_test_* building blocks (include/abo_hip.h, last section): what the test
 # suite loads (tests/conftest.py sets ABO_LIB_TEST_HOOKS=1 before the package is imported).  The shipped library exports none of them.
 LIB_TEST_PATH = os.path.join(PKG, "lib", "libabo_hip_test.so")
 

@@ -1,0 +1,262 @@
+// Private state of the single-device host driver: what api.hip shares with test_hooks.hip — the handle struct with the types it is made
+// of, and the internal functions the abo_test_* hooks call.  Nothing else includes this header: mgpu.hip, update.hip, paths.hip and
+// qei_mc.hip see the handles through the accessors of abo_internal.h.  Declarations only: every variable and every function declared
+// here is defined once, in api.hip.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+#include <mutex>
+#include <set>
+#include <vector>
+
+#include "../../include/abo_hip.h"
+#include "abo_internal.h"
+#include "abo_kernels.h"
+
+#define HIPCHK(expr)                                                                                   \
+    do {                                                                                               \
+        hipError_t e_ = (expr);                                                                        \
+        if (e_ != hipSuccess)                                                                          \
+            return fail(e_ == hipErrorOutOfMemory ? ABO_ENOMEM : ABO_EHIP, "%s failed: %s (%s:%d)", #expr, \
+                        hipGetErrorString(e_), __FILE__, __LINE__);                                    \
+    } while (0)
+
+struct abo_gp;
+struct abo_cand;
+
+#pragma GCC visibility push(hidden)
+namespace abo {
+
+int32_t fail(int32_t code, const char* fmt, ...);          // writes the calling thread's slot (abo_last_error), returns code
+hipError_t wait_stream(hipStream_t s);                     // the polled wait every call ends with
+extern std::atomic<uint64_t> g_storage_gen;                // next Storage::gen
+hipError_t pool_alloc(int dev, size_t bytes, void** p, size_t* cap);
+void pool_free(int dev, void* p, size_t cap);
+int32_t check_fitted(abo_gp* g, int32_t d);
+
+struct DevBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    int dev = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }            // every early return (HIPCHK) hands its buffers back to the pool
+    hipError_t ensure(size_t bytes) {
+        if (bytes <= cap) return hipSuccess;
+        release();
+        return pool_alloc(dev, bytes, &p, &cap);
+    }
+    void release() { if (p) pool_free(dev, p, cap); p = nullptr; cap = 0; }
+    template <class T> T* as() const { return static_cast<T*>(p); }
+};
+#define ABO_DEVBUF_MEMBER(name) abo::DevBuf name;
+
+// stream + events of a handle, recycled the same way (hipStreamCreate / ~400 hipEventCreate per step otherwise)
+// pin: a small page-locked host block that lives with the context.  A device-to-host copy of a few bytes into PAGEABLE memory blocks
+// the host until it has happened (12 – 14 µs each on this runtime, tools/memcpy_probe.hip; 2.5 – 3.7 µs and asynchronous into
+// pinned memory) — four of them were a quarter of a BO step at the reference's own sizes.  The fit's scalars and the selected
+// (score, index) pairs land here and are copied on by the host after the call's one synchronisation.
+constexpr size_t PIN_BYTES = 32768, PIN_OUT = 64;      // [0,16) fit scalars, [16,24) info, [PIN_OUT, …) selected pairs
+struct ExecCtx {
+    hipStream_t stream = nullptr;
+    std::vector<hipEvent_t> ev;
+    char* pin = nullptr;
+};
+
+constexpr int OZ_DEFAULT_NMOD = 14;   // moduli of the contraction's residue plan unless asked otherwise; P ≈ 2^110: the fixed-point images keep 50+ bits of W per row and 52–53 bits of K_XZ
+
+// a local scratch buffer of one call: on every exit path the stream is drained before the block goes back to the pool
+// (an error return must not hand memory that queued work still touches to the next handle)
+struct ScratchBuf {
+    DevBuf b;
+    hipStream_t s;
+    ScratchBuf(int dev, hipStream_t st) : s(st) { b.dev = dev; }
+    ~ScratchBuf() { if (b.p) { (void)wait_stream(s); b.release(); } }
+};
+
+// Heavy device state, shared by every view (copy / appended model) that descends from one fit.
+// Rows < N of Xs / delta / L / W / WT are immutable for every live view of size N; an append only
+// writes row N of the largest live view, so older views stay valid and rollback is free.
+#define ABO_STORAGE_BUFS(X) X(Xraw) X(Xs) X(ybuf) X(delta) X(K) X(W) X(WT)
+struct Storage {
+    std::atomic<int> refs{1};
+    // process-wide unique id: what a candidate set remembers of the factor it is synced with (a freed Storage's address
+    // is readily reused by the next refit of the same size; its id never is)
+    const uint64_t gen = g_storage_gen.fetch_add(1);
+    int dev = 0;
+    int d = 0, dp = 0;
+    int64_t cap = 0;        // padded capacity = leading dimension of K/W/WT (multiple of 128)
+    double noise_used = 0.0;
+    // sizes N of the live views on this storage.  A view may append in place only if no live view
+    // is larger (rows ≥ its N are then dead: stale rows of discarded fantasy branches are masked
+    // everywhere by the view's own N, and the append overwrites row N).
+    std::mutex mu;
+    std::multiset<int64_t> live;
+    void add_view(int64_t n) { std::lock_guard<std::mutex> lk(mu); live.insert(n); }
+    void drop_view(int64_t n) { std::lock_guard<std::mutex> lk(mu); auto it = live.find(n); if (it != live.end()) live.erase(it); }
+    int64_t max_live() { std::lock_guard<std::mutex> lk(mu); return live.empty() ? 0 : *live.rbegin(); }
+    // An append in place writes rows [n_old, n_new): allowed only while no live view reaches beyond n_old — decided AND claimed
+    // (the new view registered) under one lock, so that two host threads appending to copies of one model cannot both take the
+    // rows (the loser refits into storage of its own: copy-on-write).  A failed append gives the claim back (drop_view).
+    bool claim_rows(int64_t n_old, int64_t n_new) {
+        std::lock_guard<std::mutex> lk(mu);
+        if (!live.empty() && *live.rbegin() > n_old) return false;
+        live.insert(n_new);
+        return true;
+    }
+    ABO_STORAGE_BUFS(ABO_DEVBUF_MEMBER)
+    void set_device(int dv) {
+        dev = dv;
+#define X(name) name.dev = dv;
+        ABO_STORAGE_BUFS(X)
+#undef X
+    }
+    void release_all() {
+#define X(name) name.release();
+        ABO_STORAGE_BUFS(X)
+#undef X
+    }
+};
+inline void storage_unref(Storage* st) {
+    if (st && st->refs.fetch_sub(1) == 1) { st->release_all(); delete st; }
+}
+
+}  // namespace abo
+#pragma GCC visibility pop
+
+// Every device buffer of a handle, named ONCE: the members, set_device() and free_all() all come from this list.
+//   alpha … scal                 the fit: α, the bordered append's vext and work vectors, the workspace T, status word, scalars
+//   Zdev … top_idx               posterior workspace: staged candidates, K_XZ chunk, partial sums, μ chunk, full-length arrays, top-k scratch
+//   oz_WR … oz_badc              int8-residue contraction (ozaki.hip): residue planes of this view's W (valid for oz_gen / oz_N /
+//                                oz_plan.n), row scales and flags, and the per-chunk scratch
+//   pr_ub … pr_ti                pruned selection: bounds, gathered points, their scores, survivor list, scan scratch, threshold pairs
+//   pr_mut, pr_eps, pr_nrm       its bound pass: μ̃ and ε of every candidate, the norms ε is built from (kgen_tail.hip)
+//   pr_ub2, pr_mut2, pr_eps2     second bound level: bounds, μ̃ and ε of the first level's survivors, in list order
+//   ystar                        the samples of an abo_*_mes call that came from host memory
+//   oz_WRb … oz_delta            the bound pass's short residue plan (ozaki.hip: "the guarded bound"): the residue planes of the first
+//                                bound rows of W under it, their row scales, flags and guards — rebuilt by every bound pass
+//   loo_T                        abo_loo_grad: T = K̃⁻¹·∂K/∂log ℓ (K̃⁻¹ itself sits in T, ∂K/∂log ℓ in Kxz)
+//   cov_Zs, cov_V, cov_C         abo_predict_cov: the scaled points of both sets, V_a / V_b = K_ZX·L⁻ᵀ, the padded covariance block
+//   pr_head … pr_hdl             the fused first-level head (kgen_head32.hip): head of μ̃ and S̃ of every candidate, fp32 fragments of
+//                                W's head, δ and ‖W_i‖₁
+#define ABO_GP_BUFS(X)                                                                                                              \
+    X(alpha) X(vext) X(tvec) X(T) X(info) X(scal)                                                                                   \
+    X(Zdev) X(Kxz) X(partial) X(mu_c) X(mu_all) X(var_all) X(score_all) X(tk_keys0) X(tk_keys1) X(tk_idx0) X(tk_idx1) X(top_val) X(top_idx) \
+    X(oz_WR) X(oz_sexp) X(oz_badr) X(oz_KR) X(oz_U) X(oz_badc)                                                                      \
+    X(pr_ub) X(pr_z) X(pr_sc) X(pr_sel) X(pr_blk) X(pr_tv) X(pr_ti)                                                                 \
+    X(pr_mut) X(pr_eps) X(pr_nrm) X(pr_ub2) X(pr_mut2) X(pr_eps2)                                                                   \
+    X(ystar) X(oz_WRb) X(oz_sexpb) X(oz_badrb) X(oz_delta) X(loo_T) X(cov_Zs) X(cov_V) X(cov_C)                                     \
+    X(pr_head) X(pr_ssq) X(pr_wf) X(pr_hdl)
+
+struct abo_gp {
+    std::atomic<int> refs{1};
+    abo_params prm{};
+    abo::ExecCtx* ctx = nullptr;
+    hipStream_t stream = nullptr;      // == ctx->stream
+    abo::Storage* st = nullptr;        // null until conditioned on data
+    bool fitted = false;
+    int64_t N = 0, Np = 0;             // this view's number of factor rows and its 128-padded size
+    int64_t npts = 0;                  // training points (== N unless gradient-enhanced: N = p_out·npts)
+    int d = 0, dp = 0;
+    int p_out = 1;                     // outputs per point: 1 = StandardGP, d+1 = GradientGP (f + gradient)
+    double mean_vec[abo::MAX_P] = {0}; // prior mean per output (gradConstMean; [0] = mean_c for p_out == 1)
+    double logdet = 0.0, quad = 0.0;
+    // bordered-append bookkeeping (valid when this view was produced by abo_append)
+    bool from_append = false;
+    double ap_s2 = 0.0, ap_beta = 0.0; // Schur complement l_nn² and (y* − μ(x*))/l_nn²
+    uint64_t ap_serial = 0;            // process-wide id of the append that made this view (never reused): what a down-date column is tagged with
+    std::vector<double> ap_x;          // the point a one-row append added, as the host handed it over (abo_cand_downdate matches it against the q-EI chain)
+    double ap_s2v[abo::MAX_P] = {0}, ap_betav[abo::MAX_P] = {0};   // gradient-enhanced append: the same per appended row (p_out of them)
+    ABO_GP_BUFS(ABO_DEVBUF_MEMBER)
+    // host landing zone of the fit's scalars ({log det, δᵀα} and the LAPACK-style info): read back by one asynchronous copy at
+    // the end of the fit's launches and looked at after the NEXT stream synchronisation — the fit's own (abo_fit) or, for
+    // abo_fit_acq, the one behind the acquisition launches that were queued right behind the fit
+    double h_sc_[2] = {0.0, 0.0};      // (fallback landing zone when the context has no pinned block)
+    int64_t h_info_ = 0;
+    double* h_sc() { return ctx && ctx->pin ? reinterpret_cast<double*>(ctx->pin) : h_sc_; }
+    int64_t& h_info() { return ctx && ctx->pin ? *reinterpret_cast<int64_t*>(ctx->pin + 16) : h_info_; }
+    bool fit_small_path = false;
+    const double* in_x = nullptr;      // the caller's device arrays while a one-launch fit reads them itself (abo_fit: no staging copies);
+    const double* in_y = nullptr;      // null: the model's own copies
+    // int8-residue contraction (ozaki.hip): engine choice and the plan the cached planes of W belong to
+    int oz_engine = ABO_CONTRACT_AUTO, oz_nmod = 0;
+    int* oz_ctr_clean = nullptr;       // the tile-counter block of oz_badc known to hold zeros (OzVarArgs::ctr_clean)
+    abo::OzPlan oz_plan{};
+    bool oz_prepare_pending = false;  // events 8/9 of the current call bracket a rebuild of the residue planes of W (read with its timings)
+    uint64_t oz_gen = 0;
+    int64_t oz_N = -1;
+    // the posterior passes of the current call, in launch order (their per-chunk events are read back with them): the pruned top-k
+    // selection of abo_acq runs up to five (two bound levels, threshold, survivors or the fallback's full pass), everything else one
+    struct PostPass { int64_t chunk0, nchunk, M, rows; int nmod; bool head32 = false; };   // first chunk's event slot, chunks, candidate rows, rows of W contracted, moduli launched
+                                                                                       // (0 and head32: the fused fp32 head of a first bound level, one launch, timed in its first chunk's contraction slot)
+    std::vector<PostPass> passes;
+    int ph_rows = 0;                                           // rows of the last fused head (0: the last bound pass ran none)
+    abo_prune_stats pst{};
+    struct PruneLevels { int64_t rows1, s1, rows2, s2; double ms1, ms2; } plv{};      // abo_get_prune_levels
+    abo::OzPlan oz_plan_b{};                                   // the bound pass's short residue plan
+    int pb_rows = 0, pb_sK = 0;                                // rows the last bound pass rebuilt under it, and its scale of K
+    abo_timings tm{};
+
+    std::vector<hipEvent_t>& evs() { return ctx->ev; }
+    int64_t ld() const { return st->cap; }
+
+    void set_device(int dev) {
+#define X(name) name.dev = dev;
+        ABO_GP_BUFS(X)
+#undef X
+    }
+    __attribute__((visibility("hidden"))) void free_all();      // api.hip: buffers to the pool, the view off its storage, the context to the free list
+    hipError_t events(size_t n) {
+        while (ctx->ev.size() < n) {
+            hipEvent_t e;
+            hipError_t r = hipEventCreate(&e);
+            if (r != hipSuccess) return r;
+            ctx->ev.push_back(e);
+        }
+        return hipSuccess;
+    }
+};
+
+#pragma GCC visibility push(hidden)
+namespace abo {
+
+int32_t make_terms(const abo_gp* g, const abo_acq_term* terms, int32_t n, AcqTerms* out, const char* fn);
+int32_t mes_check_samples(const double* ystar, int32_t S, int32_t ys_space, const char* fn);
+int32_t mes_check_handle(abo_gp* g, const char* fn);
+int32_t mes_terms(abo_gp* g, const double* ystar, int32_t S, int32_t ys_space, AcqTerms* t);
+// ---- exact top-k without the full variance contraction (DESIGN.md "Pruned top-k selection") -------------------------------------------
+// The sum of squares over the first R rows of V = L⁻¹K_XZ is the variance reduction from the first R training points alone, so
+// σ²_R = k_zz − Σ_{i<R} V_ij² ≥ σ², and EI, LogEI and UCB (β ≥ 0) do not decrease with σ: the score of (μ, σ²_R) bounds the score from above.
+// W = L⁻¹ being triangular, its first R rows cost (R/N)² of the contraction.
+struct PrunePlan {
+    bool eligible;
+    int rblocks;            // 256-row blocks of W in the bound pass
+    int64_t k0;             // candidates whose exact scores set the threshold
+    int64_t max_survivors;  // more than this: the ordinary full pass runs instead of the survivor pass
+    int rblocks0;           // 256-row blocks of a first, narrower bound level over all candidates (0: none — one bound pass, at rblocks)
+    int64_t level2_min;     // the pass at rblocks runs on the first level's survivors when there are more than this many
+    bool tail32;            // the first level's tail of the mean in fp32 (kgen_tail32.hip); nothing without a first level
+    bool head32;            // … and its head — head of the mean, guarded sum of squares — by the fused fp32-MFMA kernel (kgen_head32.hip)
+};
+PrunePlan prune_plan(int64_t rows, int64_t M, int k, bool want_scores, int kind, double p0, int p_out, bool int8_fused, int d);
+// Overrides of the pruned selection's decisions, "not set" by default and for ever in the shipped library: nothing there writes them, so
+// every decision is what the environment and the defaults give.  The abo_test_prune_* hooks (test_hooks.hip) are their only writers.
+extern std::atomic<int> g_prune_bound_moduli;       // abo_test_prune_bound_moduli: 0 = the environment's / the default
+extern std::atomic<int> g_prune_force_rblocks;      // abo_test_prune_force: row blocks of the bound pass (0 = the rule); mode 1 = a threshold
+extern std::atomic<int> g_prune_force_mode;         // of −Inf (every candidate survives: the worst case, on any data), 2 = as ABO_ACQ_PRUNE=0
+extern std::atomic<int> g_prune_pre_rblocks;        // abo_test_prune_levels: row blocks of the first level (−1 = none, 0 = the rule)
+extern std::atomic<int64_t> g_prune_level2_min;     // … and the survivor count above which the second runs (−1 = the rule)
+extern std::atomic<int> g_prune_tail32;             // abo_test_prune_tail32: 0 / 1 = the first level's tail in fp64 / fp32, −1 = the environment's
+extern std::atomic<int> g_prune_head32;             // abo_test_prune_head32: 0 / 1 = the first level's head on the int8 engine / fused in fp32, −1 = the environment's
+
+struct RefineOpts { int max_iter, ls_max, history; double g_tol, f_abstol, x_abstol; };
+RefineOpts refine_defaults(const abo_refine_opts* o);
+int32_t check_refinable(abo_gp* g, int32_t d, const char* fn);
+// bounds (2·d doubles: lower, upper), starts (S·d) and the outputs all in DEVICE memory; asynchronous on the handle's stream
+int32_t refine_device(abo_gp* g, const AcqTerms& terms, const double* bounds_d, const double* starts_d, int S, RefineOpts o,
+                      double* x_out_d, double* f_out_d, int* iters_d, int grad_only);
+
+}  // namespace abo
+#pragma GCC visibility pop

@@ -28,8 +28,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/abo_hip.h"
-#include "abo_internal.h"
+#include "abo_state.h"
 #include "abo_kernels.h"
 #include "kgen_core.h"
 
@@ -39,6 +38,9 @@ namespace {
 
 thread_local char g_err[512] = "";
 
+}  // namespace
+
+namespace abo {    // shared with test_hooks.hip (abo_state.h)
 int32_t fail(int32_t code, const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
@@ -46,14 +48,6 @@ int32_t fail(int32_t code, const char* fmt, ...) {
     va_end(ap);
     return code;
 }
-
-#define HIPCHK(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess)                                                                          \
-            return fail(e_ == hipErrorOutOfMemory ? ABO_ENOMEM : ABO_EHIP, "%s failed: %s (%s:%d)", #expr, \
-                        hipGetErrorString(e_), __FILE__, __LINE__);                                    \
-    } while (0)
 
 // The end of a call waits for its stream.  hipStreamSynchronize blocks the host thread on an interrupt as soon as the work is not done at
 // once: 20 – 40 µs from the last kernel's end to the return, three times a BO step on the incremental path (0.7 ms) and once per 0.15 ms
@@ -78,6 +72,9 @@ hipError_t wait_stream(hipStream_t s) {
     }
     return hipStreamSynchronize(s);
 }
+}  // namespace abo
+
+namespace {
 
 // ---- process teardown guard (abo_internal.h) -------------------------------------------------------------------------------
 std::atomic<bool> g_exiting{false};
@@ -122,6 +119,9 @@ size_t round_size(size_t bytes) {
     return (bytes + g - 1) / g * g;
 }
 
+}  // namespace
+
+namespace abo {    // shared with test_hooks.hip (abo_state.h)
 hipError_t pool_alloc(int dev, size_t bytes, void** p, size_t* cap) {
     const size_t want = round_size(bytes);
     Pool& pl = g_pool[dev & 15];
@@ -176,6 +176,9 @@ void pool_free(int dev, void* p, size_t cap) {
     for (void* q : evict) (void)hipFree(q);
     if (!kept) (void)hipFree(p);
 }
+}  // namespace abo
+
+namespace {
 
 void pool_trim(int dev) {
     if (g_exiting.load()) return;
@@ -189,34 +192,6 @@ void pool_trim(int dev) {
     for (void* q : drop) (void)hipFree(q);
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    int dev = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { release(); }            // every early return (HIPCHK) hands its buffers back to the pool
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        release();
-        return pool_alloc(dev, bytes, &p, &cap);
-    }
-    void release() { if (p) pool_free(dev, p, cap); p = nullptr; cap = 0; }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-
-// stream + events of a handle, recycled the same way (hipStreamCreate / ~400 hipEventCreate per step otherwise)
-// pin: a small page-locked host block that lives with the context.  A device-to-host copy of a few bytes into PAGEABLE memory blocks
-// the host until it has happened (12 – 14 µs each on this runtime, tools/memcpy_probe.hip; 2.5 – 3.7 µs and asynchronous into
-// pinned memory) — four of them were a quarter of a BO step at the reference's own sizes.  The fit's scalars and the selected
-// (score, index) pairs land here and are copied on by the host after the call's one synchronisation.
-constexpr size_t PIN_BYTES = 32768, PIN_OUT = 64;      // [0,16) fit scalars, [16,24) info, [PIN_OUT, …) selected pairs
-struct ExecCtx {
-    hipStream_t stream = nullptr;
-    std::vector<hipEvent_t> ev;
-    char* pin = nullptr;
-};
 std::mutex g_ctx_mu;
 std::vector<ExecCtx*> g_ctx_free[16];
 
@@ -253,21 +228,17 @@ int dp_for(int d) {
     return p;
 }
 
-// a local scratch buffer of one call: on every exit path the stream is drained before the block goes back to the pool
-// (an error return must not hand memory that queued work still touches to the next handle)
-struct ScratchBuf {
-    DevBuf b;
-    hipStream_t s;
-    ScratchBuf(int dev, hipStream_t st) : s(st) { b.dev = dev; }
-    ~ScratchBuf() { if (b.p) { (void)wait_stream(s); b.release(); } }
-};
+}  // namespace
 
+namespace abo {    // shared with test_hooks.hip (abo_state.h)
 std::atomic<uint64_t> g_storage_gen{1};
+}  // namespace abo
+
+namespace {
 std::atomic<uint64_t> g_append_serial{1};
 
 // contraction engine of the posterior variance: process default (ABO_CONTRACTION = auto | fp64 | int8 | int8:<moduli>),
 // overridable per handle (abo_set_contraction)
-constexpr int OZ_DEFAULT_NMOD = 14;   // P ≈ 2^110: the fixed-point images keep 50+ bits of W per row and 52–53 bits of K_XZ
 constexpr int OZ_AUTO_MIN_NP = 1280;  // below this the fp64 kernels win (tools/engine_crossover.py, profiles/r06_engine_crossover.txt: fp64/int8 = 0.97 at
                                       // 1024, 1.09 at 1280, 1.21 at 1536, 1.90 at 4096; round 2's engine crossed at 1536)
 std::atomic<int> g_oz_engine{-1}, g_oz_nmod{OZ_DEFAULT_NMOD};
@@ -292,152 +263,21 @@ void oz_defaults(int* engine, int* nmod) {
 
 }  // namespace
 
-// Heavy device state, shared by every view (copy / appended model) that descends from one fit.
-// Rows < N of Xs / delta / L / W / WT are immutable for every live view of size N; an append only
-// writes row N of the largest live view, so older views stay valid and rollback is free.
-struct Storage {
-    std::atomic<int> refs{1};
-    // process-wide unique id: what a candidate set remembers of the factor it is synced with (a freed Storage's address
-    // is readily reused by the next refit of the same size; its id never is)
-    const uint64_t gen = g_storage_gen.fetch_add(1);
-    int dev = 0;
-    int d = 0, dp = 0;
-    int64_t cap = 0;        // padded capacity = leading dimension of K/W/WT (multiple of 128)
-    double noise_used = 0.0;
-    // sizes N of the live views on this storage.  A view may append in place only if no live view
-    // is larger (rows ≥ its N are then dead: stale rows of discarded fantasy branches are masked
-    // everywhere by the view's own N, and the append overwrites row N).
-    std::mutex mu;
-    std::multiset<int64_t> live;
-    void add_view(int64_t n) { std::lock_guard<std::mutex> lk(mu); live.insert(n); }
-    void drop_view(int64_t n) { std::lock_guard<std::mutex> lk(mu); auto it = live.find(n); if (it != live.end()) live.erase(it); }
-    int64_t max_live() { std::lock_guard<std::mutex> lk(mu); return live.empty() ? 0 : *live.rbegin(); }
-    // An append in place writes rows [n_old, n_new): allowed only while no live view reaches beyond n_old — decided AND claimed
-    // (the new view registered) under one lock, so that two host threads appending to copies of one model cannot both take the
-    // rows (the loser refits into storage of its own: copy-on-write).  A failed append gives the claim back (drop_view).
-    bool claim_rows(int64_t n_old, int64_t n_new) {
-        std::lock_guard<std::mutex> lk(mu);
-        if (!live.empty() && *live.rbegin() > n_old) return false;
-        live.insert(n_new);
-        return true;
+void abo_gp::free_all() {
+#define X(name) name.release();
+    ABO_GP_BUFS(X)
+#undef X
+    oz_N = -1;
+    oz_ctr_clean = nullptr;
+    if (st && fitted) st->drop_view(N);
+    storage_unref(st);
+    st = nullptr;
+    if (ctx) {
+        std::lock_guard<std::mutex> lk(g_ctx_mu);
+        g_ctx_free[prm.device & 15].push_back(ctx);
+        ctx = nullptr; stream = nullptr;
     }
-    DevBuf Xraw, Xs, ybuf, delta, K, W, WT;
-    void set_device(int dv) {
-        dev = dv;
-        DevBuf* all[] = {&Xraw, &Xs, &ybuf, &delta, &K, &W, &WT};
-        for (DevBuf* b : all) b->dev = dv;
-    }
-    void release_all() {
-        DevBuf* all[] = {&Xraw, &Xs, &ybuf, &delta, &K, &W, &WT};
-        for (DevBuf* b : all) b->release();
-    }
-};
-
-void storage_unref(Storage* st) {
-    if (st && st->refs.fetch_sub(1) == 1) { st->release_all(); delete st; }
 }
-
-struct abo_gp {
-    std::atomic<int> refs{1};
-    abo_params prm{};
-    ExecCtx* ctx = nullptr;
-    hipStream_t stream = nullptr;      // == ctx->stream
-    Storage* st = nullptr;             // null until conditioned on data
-    bool fitted = false;
-    int64_t N = 0, Np = 0;             // this view's number of factor rows and its 128-padded size
-    int64_t npts = 0;                  // training points (== N unless gradient-enhanced: N = p_out·npts)
-    int d = 0, dp = 0;
-    int p_out = 1;                     // outputs per point: 1 = StandardGP, d+1 = GradientGP (f + gradient)
-    double mean_vec[MAX_P] = {0};      // prior mean per output (gradConstMean; [0] = mean_c for p_out == 1)
-    double logdet = 0.0, quad = 0.0;
-    // bordered-append bookkeeping (valid when this view was produced by abo_append)
-    bool from_append = false;
-    double ap_s2 = 0.0, ap_beta = 0.0; // Schur complement l_nn² and (y* − μ(x*))/l_nn²
-    uint64_t ap_serial = 0;            // process-wide id of the append that made this view (never reused): what a down-date column is tagged with
-    std::vector<double> ap_x;          // the point a one-row append added, as the host handed it over (abo_cand_downdate matches it against the q-EI chain)
-    double ap_s2v[MAX_P] = {0}, ap_betav[MAX_P] = {0};   // gradient-enhanced append: the same per appended row (p_out of them)
-    DevBuf alpha, vext, tvec, T, info, scal;
-    DevBuf loo_T;                      // abo_loo_grad: T = K̃⁻¹·∂K/∂log ℓ (K̃⁻¹ itself sits in T, ∂K/∂log ℓ in Kxz)
-    DevBuf cov_Zs, cov_V, cov_C;       // abo_predict_cov: the scaled points of both sets, V_a / V_b = K_ZX·L⁻ᵀ, the padded covariance block
-    // host landing zone of the fit's scalars ({log det, δᵀα} and the LAPACK-style info): read back by one asynchronous copy at
-    // the end of the fit's launches and looked at after the NEXT stream synchronisation — the fit's own (abo_fit) or, for
-    // abo_fit_acq, the one behind the acquisition launches that were queued right behind the fit
-    double h_sc_[2] = {0.0, 0.0};      // (fallback landing zone when the context has no pinned block)
-    int64_t h_info_ = 0;
-    double* h_sc() { return ctx && ctx->pin ? reinterpret_cast<double*>(ctx->pin) : h_sc_; }
-    int64_t& h_info() { return ctx && ctx->pin ? *reinterpret_cast<int64_t*>(ctx->pin + 16) : h_info_; }
-    bool fit_small_path = false;
-    const double* in_x = nullptr;      // the caller's device arrays while a one-launch fit reads them itself (abo_fit: no staging copies);
-    const double* in_y = nullptr;      // null: the model's own copies
-    // posterior workspace
-    DevBuf Zdev, Kxz, partial, mu_c, mu_all, var_all, score_all, tk_keys0, tk_keys1, tk_idx0, tk_idx1, top_val, top_idx;
-    DevBuf ystar;                      // the samples of an abo_*_mes call that came from host memory
-    // int8-residue contraction (ozaki.hip): engine choice, the residue planes of this view's W (valid for oz_gen / oz_N /
-    // oz_plan.n) and the per-chunk scratch
-    int oz_engine = ABO_CONTRACT_AUTO, oz_nmod = 0;
-    int* oz_ctr_clean = nullptr;       // the tile-counter block of oz_badc known to hold zeros (OzVarArgs::ctr_clean)
-    OzPlan oz_plan{};
-    bool oz_prepare_pending = false;  // events 8/9 of the current call bracket a rebuild of the residue planes of W (read with its timings)
-    uint64_t oz_gen = 0;
-    int64_t oz_N = -1;
-    // the posterior passes of the current call, in launch order (their per-chunk events are read back with them): the pruned top-k
-    // selection of abo_acq runs up to five (two bound levels, threshold, survivors or the fallback's full pass), everything else one
-    struct PostPass { int64_t chunk0, nchunk, M, rows; int nmod; bool head32 = false; };   // first chunk's event slot, chunks, candidate rows, rows of W contracted, moduli launched
-                                                                                       // (0 and head32: the fused fp32 head of a first bound level, one launch, timed in its first chunk's contraction slot)
-    std::vector<PostPass> passes;
-    DevBuf pr_ub, pr_z, pr_sc, pr_sel, pr_blk, pr_tv, pr_ti;   // pruned selection: bounds, gathered points, their scores, survivor list, scan scratch, threshold pairs
-    DevBuf pr_mut, pr_eps, pr_nrm;                             // its bound pass: μ̃ and ε of every candidate, the norms ε is built from (kgen_tail.hip)
-    DevBuf pr_head, pr_ssq, pr_wf, pr_hdl;                     // the fused first-level head (kgen_head32.hip): head of μ̃ and S̃ of every candidate, fp32 fragments of W's head, δ and ‖W_i‖₁
-    int ph_rows = 0;                                           // rows of the last fused head (0: the last bound pass ran none)
-    DevBuf pr_ub2, pr_mut2, pr_eps2;                           // second bound level: bounds, μ̃ and ε of the first level's survivors, in list order
-    abo_prune_stats pst{};
-    struct PruneLevels { int64_t rows1, s1, rows2, s2; double ms1, ms2; } plv{};      // abo_get_prune_levels
-    // the bound pass's short residue plan (ozaki.hip: "the guarded bound"): the plan, the residue planes of the first bound rows of W
-    // under it, their row scales, flags and guards — rebuilt by every bound pass (pb_rows of them by the last one, at pb_sK)
-    OzPlan oz_plan_b{};
-    DevBuf oz_WRb, oz_sexpb, oz_badrb, oz_delta;
-    int pb_rows = 0, pb_sK = 0;
-    DevBuf oz_WR, oz_sexp, oz_badr, oz_KR, oz_U, oz_badc;
-    abo_timings tm{};
-
-    std::vector<hipEvent_t>& evs() { return ctx->ev; }
-    int64_t ld() const { return st->cap; }
-
-    void set_device(int dev) {
-        DevBuf* all[] = {&alpha, &vext, &tvec, &T, &info, &scal, &Zdev, &Kxz, &partial, &mu_c, &mu_all, &var_all,
-                         &score_all, &tk_keys0, &tk_keys1, &tk_idx0, &tk_idx1, &top_val, &top_idx,
-                         &oz_WR, &oz_sexp, &oz_badr, &oz_KR, &oz_U, &oz_badc, &pr_ub, &pr_z, &pr_sc, &pr_sel, &pr_blk, &pr_tv, &pr_ti,
-                         &pr_mut, &pr_eps, &pr_nrm, &pr_ub2, &pr_mut2, &pr_eps2, &ystar, &oz_WRb, &oz_sexpb, &oz_badrb, &oz_delta, &loo_T, &cov_Zs, &cov_V, &cov_C};
-        for (DevBuf* b : all) b->dev = dev;
-    }
-
-    void free_all() {
-        DevBuf* all[] = {&alpha, &vext, &tvec, &T, &info, &scal, &Zdev, &Kxz, &partial, &mu_c, &mu_all, &var_all,
-                         &score_all, &tk_keys0, &tk_keys1, &tk_idx0, &tk_idx1, &top_val, &top_idx,
-                         &oz_WR, &oz_sexp, &oz_badr, &oz_KR, &oz_U, &oz_badc, &pr_ub, &pr_z, &pr_sc, &pr_sel, &pr_blk, &pr_tv, &pr_ti,
-                         &pr_mut, &pr_eps, &pr_nrm, &pr_ub2, &pr_mut2, &pr_eps2, &ystar, &oz_WRb, &oz_sexpb, &oz_badrb, &oz_delta, &loo_T, &cov_Zs, &cov_V, &cov_C};
-        for (DevBuf* b : all) b->release();
-        oz_N = -1;
-        oz_ctr_clean = nullptr;
-        if (st && fitted) st->drop_view(N);
-        storage_unref(st);
-        st = nullptr;
-        if (ctx) {
-            std::lock_guard<std::mutex> lk(g_ctx_mu);
-            g_ctx_free[prm.device & 15].push_back(ctx);
-            ctx = nullptr; stream = nullptr;
-        }
-    }
-    hipError_t events(size_t n) {
-        while (ctx->ev.size() < n) {
-            hipEvent_t e;
-            hipError_t r = hipEventCreate(&e);
-            if (r != hipSuccess) return r;
-            ctx->ev.push_back(e);
-        }
-        return hipSuccess;
-    }
-};
 
 // candidate set resident in HBM with its posterior (C5: O(N·M) down-dates instead of re-evaluation)
 struct abo_cand {
@@ -452,11 +292,13 @@ struct abo_cand {
     uint64_t dd_serial = 0;
     int dd_src = -1, dd_chain = -1;
     uint64_t mu_epoch = 1;                // grows whenever the stored μ — and with it the exclusions — may have changed other than by a down-date
-    DevBuf Z, mu, var, score, cdot, tk_keys0, tk_keys1, tk_idx0, tk_idx1, top_val, top_idx, mu_bak, var_bak;
-    // resident K_ZX (candidate-major, kzx_ld doubles per candidate, column k = training row k of synced_st): kept when
+#define ABO_CAND_BUFS(X)                                                                                                            \
+    X(Z) X(mu) X(var) X(score) X(cdot) X(tk_keys0) X(tk_keys1) X(tk_idx0) X(tk_idx1) X(top_val) X(top_idx) X(mu_bak) X(var_bak)      \
+    X(Kzx) X(qblk) X(qchain) X(qwork) X(qrec) X(qmu) X(qvar) X(qdev)
+    ABO_CAND_BUFS(ABO_DEVBUF_MEMBER)
+    // Kzx: resident K_ZX (candidate-major, kzx_ld doubles per candidate, column k = training row k of synced_st): kept when
     // it fits the budget (ABO_CAND_KZX_GIB, default 64), so that a down-date streams it once instead of re-evaluating
     // N·M kernel values; kzx_ld = 0 → not resident, the down-date recomputes
-    DevBuf Kzx;
     int64_t kzx_ld = 0;
     // block form of greedy q-EI (qei.hip).  Base = the model the set was synced with when the state was last reset (gen, N).
     //   qblk   [nblk_cap][T16][Mp]  covariances Cov(z, x_t) of the block points under the model of the block's build (ring of blocks)
@@ -482,17 +324,16 @@ struct abo_cand {
         int builds = 0, batch0 = 0;               // batch0: nchain when the batch began
         double block_ms = 0.0, pass_ms = 0.0, pass_bytes = 0.0, pass_flop = 0.0;
     } qei;
-    DevBuf qblk, qchain, qwork, qrec, qmu, qvar, qdev;
     void set_device(int dev) {
         device = dev;
-        DevBuf* all[] = {&Z, &mu, &var, &score, &cdot, &tk_keys0, &tk_keys1, &tk_idx0, &tk_idx1, &top_val, &top_idx, &mu_bak, &var_bak, &Kzx,
-                         &qblk, &qchain, &qwork, &qrec, &qmu, &qvar, &qdev};
-        for (DevBuf* b : all) b->dev = dev;
+#define X(name) name.dev = dev;
+        ABO_CAND_BUFS(X)
+#undef X
     }
     void free_all() {
-        DevBuf* all[] = {&Z, &mu, &var, &score, &cdot, &tk_keys0, &tk_keys1, &tk_idx0, &tk_idx1, &top_val, &top_idx, &mu_bak, &var_bak, &Kzx,
-                         &qblk, &qchain, &qwork, &qrec, &qmu, &qvar, &qdev};
-        for (DevBuf* b : all) b->release();
+#define X(name) name.release();
+        ABO_CAND_BUFS(X)
+#undef X
         kzx_ld = 0;
         qei = Qei();
     }
@@ -860,24 +701,24 @@ int32_t oz_planes_of_w(abo_gp* g) {
     return ABO_OK;
 }
 
-// mu / var / score for M candidates into device arrays (any may be null)
-// pc outputs per candidate (1 = function value; p_out = all outputs of a gradient-enhanced GP), rows by outputs
-// unless point_major; mu/var/score arrays then have pc·M entries.
-// kstore / ldstore: write K_XZ into a caller-owned candidate-major matrix (pad_up(M,128) rows of ldstore ≥ Np doubles)
-// instead of the per-chunk scratch — the resident K_ZX of a candidate set.
-// rblocks > 0 (the bound pass of the pruned selection; int8 engine with generator-written planes only, else PRUNE_UNAVAILABLE):
-// the contraction covers the first rblocks 256-row blocks of W — var / score then come from σ²_R ≥ σ² and from μ̃ − ε ≤ μ: the mean's
-// columns past those blocks are summed by the cheaper launch_kgen_tail, which also proves ε ≥ |μ̃ − μ| (kgen_tail.hip).
-// more: a further pass of the same call — its events and counts are kept next to those of the passes before it.
-// level2: a bound pass over the survivors of a first one — μ̃ and ε go to buffers of their own.
-// tail32: the tail of a bound pass by launch_kgen_tail32 (fp32 pairs, a wider proven ε: kgen_tail32.hip) — the M-wide first level.
-// head32 (with tail32 only): the head of that pass — head of the mean and guarded sum of squares — by ONE launch of kgen_head32.hip over
-// all candidates in place of head generator, residue GEMM and reconstruction per chunk; the chunk loop then runs tail and epilogue alone.
+// what the chunked posterior pass does beyond mu / var / score of M candidates
+struct PostOpts {
+    int pc = 1;                  // outputs per candidate: 1 = function value; p_out = all outputs of a gradient-enhanced GP (mu / var / score arrays then have pc·M entries)
+    bool point_major = false;    // with pc > 1: the rows go point by point (i·pc + q) instead of output by output (q·M + i)
+    double* kstore = nullptr;    // write K_XZ into a caller-owned candidate-major matrix (pad_up(M,128) rows of ldstore ≥ Np doubles)
+    int64_t ldstore = 0;         // instead of the per-chunk scratch — the resident K_ZX of a candidate set
+    // rblocks > 0 (the bound pass of the pruned selection; int8 engine with generator-written planes only, else PRUNE_UNAVAILABLE):
+    // the contraction covers the first rblocks 256-row blocks of W — var / score then come from σ²_R ≥ σ² and from μ̃ − ε ≤ μ: the mean's
+    // columns past those blocks are summed by the cheaper launch_kgen_tail, which also proves ε ≥ |μ̃ − μ| (kgen_tail.hip).
+    int rblocks = 0;
+    bool more = false;           // a further pass of the same call — its events and counts are kept next to those of the passes before it
+    bool level2 = false;         // a bound pass over the survivors of a first one — μ̃ and ε go to buffers of their own
+    bool tail32 = false;         // the tail of a bound pass by launch_kgen_tail32 (fp32 pairs, a wider proven ε: kgen_tail32.hip) — the M-wide first level
+    // head32 (with tail32 only): the head of that pass — head of the mean and guarded sum of squares — by ONE launch of kgen_head32.hip over
+    // all candidates in place of head generator, residue GEMM and reconstruction per chunk; the chunk loop then runs tail and epilogue alone.
+    bool head32 = false;
+};
 constexpr int32_t PRUNE_UNAVAILABLE = -100;
-
-#ifdef ABO_TEST_HOOKS
-std::atomic<int> g_prune_bound_moduli{0};       // abo_test_prune_bound_moduli: 0 = the environment's / the default
-#endif
 
 // moduli of the bound pass's residue plan: 8 (default), 9, 10 — a short plan with the guard of ozaki.hip — or 14: the handle's plan,
 // exact contraction, as before the short plan existed.  ABO_PRUNE_BOUND_MODULI; any other value (11 – 13, below 8, text) is IGNORED and
@@ -888,15 +729,17 @@ int prune_bound_moduli() {
         const int v = e ? atoi(e) : 0;
         return (kgen_short_moduli(v) || v == 14) ? v : 8;
     }();
-#ifdef ABO_TEST_HOOKS
-    if (g_prune_bound_moduli.load() > 0) return g_prune_bound_moduli.load();
-#endif
+    if (g_prune_bound_moduli.load(std::memory_order_relaxed) > 0) return g_prune_bound_moduli.load(std::memory_order_relaxed);
     return env;
 }
 
+// mu / var / score for M candidates into device arrays (any may be null)
 int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0, double best_y, double* mu_out,
-                  double* var_out, double* score_out, int pc = 1, int point_major = 0, double* kstore = nullptr,
-                  int64_t ldstore = 0, int rblocks = 0, bool more = false, bool level2 = false, bool tail32 = false, bool head32 = false) {
+                  double* var_out, double* score_out, const PostOpts& o = {}) {
+    const int pc = o.pc, point_major = o.point_major ? 1 : 0, rblocks = o.rblocks;
+    double* const kstore = o.kstore;
+    const int64_t ldstore = o.ldstore;
+    const bool more = o.more, level2 = o.level2, tail32 = o.tail32;
     const int64_t M = Mpts * pc;                         // candidate rows
     hipStream_t s = g->stream;
     const int64_t Np = g->Np;
@@ -935,7 +778,7 @@ int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0
     // the bound pass on a short plan: its own planes of the first 256·rblocks rows of W, row scales and guards — rebuilt every call (one
     // row-scale and one quantiser launch over R × R; appends, abo_update, a changed R and shared factor storage would all have to
     // invalidate a cache)
-    head32 = head32 && tail32 && rblocks > 0 && oz && (int64_t)256 * rblocks <= g->npts && 256 * rblocks <= 2048;
+    const bool head32 = o.head32 && tail32 && rblocks > 0 && oz && (int64_t)256 * rblocks <= g->npts && 256 * rblocks <= 2048;
     const int nb = rblocks > 0 && !head32 ? prune_bound_moduli() : 0;
     const bool shortp = nb > 0 && nb != g->oz_plan.n;
     const double sf2k = g->p_out > 1 ? (pc > 1 ? 2.0 : 1.5) * g->prm.sigma_f2 : g->prm.sigma_f2;
@@ -1179,6 +1022,9 @@ void collect_posterior_timings(abo_gp* g, bool with_var) {
     g->tm.var_gemm_flop = with_var ? work : 0.0;
 }
 
+}  // namespace
+
+namespace abo {    // shared with test_hooks.hip (abo_state.h)
 int32_t check_fitted(abo_gp* g, int32_t d) {
     if (!g) return fail(ABO_EINVAL, "null handle");
     tl_phase_np = g->Np;                             // (every posterior / acquisition entry point passes here first)
@@ -1186,6 +1032,9 @@ int32_t check_fitted(abo_gp* g, int32_t d) {
     if (d != g->d) return fail(ABO_EDIM, "DimensionMismatch: candidate dimension %d, model dimension %d", d, g->d);
     return ABO_OK;
 }
+}  // namespace abo
+
+namespace {
 
 int32_t stage_candidates(abo_gp* g, const double* Z, int64_t M, int32_t z_space, const double** Zd) {
     if (z_space == ABO_DEVICE) { *Zd = Z; return ABO_OK; }
@@ -1865,7 +1714,9 @@ int32_t abo_predict_grad(abo_gp* g, const double* Z, int64_t M, int32_t d, int32
     double* var_d = nullptr;
     if (mu) { if (out_space == ABO_DEVICE) mu_d = mu; else { HIPCHK(g->mu_all.ensure(sizeof(double) * M * P)); mu_d = g->mu_all.as<double>(); } }
     if (var) { if (out_space == ABO_DEVICE) var_d = var; else { HIPCHK(g->var_all.ensure(sizeof(double) * M * P)); var_d = g->var_all.as<double>(); } }
-    rc = posterior(g, Zd, M, -1, 0.0, 0.0, mu_d, var_d, nullptr, P, 0);
+    PostOpts all_outputs;
+    all_outputs.pc = P;
+    rc = posterior(g, Zd, M, -1, 0.0, 0.0, mu_d, var_d, nullptr, all_outputs);
     if (rc) return rc;
     if (mu && out_space == ABO_HOST) { rc = copy_out(mu, mu_d, sizeof(double) * M * P, ABO_HOST, s); if (rc) return rc; }
     if (var && out_space == ABO_HOST) { rc = copy_out(var, var_d, sizeof(double) * M * P, ABO_HOST, s); if (rc) return rc; }
@@ -1907,8 +1758,7 @@ int32_t abo_acq(abo_gp* g, const double* Z, int64_t M, int32_t d, int32_t z_spac
 
 }  // extern "C"
 
-namespace {
-
+namespace abo {    // shared with test_hooks.hip (abo_state.h)
 // C-ABI terms → the kernels' form; validates kinds against the handle (GRADNORM_UCB needs gradient outputs)
 int32_t make_terms(const abo_gp* g, const abo_acq_term* terms, int32_t n, AcqTerms* out, const char* fn) {
     if (!terms || n < 1) return fail(ABO_EINVAL, "%s: an objective needs at least one term", fn);
@@ -1926,6 +1776,9 @@ int32_t make_terms(const abo_gp* g, const abo_acq_term* terms, int32_t n, AcqTer
     }
     return ABO_OK;
 }
+}  // namespace abo
+
+namespace {
 
 AcqTerms one_term(int32_t kind, double p0, double best_y) {
     AcqTerms t{};
@@ -1942,8 +1795,11 @@ AcqTerms one_term(int32_t kind, double p0, double best_y) {
 int32_t score_terms_device(abo_gp* g, const double* Zd, int64_t M, const AcqTerms& t, double* sc_d, bool more = false) {
     hipStream_t s = g->stream;
     if (terms_plain(t)) {
-        if (t.kind[0] != ABO_ACQ_MEAN)
-            return posterior(g, Zd, M, t.kind[0], t.p0[0], t.best_y[0], nullptr, nullptr, sc_d, 1, 0, nullptr, 0, 0, more);
+        if (t.kind[0] != ABO_ACQ_MEAN) {
+            PostOpts o;
+            o.more = more;
+            return posterior(g, Zd, M, t.kind[0], t.p0[0], t.best_y[0], nullptr, nullptr, sc_d, o);
+        }
         // −mu only: skip the contraction (scores come from the mean pass)
         HIPCHK(g->mu_all.ensure(sizeof(double) * M));
         int32_t rc = posterior(g, Zd, M, -1, 0.0, 0.0, g->mu_all.as<double>(), nullptr, nullptr);
@@ -1980,37 +1836,26 @@ int32_t score_terms_device(abo_gp* g, const double* Zd, int64_t M, const AcqTerm
     return ABO_OK;
 }
 
-// ---- exact top-k without the full variance contraction (DESIGN.md "Pruned top-k selection") -------------------------------------------
-// The sum of squares over the first R rows of V = L⁻¹K_XZ is the variance reduction from the first R training points alone, so
-// σ²_R = k_zz − Σ_{i<R} V_ij² ≥ σ², and EI, LogEI and UCB (β ≥ 0) do not decrease with σ: the score of (μ, σ²_R) bounds the score from above.
-// W = L⁻¹ being triangular, its first R rows cost (R/N)² of the contraction.
-struct PrunePlan {
-    bool eligible;
-    int rblocks;            // 256-row blocks of W in the bound pass
-    int64_t k0;             // candidates whose exact scores set the threshold
-    int64_t max_survivors;  // more than this: the ordinary full pass runs instead of the survivor pass
-    int rblocks0;           // 256-row blocks of a first, narrower bound level over all candidates (0: none — one bound pass, at rblocks)
-    int64_t level2_min;     // the pass at rblocks runs on the first level's survivors when there are more than this many
-    bool tail32;            // the first level's tail of the mean in fp32 (kgen_tail32.hip); nothing without a first level
-    bool head32;            // … and its head — head of the mean, guarded sum of squares — by the fused fp32-MFMA kernel (kgen_head32.hip)
-};
+}  // namespace
 
-#ifdef ABO_TEST_HOOKS
-std::atomic<int> g_prune_force_rblocks{0};      // abo_test_prune_force: row blocks of the bound pass (0 = the rule); mode 1 = a threshold
-std::atomic<int> g_prune_force_mode{0};         // of −Inf (every candidate survives: the worst case, on any data), 2 = as ABO_ACQ_PRUNE=0
-std::atomic<int> g_prune_pre_rblocks{0};        // abo_test_prune_levels: row blocks of the first level (−1 = none, 0 = the rule)
-std::atomic<int64_t> g_prune_level2_min{-1};    // … and the survivor count above which the second runs (−1 = the rule)
-std::atomic<int> g_prune_tail32{-1};            // abo_test_prune_tail32: 0 / 1 = the first level's tail in fp64 / fp32, −1 = the environment's
-std::atomic<int> g_prune_head32{-1};            // abo_test_prune_head32: 0 / 1 = the first level's head on the int8 engine / fused in fp32, −1 = the environment's
-#endif
+namespace abo {    // shared with test_hooks.hip (abo_state.h)
+// the overrides of abo_state.h: defined here, read below, written by test_hooks.hip alone
+std::atomic<int> g_prune_bound_moduli{0};
+std::atomic<int> g_prune_force_rblocks{0};
+std::atomic<int> g_prune_force_mode{0};
+std::atomic<int> g_prune_pre_rblocks{0};
+std::atomic<int64_t> g_prune_level2_min{-1};
+std::atomic<int> g_prune_tail32{-1};
+std::atomic<int> g_prune_head32{-1};
+}  // namespace abo
+
+namespace {
 
 // The mean's tail of the M-wide FIRST bound level in fp32 (kgen_tail32.hip).  ABO_PRUNE_TAIL32=0 (read once) keeps the fp64 tail
 // there, for A/B runs.  Every other bound pass — the second level, a single level — has the fp64 tail either way.
 bool prune_tail32() {
     static const bool on = [] { const char* e = getenv("ABO_PRUNE_TAIL32"); return !(e && e[0] == '0'); }();
-#ifdef ABO_TEST_HOOKS
-    if (g_prune_tail32.load() >= 0) return g_prune_tail32.load() != 0;
-#endif
+    if (g_prune_tail32.load(std::memory_order_relaxed) >= 0) return g_prune_tail32.load(std::memory_order_relaxed) != 0;
     return on;
 }
 
@@ -2021,21 +1866,20 @@ bool prune_head32() {
     static const bool on = [] { const char* e = getenv("ABO_PRUNE_HEAD32"); return !(e && e[0] == '0'); }();
     static const bool moduli_env = getenv("ABO_PRUNE_BOUND_MODULI") != nullptr;
     if (moduli_env) return false;
-#ifdef ABO_TEST_HOOKS
-    if (g_prune_bound_moduli.load() != 0) return false;
-    if (g_prune_head32.load() >= 0) return g_prune_head32.load() != 0;
-#endif
+    if (g_prune_bound_moduli.load(std::memory_order_relaxed) != 0) return false;
+    if (g_prune_head32.load(std::memory_order_relaxed) >= 0) return g_prune_head32.load(std::memory_order_relaxed) != 0;
     return on;
 }
 
 bool prune_enabled() {
     static const bool on = [] { const char* e = getenv("ABO_ACQ_PRUNE"); return !(e && e[0] == '0'); }();
-#ifdef ABO_TEST_HOOKS
-    if (g_prune_force_mode.load() == 2) return false;
-#endif
+    if (g_prune_force_mode.load(std::memory_order_relaxed) == 2) return false;
     return on;
 }
 
+}  // namespace
+
+namespace abo {    // shared with test_hooks.hip (abo_state.h)
 // rows: factor rows N of the model; int8_fused: the int8-residue engine would run this call's contraction with generator-written planes
 PrunePlan prune_plan(int64_t rows, int64_t M, int k, bool want_scores, int kind, double p0, int p_out, bool int8_fused, int d) {
     PrunePlan pp{false, 0, 0, 0, 0, 0};
@@ -2056,11 +1900,9 @@ PrunePlan prune_plan(int64_t rows, int64_t M, int k, bool want_scores, int kind,
     if (rb0 < 1) rb0 = 1;
     bool forced = false;
     int pre = 0;
-#ifdef ABO_TEST_HOOKS
-    forced = g_prune_force_rblocks.load() > 0;
-    if (forced) rb = g_prune_force_rblocks.load();
-    pre = g_prune_pre_rblocks.load();
-#endif
+    forced = g_prune_force_rblocks.load(std::memory_order_relaxed) > 0;
+    if (forced) rb = g_prune_force_rblocks.load(std::memory_order_relaxed);
+    pre = g_prune_pre_rblocks.load(std::memory_order_relaxed);
     if (pre > 0) rb0 = pre;              // (a forced first level that is not below rblocks: an error the callers report)
     else if (pre < 0 || forced || rb0 >= rb) rb0 = 0;
     pp.rblocks = rb;
@@ -2070,9 +1912,7 @@ PrunePlan prune_plan(int64_t rows, int64_t M, int k, bool want_scores, int kind,
     pp.k0 = k > 0 ? ((int64_t)4 * k > 1024 ? (int64_t)4 * k : 1024) : 0;
     // below 4·K0 survivors the full pass on them costs less than the ≈ 16 launches of another bound pass
     pp.level2_min = 4 * pp.k0;
-#ifdef ABO_TEST_HOOKS
-    if (g_prune_level2_min.load() >= 0) pp.level2_min = g_prune_level2_min.load();
-#endif
+    if (g_prune_level2_min.load(std::memory_order_relaxed) >= 0) pp.level2_min = g_prune_level2_min.load(std::memory_order_relaxed);
     // the survivor pass costs S/M of the full pass it replaces (plus a gather of S points): it is the cheaper of the two for any
     // S < M, and is taken while it saves at least an eighth of the pass — far more than the extra launches cost
     pp.max_survivors = M - M / 8;
@@ -2083,6 +1923,9 @@ PrunePlan prune_plan(int64_t rows, int64_t M, int k, bool want_scores, int kind,
                   M >= 4 * pp.k0 && M * (int64_t)d < ((int64_t)1 << 31);
     return pp;
 }
+}  // namespace abo
+
+namespace {
 
 // The pruned selection on device candidates Zd.  *done = false: nothing selected (the engine was not available after all, or too many
 // candidates survived) — the caller runs the ordinary pass, with more = true when passes were launched here.
@@ -2110,8 +1953,9 @@ int32_t prune_select(abo_gp* g, const double* Zd, int64_t M, const AcqTerms& t, 
     const bool two_levels = pp.rblocks0 > 0;
     HIPCHK(hipEventRecord(g->evs()[PE], s));
     // (a first level's looser mean costs survivors alone, and the second level is there when they are many; a single level has no such net)
-    int32_t rc = posterior(g, Zd, M, kind, p0, best_y, nullptr, nullptr, ub, 1, 0, nullptr, 0, two_levels ? pp.rblocks0 : pp.rblocks, false, false,
-                           pp.tail32, pp.head32);
+    PostOpts bound;
+    bound.rblocks = two_levels ? pp.rblocks0 : pp.rblocks; bound.tail32 = pp.tail32; bound.head32 = pp.head32;
+    int32_t rc = posterior(g, Zd, M, kind, p0, best_y, nullptr, nullptr, ub, bound);
     if (rc == PRUNE_UNAVAILABLE) return ABO_OK;
     if (rc) return rc;
     g->pst.bound_rows = g->passes.back().rows;
@@ -2120,17 +1964,17 @@ int32_t prune_select(abo_gp* g, const double* Zd, int64_t M, const AcqTerms& t, 
     // 2. threshold: exact scores of the K0 best by bound (NaN bounds first, as everywhere), τ = the k-th best of them
     HIPCHK(launch_topk(ub, M, (int)K0, 0, w, g->pr_tv.as<double>(), g->pr_ti.as<int64_t>(), s));
     HIPCHK(launch_gather_points(Zd, g->pr_ti.as<int64_t>(), 0, (int)K0, d, g->pr_z.as<double>(), s));
-    rc = posterior(g, g->pr_z.as<double>(), K0, kind, p0, best_y, nullptr, nullptr, g->pr_sc.as<double>(), 1, 0, nullptr, 0, 0, true);
+    PostOpts further;
+    further.more = true;
+    rc = posterior(g, g->pr_z.as<double>(), K0, kind, p0, best_y, nullptr, nullptr, g->pr_sc.as<double>(), further);
     if (rc) return rc;
     HIPCHK(launch_topk(g->pr_sc.as<double>(), K0, k, 0, w, g->pr_tv.as<double>(), g->pr_ti.as<int64_t>(), s));
     const double* tau = g->pr_tv.as<double>() + (k - 1);
-#ifdef ABO_TEST_HOOKS
-    if (g_prune_force_mode.load() == 1) {
+    if (g_prune_force_mode.load(std::memory_order_relaxed) == 1) {
         static const double ninf = -HUGE_VAL;
         HIPCHK(hipMemcpyAsync(count_d + 1, &ninf, sizeof(double), hipMemcpyHostToDevice, s));
         tau = reinterpret_cast<const double*>(count_d + 1);
     }
-#endif
     // 3. survivors: every candidate whose guarded bound reaches τ (the k that set τ among them), in index order
     HIPCHK(launch_prune_compact(ub, M, tau, kind == ABO_ACQ_LOGEI ? PRUNE_ABS_LOGEI : PRUNE_ABS, g->pr_blk.as<int>(), g->pr_sel.as<int64_t>(),
                                 count_d, s));
@@ -2150,7 +1994,9 @@ int32_t prune_select(abo_gp* g, const double* Zd, int64_t M, const AcqTerms& t, 
         HIPCHK(g->pr_z.ensure(sizeof(double) * S * d));
         HIPCHK(g->pr_ub2.ensure(sizeof(double) * S));
         HIPCHK(launch_gather_points(Zd, g->pr_sel.as<int64_t>(), 0, (int)S, d, g->pr_z.as<double>(), s));
-        rc = posterior(g, g->pr_z.as<double>(), S, kind, p0, best_y, nullptr, nullptr, g->pr_ub2.as<double>(), 1, 0, nullptr, 0, pp.rblocks, true, true);
+        PostOpts bound2;
+        bound2.rblocks = pp.rblocks; bound2.more = true; bound2.level2 = true;
+        rc = posterior(g, g->pr_z.as<double>(), S, kind, p0, best_y, nullptr, nullptr, g->pr_ub2.as<double>(), bound2);
         if (rc && rc != PRUNE_UNAVAILABLE) return rc;
         if (!rc) {          // (no scratch for the engine at this size: the first level's list goes on as it is)
             g->plv.rows2 = g->passes.back().rows;
@@ -2168,7 +2014,7 @@ int32_t prune_select(abo_gp* g, const double* Zd, int64_t M, const AcqTerms& t, 
     HIPCHK(g->pr_z.ensure(sizeof(double) * S * d));
     HIPCHK(g->pr_sc.ensure(sizeof(double) * S));
     HIPCHK(launch_gather_points(Zd, g->pr_sel.as<int64_t>(), 0, (int)S, d, g->pr_z.as<double>(), s));
-    rc = posterior(g, g->pr_z.as<double>(), S, kind, p0, best_y, nullptr, nullptr, g->pr_sc.as<double>(), 1, 0, nullptr, 0, 0, true);
+    rc = posterior(g, g->pr_z.as<double>(), S, kind, p0, best_y, nullptr, nullptr, g->pr_sc.as<double>(), further);
     if (rc) return rc;
     PHASE_EVENT(g->evs()[6], s);
     // 4. the selection among the exactly evaluated: list positions are in index order, so ties fall as they do over all M
@@ -2758,8 +2604,9 @@ int32_t abo_cand_refresh(abo_gp* g, abo_cand* c) {
             c->Kzx.release();
         }
         HIPCHK(hipEventRecord(g->evs()[5], g->stream));
-        rc = posterior(g, c->Z.as<double>(), c->M, -1, 0.0, 0.0, c->mu.as<double>(), c->var.as<double>(), nullptr, 1, 0,
-                       c->kzx_ld ? c->Kzx.as<double>() : nullptr, c->kzx_ld);
+        PostOpts keep;
+        keep.kstore = c->kzx_ld ? c->Kzx.as<double>() : nullptr; keep.ldstore = c->kzx_ld;
+        rc = posterior(g, c->Z.as<double>(), c->M, -1, 0.0, 0.0, c->mu.as<double>(), c->var.as<double>(), nullptr, keep);
         if (rc) return rc;
         HIPCHK(hipEventRecord(g->evs()[6], g->stream));
         HIPCHK(wait_stream(g->stream));
@@ -3492,10 +3339,7 @@ void abo::qei_mc_close(abo_cand* c, const QeiMcStats& keep) {
 }
 
 // ---- optimize_acquisition on the device (acq_utils.jl:33-73): refinement launch + the one-call driver -----------------
-namespace {
-
-struct RefineOpts { int max_iter, ls_max, history; double g_tol, f_abstol, x_abstol; };
-
+namespace abo {    // shared with test_hooks.hip (abo_state.h)
 RefineOpts refine_defaults(const abo_refine_opts* o) {
     RefineOpts r{100, 20, 10, 1e-5, 2.2e-9, 1e-4};        // acq_utils.jl:10, :62; Optim's LBFGS keeps m = 10 pairs
     if (o) {
@@ -3517,6 +3361,9 @@ int32_t check_refinable(abo_gp* g, int32_t d, const char* fn) {
     if (g->p_out > 1 && d + 1 != g->p_out) return fail(ABO_EINVAL, "%s: gradient-enhanced handle with p = %d outputs and d = %d", fn, g->p_out, d);
     return ABO_OK;
 }
+}  // namespace abo
+
+namespace {
 
 hipError_t grad_eval_cb(void* ctx, const double* pts, int npts, double* mu, double* cov, hipStream_t) {
     abo_gp* g = static_cast<abo_gp*>(ctx);
@@ -3524,6 +3371,9 @@ hipError_t grad_eval_cb(void* ctx, const double* pts, int npts, double* mu, doub
     return grad_eval_device(g, pts, npts, 0.0, mu, cov, nullptr) == ABO_OK ? hipSuccess : hipErrorUnknown;
 }
 
+}  // namespace
+
+namespace abo {    // shared with test_hooks.hip (abo_state.h)
 // bounds (2·d doubles: lower, upper), starts (S·d) and the outputs all in DEVICE memory; asynchronous on the handle's stream
 // between events 5 and 6
 int32_t refine_device(abo_gp* g, const AcqTerms& terms, const double* bounds_d, const double* starts_d, int S,
@@ -3575,6 +3425,9 @@ int32_t refine_device(abo_gp* g, const AcqTerms& terms, const double* bounds_d, 
     HIPCHK(launch_refine(ra, S, grad_only, s));
     return ABO_OK;
 }
+}  // namespace abo
+
+namespace {
 
 // the best refined point, the reference's way (acq_utils.jl:66-72: strict `>` keeps the first maximum); the best grid point if no
 // refined value reaches its score
@@ -3662,44 +3515,6 @@ int32_t abo_refine(abo_gp* g, int32_t kind, double p0, double best_y, const doub
     if (rc) return rc;
     return refine_terms_impl(g, t, lower, upper, d, starts, S, opts, x_out, f_out, iters_out);
 }
-
-#ifdef ABO_TEST_HOOKS
-static int32_t acq_grad_impl(abo_gp* g, const AcqTerms& t, const double* Z, int64_t M, int32_t d, double* f, double* grad);
-int32_t abo_test_acq_grad_terms(abo_gp* g, const abo_acq_term* terms, int32_t nterms, const double* Z, int64_t M, int32_t d, double* f,
-                                double* grad) {
-    if (!g) return fail(ABO_EINVAL, "abo_test_acq_grad: null handle");
-    int32_t rc = check_refinable(g, d, "abo_test_acq_grad");
-    if (rc) return rc;
-    AcqTerms t{};
-    rc = make_terms(g, terms, nterms, &t, "abo_test_acq_grad");
-    if (rc) return rc;
-    if (M < 0 || M > 65535 || (M > 0 && (!Z || !f || !grad))) return fail(ABO_EINVAL, "abo_test_acq_grad: bad argument (M ≤ 65535)");
-    if (M == 0) return ABO_OK;
-    return acq_grad_impl(g, t, Z, M, d, f, grad);
-}
-
-static int32_t acq_grad_impl(abo_gp* g, const AcqTerms& t, const double* Z, int64_t M, int32_t d, double* f, double* grad) {
-    int32_t rc;
-    HIPCHK(hipSetDevice(g->prm.device));
-    hipStream_t s = g->stream;
-    const size_t ns = (size_t)M * d;
-    HIPCHK(g->Zdev.ensure(sizeof(double) * (2 * ns + M)));
-    double *sd = g->Zdev.as<double>(), *xd = sd + ns, *fd = xd + ns;
-    HIPCHK(hipMemcpyAsync(sd, Z, sizeof(double) * ns, hipMemcpyHostToDevice, s));
-    rc = refine_device(g, t, nullptr, sd, (int)M, refine_defaults(nullptr), xd, fd, nullptr, 1);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(grad, xd, sizeof(double) * ns, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(f, fd, sizeof(double) * M, hipMemcpyDeviceToHost, s));
-    HIPCHK(wait_stream(s));
-    return ABO_OK;
-}
-
-int32_t abo_test_acq_grad(abo_gp* g, int32_t kind, double p0, double best_y, const double* Z, int64_t M, int32_t d, double* f,
-                          double* grad) {
-    const abo_acq_term one{kind, 0, p0, best_y, 1.0};
-    return abo_test_acq_grad_terms(g, &one, 1, Z, M, d, f, grad);
-}
-#endif  // ABO_TEST_HOOKS
 
 }  // extern "C"
 
@@ -3864,7 +3679,7 @@ int32_t abo_acq_lhs(abo_gp* g, int64_t n, int32_t d, const double* lower, const 
 // that build the objective's one term (AcqTerms::ystar) and run the same stages: acq_terms_impl (posterior pass + epilogue + the
 // selection of abo_acq; never the pruned one: terms_plain is false), refine_terms_impl, optimize_terms_impl.
 
-namespace {
+namespace abo {    // shared with test_hooks.hip (abo_state.h)
 
 // the checks that need no handle: they run first
 int32_t mes_check_samples(const double* ystar, int32_t S, int32_t ys_space, const char* fn) {
@@ -3895,7 +3710,7 @@ int32_t mes_terms(abo_gp* g, const double* ystar, int32_t S, int32_t ys_space, A
     return ABO_OK;
 }
 
-}  // namespace
+}  // namespace abo
 
 extern "C" {
 
@@ -3989,35 +3804,6 @@ int32_t abo_optimize_acquisition_mes(abo_gp* g, const double* ystar, int32_t S, 
     return optimize_terms_impl(g, t, lower, upper, d, n_grid, n_local, seed, opts, best_x, best_val, starts_x, starts_val, refined_x,
                                refined_val);
 }
-
-#ifdef ABO_TEST_HOOKS
-int32_t abo_test_mes_partials(int32_t device, const double* mu, const double* var, int64_t M, const double* ystar, int32_t S, double* f,
-                              double* dmu, double* dvar) {
-    if (M < 0 || (M > 0 && (!mu || !var || !f || !dmu || !dvar))) return fail(ABO_EINVAL, "abo_test_mes_partials: bad argument");
-    int32_t rc = mes_check_samples(ystar, S, ABO_DEVICE, "abo_test_mes_partials");
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(launch_score_mes(mu, var, M, ystar, S, f, dmu, dvar, nullptr));
-    HIPCHK(wait_stream(nullptr));
-    return ABO_OK;
-}
-
-int32_t abo_test_acq_grad_mes(abo_gp* g, const double* ystar, int32_t S, const double* Z, int64_t M, int32_t d, double* f, double* grad) {
-    int32_t rc = mes_check_samples(ystar, S, ABO_HOST, "abo_test_acq_grad_mes");
-    if (rc) return rc;
-    if (!g) return fail(ABO_EINVAL, "abo_test_acq_grad_mes: null handle");
-    rc = check_refinable(g, d, "abo_test_acq_grad_mes");
-    if (rc) return rc;
-    rc = mes_check_handle(g, "abo_test_acq_grad_mes");
-    if (rc) return rc;
-    if (M < 0 || M > 65535 || (M > 0 && (!Z || !f || !grad))) return fail(ABO_EINVAL, "abo_test_acq_grad_mes: bad argument (M ≤ 65535)");
-    if (M == 0) return ABO_OK;
-    AcqTerms t;
-    rc = mes_terms(g, ystar, S, ABO_HOST, &t);
-    if (rc) return rc;
-    return acq_grad_impl(g, t, Z, M, d, f, grad);
-}
-#endif  // ABO_TEST_HOOKS
 
 }  // extern "C"
 
@@ -4396,384 +4182,5 @@ int32_t abo_score(int32_t device, const double* mu, const double* var, int64_t M
     HIPCHK(wait_stream(nullptr));
     return ABO_OK;
 }
-
-#ifdef ABO_TEST_HOOKS
-int32_t abo_test_acq_partials(int32_t device, const double* mu, const double* var, int64_t M, int32_t kind, double p0, double best_y,
-                              double* f, double* dmu, double* dvar) {
-    if (M < 0 || (M > 0 && (!mu || !var || !f || !dmu || !dvar))) return fail(ABO_EINVAL, "abo_test_acq_partials: bad argument");
-    if (!plain_kind(kind)) return fail(ABO_EINVAL, "abo_test_acq_partials: unknown acquisition kind %d", kind);
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(launch_score_partials(mu, var, f, dmu, dvar, M, kind, p0, best_y, nullptr));
-    HIPCHK(wait_stream(nullptr));
-    return ABO_OK;
-}
-
-int32_t abo_test_prune_plan(int64_t rows, int64_t M, int32_t k, int32_t want_scores, int32_t kind, double p0, int32_t p_out, int32_t int8_fused,
-                            int32_t d, int64_t* out) {
-    if (!out) return fail(ABO_EINVAL, "abo_test_prune_plan: null argument");
-    const PrunePlan pp = prune_plan(rows, M, k, want_scores != 0, kind, p0, p_out, int8_fused != 0, d);
-    out[0] = pp.eligible; out[1] = pp.rblocks; out[2] = pp.k0; out[3] = pp.max_survivors;
-    return ABO_OK;
-}
-
-int32_t abo_test_prune_force(int32_t rblocks, int32_t mode) {
-    if (rblocks < 0 || mode < 0 || mode > 2) return fail(ABO_EINVAL, "abo_test_prune_force: rblocks = %d, mode = %d", rblocks, mode);
-    g_prune_force_rblocks.store(rblocks);
-    g_prune_force_mode.store(mode);
-    return ABO_OK;
-}
-
-int32_t abo_test_prune_levels(int32_t pre_rblocks, int64_t level2_min) {
-    if (pre_rblocks < -1 || level2_min < -1) return fail(ABO_EINVAL, "abo_test_prune_levels: pre_rblocks = %d, level2_min = %lld", pre_rblocks, (long long)level2_min);
-    g_prune_pre_rblocks.store(pre_rblocks);
-    g_prune_level2_min.store(level2_min);
-    return ABO_OK;
-}
-
-int32_t abo_test_prune_tail32(int32_t mode) {
-    if (mode < -1 || mode > 1) return fail(ABO_EINVAL, "abo_test_prune_tail32: mode = %d (-1 = the environment's, 0 = fp64, 1 = fp32)", mode);
-    g_prune_tail32.store(mode);
-    return ABO_OK;
-}
-
-int32_t abo_test_prune_head32(int32_t mode) {
-    if (mode < -1 || mode > 1) return fail(ABO_EINVAL, "abo_test_prune_head32: mode = %d (-1 = the environment's, 0 = int8 head, 1 = fused fp32 head)", mode);
-    g_prune_head32.store(mode);
-    return ABO_OK;
-}
-
-int32_t abo_test_bound_head32(abo_gp* g, const double* Z, int64_t M, int32_t rblocks, double* head, double* ssq, double* delta, double* l1) {
-    if (!g || !Z || !head || !ssq || !delta || !l1 || M <= 0 || rblocks <= 0) return fail(ABO_EINVAL, "abo_test_bound_head32: bad argument");
-    { int32_t rc = check_fitted(g, g->d); if (rc) return rc; }
-    if (g->p_out != 1) return fail(ABO_EINVAL, "abo_test_bound_head32: an ordinary model only");
-    const int rows = 256 * rblocks;
-    HIPCHK(hipSetDevice(g->prm.device));
-    hipStream_t s = g->stream;
-    // every output with one sentinel behind M / behind row R: the kernels write nothing there
-    ScratchBuf zd(g->prm.device, s), out(g->prm.device, s), wf(g->prm.device, s), dl(g->prm.device, s);
-    HIPCHK(zd.b.ensure(sizeof(double) * M * g->d));
-    HIPCHK(out.b.ensure(sizeof(double) * 2 * (M + 1)));
-    HIPCHK(wf.b.ensure(sizeof(float) * rows * rows));
-    HIPCHK(dl.b.ensure(sizeof(double) * 2 * (rows + 1)));
-    const std::vector<double> fill(2 * (size_t)(M + 1), -7.0), fill_r(2 * (size_t)(rows + 1), -7.0);
-    HIPCHK(hipMemcpyAsync(zd.b.p, Z, sizeof(double) * M * g->d, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(out.b.p, fill.data(), sizeof(double) * fill.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(dl.b.p, fill_r.data(), sizeof(double) * fill_r.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(wait_stream(s));
-    OzPlan full;
-    if (!oz_make_plan(OZ_DEFAULT_NMOD, &full)) return fail(ABO_EINVAL, "abo_test_bound_head32: no plan");
-    KgenHead32Args ha{};
-    ha.Xs = g->st->Xs.as<double>(); ha.Z = zd.b.as<double>(); ha.alpha = g->alpha.as<double>(); ha.W = g->st->W.as<double>(); ha.ldw = g->st->cap;
-    ha.Wf = wf.b.as<float>(); ha.delta = dl.b.as<double>(); ha.l1 = dl.b.as<double>() + rows + 1;
-    ha.head = out.b.as<double>(); ha.ssq = out.b.as<double>() + M + 1;
-    ha.M = M; ha.N = (int)g->npts; ha.Np = (int)g->Np; ha.R = rows; ha.d = g->d; ha.dp = g->dp; ha.family = g->prm.family;
-    ha.s = 1.0 / g->prm.ell; ha.sigma_f2 = g->prm.sigma_f2; ha.mean_c = g->prm.mean_c;
-    ha.eP_full = full.eP; ha.sK_full = oz_k_scale(g->prm.sigma_f2);
-    ha.rec_full = (128.0 * full.n * full.n + 256.0 * full.n) * std::ldexp(1.0, full.eP - 91);
-    const hipError_t le = launch_kgen_head32(ha, s);
-    if (le == hipErrorInvalidValue) return fail(ABO_EINVAL, "abo_test_bound_head32: %d rows on a model of %lld points", rows, (long long)g->npts);
-    HIPCHK(le);
-    // head / ssq: M + 1 doubles each, delta / l1: rows + 1 — the last of each is the sentinel (−7) as the kernels left it
-    HIPCHK(hipMemcpyAsync(head, ha.head, sizeof(double) * (M + 1), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(ssq, ha.ssq, sizeof(double) * (M + 1), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(delta, ha.delta, sizeof(double) * (rows + 1), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(l1, ha.l1, sizeof(double) * (rows + 1), hipMemcpyDeviceToHost, s));
-    HIPCHK(wait_stream(s));
-    return ABO_OK;
-}
-
-int32_t abo_test_prune_plan_levels(int64_t rows, int64_t M, int32_t k, int32_t want_scores, int32_t kind, double p0, int32_t p_out,
-                                   int32_t int8_fused, int32_t d, int64_t* out) {
-    if (!out) return fail(ABO_EINVAL, "abo_test_prune_plan_levels: null argument");
-    const PrunePlan pp = prune_plan(rows, M, k, want_scores != 0, kind, p0, p_out, int8_fused != 0, d);
-    if (pp.rblocks0 >= pp.rblocks) return fail(ABO_EINVAL, "abo_test_prune_plan_levels: a first bound level of %d row blocks is not below the bound pass's %d", pp.rblocks0, pp.rblocks);
-    out[0] = pp.eligible; out[1] = pp.rblocks; out[2] = pp.k0; out[3] = pp.max_survivors; out[4] = pp.rblocks0;
-    return ABO_OK;
-}
-
-int32_t abo_test_prune_bound_moduli(int32_t n) {
-    if (n != 0 && n != 14 && !kgen_short_moduli(n)) return fail(ABO_EINVAL, "abo_test_prune_bound_moduli: n = %d (0 = default, 8, 9, 10, 14)", n);
-    g_prune_bound_moduli.store(n);
-    return ABO_OK;
-}
-
-int32_t abo_test_prune_bound_plan(abo_gp* g, int32_t* sexp_b, double* delta, int64_t n_rows) {
-    if (!g || !sexp_b || !delta || n_rows < 0) return fail(ABO_EINVAL, "abo_test_prune_bound_plan: bad argument");
-    if (!g->pst.bound_rows || g->pb_rows <= 0 || n_rows > g->pb_rows)
-        return fail(ABO_EINVAL, "abo_test_prune_bound_plan: the last abo_acq on this handle ran no bound pass on a short plan over %lld rows", (long long)n_rows);
-    HIPCHK(hipSetDevice(g->prm.device));
-    HIPCHK(hipMemcpyAsync(sexp_b, g->oz_sexpb.p, sizeof(int) * n_rows, hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(hipMemcpyAsync(delta, g->oz_delta.p, sizeof(double) * n_rows, hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(wait_stream(g->stream));
-    return ABO_OK;
-}
-
-int32_t abo_test_prune_bounds(abo_gp* g, double* out, int64_t M) {
-    if (!g || !out || M < 0) return fail(ABO_EINVAL, "abo_test_prune_bounds: bad argument");
-    if (!g->pst.bound_rows || g->pr_ub.cap < sizeof(double) * (size_t)M) return fail(ABO_EINVAL, "abo_test_prune_bounds: the last abo_acq on this handle ran no bound pass over %lld candidates", (long long)M);
-    HIPCHK(hipSetDevice(g->prm.device));
-    HIPCHK(hipMemcpyAsync(out, g->pr_ub.p, sizeof(double) * M, hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(wait_stream(g->stream));
-    return ABO_OK;
-}
-
-int32_t abo_test_prune_mean(abo_gp* g, double* mu, double* eps, int64_t M) {
-    if (!g || !mu || !eps || M < 0) return fail(ABO_EINVAL, "abo_test_prune_mean: bad argument");
-    if (!g->pst.bound_rows || g->pr_mut.cap < sizeof(double) * (size_t)M || g->pr_eps.cap < sizeof(double) * (size_t)M)
-        return fail(ABO_EINVAL, "abo_test_prune_mean: the last abo_acq on this handle ran no bound pass over %lld candidates", (long long)M);
-    HIPCHK(hipSetDevice(g->prm.device));
-    HIPCHK(hipMemcpyAsync(mu, g->pr_mut.p, sizeof(double) * M, hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(hipMemcpyAsync(eps, g->pr_eps.p, sizeof(double) * M, hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(wait_stream(g->stream));
-    return ABO_OK;
-}
-
-int32_t abo_test_kappa_tail(int32_t device, int32_t family, const double* d2, double* out, int64_t n) {
-    if (!d2 || !out || n < 0) return fail(ABO_EINVAL, "abo_test_kappa_tail: bad argument");
-    if (family < ABO_KERNEL_SE || family > ABO_KERNEL_MATERN32) return fail(ABO_EINVAL, "abo_test_kappa_tail: unknown family");
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(launch_kappa_tail_test(family, d2, out, n, nullptr));
-    HIPCHK(wait_stream(nullptr));
-    return ABO_OK;
-}
-
-int32_t abo_test_kappa_tail32(int32_t device, int32_t family, const double* d2, double* out, int64_t n) {
-    if (!d2 || !out || n < 0) return fail(ABO_EINVAL, "abo_test_kappa_tail32: bad argument");
-    if (family < ABO_KERNEL_SE || family > ABO_KERNEL_MATERN32) return fail(ABO_EINVAL, "abo_test_kappa_tail32: unknown family");
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(launch_kappa_tail32_test(family, d2, out, n, nullptr));
-    HIPCHK(wait_stream(nullptr));
-    return ABO_OK;
-}
-
-int32_t abo_test_oz_plan(int32_t n, int32_t* p, double* tables, double* scal, int32_t* eP) {
-    if (!p || !tables || !scal || !eP) return fail(ABO_EINVAL, "abo_test_oz_plan: null argument");
-    OzPlan pl;
-    if (!oz_make_plan(n, &pl)) return fail(ABO_EINVAL, "abo_test_oz_plan: %d moduli not supported (8 … %d)", n, OZ_MAXMOD);
-    for (int l = 0; l < n; ++l) {
-        p[l] = pl.p[l];
-        tables[0 * OZ_MAXMOD + l] = pl.invp[l];
-        tables[1 * OZ_MAXMOD + l] = pl.c26[l];
-        tables[2 * OZ_MAXMOD + l] = pl.s1[l];
-        tables[3 * OZ_MAXMOD + l] = pl.s2[l];
-    }
-    scal[0] = pl.P1; scal[1] = pl.P2; scal[2] = pl.invP;
-    *eP = pl.eP;
-    return ABO_OK;
-}
-
-int32_t abo_test_oz_contract(int32_t device, const double* W, int64_t ldw, int32_t Np, int32_t nvalid, const double* Kxz, int64_t ldk,
-                             int32_t Mc, double kmax, int32_t nmod, double* partial, int64_t ldp) {
-    if (!W || !Kxz || !partial) return fail(ABO_EINVAL, "abo_test_oz_contract: null argument");
-    if (Np <= 0 || Np % TB || Mc <= 0 || Mc % TB || nvalid < 0 || nvalid > Np || ldw < Np || ldk < Np || ldp < Mc || !(kmax > 0.0))
-        return fail(ABO_EINVAL, "abo_test_oz_contract: Np and Mc multiples of 128, nvalid <= Np, leading dimensions >= Np / Mc, kmax > 0");
-    OzPlan pl;
-    if (!oz_make_plan(nmod, &pl)) return fail(ABO_EINVAL, "abo_test_oz_contract: %d moduli not supported", nmod);
-    HIPCHK(hipSetDevice(device));
-    const int64_t q = pad_up(Np, 256), mq = pad_up(Mc, 256);
-    ScratchBuf wr(device, nullptr), kr(device, nullptr), u(device, nullptr), ints(device, nullptr);
-    HIPCHK(wr.b.ensure(oz_w_bytes(nmod, Np)));
-    HIPCHK(kr.b.ensure(oz_k_bytes(nmod, Np, Mc)));
-    HIPCHK(u.b.ensure(oz_k_bytes(nmod, Np, Mc)));
-    HIPCHK(ints.b.ensure(sizeof(int) * (2 * q + mq + OZ_CTR_INTS)));
-    int* sexp = ints.b.as<int>();
-    HIPCHK(oz_prepare_w(pl, W, ldw, Np, nvalid, wr.b.as<int8_t>(), sexp, sexp + q, nullptr));
-    OzVarArgs oa{};
-    oa.plan = &pl; oa.Kxz = Kxz; oa.ldk = ldk; oa.WR = wr.b.as<int8_t>(); oa.sexp = sexp; oa.bad_row = sexp + q;
-    oa.KR = kr.b.as<int8_t>(); oa.U = u.b.as<int8_t>(); oa.bad_col = sexp + 2 * q; oa.partial = partial; oa.ldp = ldp;
-    oa.Np = Np; oa.Mc = Mc; oa.nvalid = nvalid; oa.sK = oz_k_scale(kmax);
-    HIPCHK(launch_var_ozaki(oa, nullptr));
-    HIPCHK(wait_stream(nullptr));
-    return ABO_OK;
-}
-
-int32_t abo_test_oz_contract_bound(int32_t device, const double* W, int64_t ldw, int32_t Np, int32_t nvalid, const double* Kxz, int64_t ldk,
-                                   int32_t Mc, double kmax, int32_t nmod_b, int32_t rblocks, double* partial, int64_t ldp, double* delta) {
-    if (!W || !Kxz || !partial || !delta) return fail(ABO_EINVAL, "abo_test_oz_contract_bound: null argument");
-    const int rows = 256 * rblocks;
-    if (Np <= 0 || Np % TB || Mc <= 0 || Mc % TB || nvalid < 0 || nvalid > Np || ldw < Np || ldk < Np || ldp < Mc || !(kmax > 0.0) ||
-        rblocks <= 0 || rows > pad_up(Np, 256))
-        return fail(ABO_EINVAL, "abo_test_oz_contract_bound: Np and Mc multiples of 128, nvalid <= Np, leading dimensions >= Np / Mc, kmax > 0, 256·rblocks <= pad256(Np)");
-    OzPlan pl, full;
-    if (!oz_make_plan(nmod_b, &pl) || !oz_make_plan(14, &full)) return fail(ABO_EINVAL, "abo_test_oz_contract_bound: %d moduli not supported", nmod_b);
-    HIPCHK(hipSetDevice(device));
-    const int64_t q = pad_up(Np, 256), mq = pad_up(Mc, 256);
-    ScratchBuf wr(device, nullptr), kr(device, nullptr), u(device, nullptr), ints(device, nullptr);
-    HIPCHK(wr.b.ensure((size_t)nmod_b * rows * q));
-    HIPCHK(kr.b.ensure(oz_k_bytes(nmod_b, Np, Mc)));
-    HIPCHK(u.b.ensure(oz_k_bytes(nmod_b, Np, Mc)));
-    HIPCHK(ints.b.ensure(sizeof(int) * (2 * q + mq + OZ_CTR_INTS)));
-    int* sexp = ints.b.as<int>();
-    const int bK = oz_bound_kbits(pl.eP, rows);
-    const int sKb = oz_k_scale(kmax, bK);
-    HIPCHK(oz_prepare_w_bound(pl, full, W, ldw, Np, nvalid, rows, bK, sKb, oz_k_scale(kmax), kmax * (1.0 + 0x1p-40), wr.b.as<int8_t>(), sexp, sexp + q,
-                              delta, nullptr));
-    OzVarArgs oa{};
-    oa.plan = &pl; oa.Kxz = Kxz; oa.ldk = ldk; oa.WR = wr.b.as<int8_t>(); oa.sexp = sexp; oa.bad_row = sexp + q;
-    oa.KR = kr.b.as<int8_t>(); oa.U = u.b.as<int8_t>(); oa.bad_col = sexp + 2 * q; oa.partial = partial; oa.ldp = ldp;
-    oa.Np = Np; oa.Mc = Mc; oa.nvalid = nvalid; oa.sK = sKb; oa.rblocks = rblocks; oa.delta = delta; oa.w_plane = (int64_t)rows * q;
-    HIPCHK(launch_var_ozaki(oa, nullptr));
-    HIPCHK(wait_stream(nullptr));
-    return ABO_OK;
-}
-
-int32_t abo_test_kappa(int32_t device, int32_t family, const double* d2, double* out, int64_t n) {
-    if (!d2 || !out || n < 0) return fail(ABO_EINVAL, "abo_test_kappa: bad argument");
-    if (family < ABO_KERNEL_SE || family > ABO_KERNEL_MATERN32) return fail(ABO_EINVAL, "abo_test_kappa: unknown family");
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(launch_kappa_test(family, d2, out, n, nullptr));
-    HIPCHK(wait_stream(nullptr));
-    return ABO_OK;
-}
-
-int32_t abo_test_gemm_nt(int32_t device, const double* A, const double* B, double* C, int32_t M, int32_t N, int32_t K,
-                         int64_t lda, int64_t ldb, int64_t ldc, double alpha, double beta) {
-    if (!A || !B || !C) return fail(ABO_EINVAL, "abo_test_gemm_nt: null argument");
-    if (M <= 0 || N <= 0 || K <= 0 || M % 128 || N % 128 || K % 16 || (lda & 1) || (ldb & 1))
-        return fail(ABO_EINVAL, "abo_test_gemm_nt: M, N must be multiples of 128, K of 16, lda/ldb even");
-    HIPCHK(hipSetDevice(device));
-    GemmArgs a{};
-    a.A = A; a.B = B; a.C = C; a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.M = M; a.N = N; a.K = K;
-    a.kmode = K_FULL; a.batch = 1; a.alpha = alpha; a.beta = beta;
-    HIPCHK(launch_gemm_nt(a, nullptr));
-    HIPCHK(wait_stream(nullptr));
-    return ABO_OK;
-}
-
-// what the GEMM kernels assume of shapes and flags (no pointer is looked at): nullptr, or the text of the complaint
-static const char* gemm_args_complaint(const GemmArgs& a) {
-    if (a.M <= 0 || a.N <= 0 || a.M % TB || a.N % TB) return "M, N must be positive multiples of 128";
-    if (a.K <= 0 || a.K % 16) return "K must be a positive multiple of 16";
-    if (a.kmode < K_FULL || a.kmode > K_B_UPPER) return "unknown kmode";
-    if (a.batch < 1 || a.ksplit < 0 || a.mrows < 0) return "batch >= 1, ksplit >= 0, mrows >= 0";
-    if (a.ksplit && (a.K % 128 || a.ksplit % 128)) return "split-k: K and ksplit must be multiples of 128";
-    if (a.ksplit && (a.batch != 1 || a.beta != 0.0 || a.Ct)) return "split-k: batch == 1, beta == 0, no Ct";
-    return nullptr;
-}
-
-int32_t abo_test_gemm_path(int32_t M, int32_t N, int32_t K, int32_t kmode, int32_t lower_only, int32_t batch, int32_t ksplit,
-                           int32_t mrows, int32_t in_place, int32_t* path) {
-    if (!path) return fail(ABO_EINVAL, "abo_test_gemm_path: null argument");
-    static double op[3];                       // three distinct addresses; never dereferenced
-    GemmArgs a{};
-    a.A = &op[0]; a.B = &op[1]; a.C = in_place ? &op[0] : &op[2];
-    a.M = M; a.N = N; a.K = K; a.kmode = kmode; a.lower_only = lower_only; a.batch = batch; a.alpha = 1.0; a.ksplit = ksplit; a.mrows = mrows;
-    if (const char* why = gemm_args_complaint(a)) return fail(ABO_EINVAL, "abo_test_gemm_path: %s", why);
-    *path = gemm_nt_path(a);
-    return ABO_OK;
-}
-
-int32_t abo_test_gemm_swz_map(int32_t T, int32_t G, int32_t Q, int32_t* ti, int32_t* tj) {
-    if (!ti || !tj) return fail(ABO_EINVAL, "abo_test_gemm_swz_map: null argument");
-    if (T < 1 || T > 4096 || G < 1 || Q < 0 || Q >= T * (T + 1) / 2) return fail(ABO_EINVAL, "abo_test_gemm_swz_map: 1 <= T <= 4096, G >= 1, 0 <= Q < T(T+1)/2");
-    int i = -1, j = -1;
-    gemm_swz_tile(T, G, Q, i, j);
-    *ti = i; *tj = j;
-    return ABO_OK;
-}
-
-int32_t abo_test_gemm_swz_q(int32_t tiles, int32_t L, int32_t* Q) {
-    if (!Q) return fail(ABO_EINVAL, "abo_test_gemm_swz_q: null argument");
-    if (tiles < 1 || L < 0 || L >= (tiles + 7) / 8 * 8) return fail(ABO_EINVAL, "abo_test_gemm_swz_q: tiles >= 1, 0 <= L < ceil(tiles / 8) * 8");
-    *Q = gemm_swz_q(L, tiles);
-    return ABO_OK;
-}
-
-int32_t abo_test_gemm_args(int32_t device, const double* A, const double* B, double* C, double* Ct, int64_t lda, int64_t ldb, int64_t ldc,
-                           int64_t ldct, int64_t sA, int64_t sB, int64_t sC, int64_t sCt, int32_t M, int32_t N, int32_t K, int32_t kmode,
-                           int32_t lower_only, int32_t batch, double alpha, double beta, int32_t ksplit, int32_t mrows, const int64_t* info,
-                           int32_t* path) {
-    if (!A || !B || !C || !path) return fail(ABO_EINVAL, "abo_test_gemm_args: null argument");
-    GemmArgs a{};
-    a.A = A; a.B = B; a.C = C; a.Ct = Ct; a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.ldct = ldct; a.sA = sA; a.sB = sB; a.sC = sC; a.sCt = sCt;
-    a.M = M; a.N = N; a.K = K; a.kmode = kmode; a.lower_only = lower_only; a.batch = batch; a.alpha = alpha; a.beta = beta; a.info = info;
-    a.ksplit = ksplit; a.mrows = mrows;
-    if (const char* why = gemm_args_complaint(a)) return fail(ABO_EINVAL, "abo_test_gemm_args: %s", why);
-    if ((lda & 1) || (ldb & 1) || lda < K || ldb < K || ldc < N || (Ct && ldct < M) || ((sA | sB) & 1) || sA < 0 || sB < 0 || sC < 0 || sCt < 0)
-        return fail(ABO_EINVAL, "abo_test_gemm_args: lda, ldb even and >= K, ldc >= N, ldct >= M, batch strides >= 0 (those of A and B even)");
-    const int p = gemm_nt_path(a);
-    if (p == GEMM_PATH_SKINNY && (kmode == K_A_LOWER || kmode == K_A_UPPER))
-        return fail(ABO_EINVAL, "abo_test_gemm_args: the skinny split-k kernel knows K_FULL, K_B_LOWER and K_B_UPPER only");
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(launch_gemm_nt(a, nullptr));
-    HIPCHK(wait_stream(nullptr));
-    *path = p;
-    return ABO_OK;
-}
-
-int32_t abo_test_qei_pass(int32_t device, const double* A, int64_t lda, int32_t rows16, const double* B, int64_t ldb, int64_t nB, int32_t K,
-                          double alpha, double* C, int64_t ldc, int32_t kmode, int32_t ksplit, int64_t sC) {
-    if (!A || !B || !C) return fail(ABO_EINVAL, "abo_test_qei_pass: null argument");
-    if (lda < K || ldb < K || ldc < nB || sC < 0) return fail(ABO_EINVAL, "abo_test_qei_pass: lda, ldb >= K, ldc >= nB, sC >= 0");
-    HIPCHK(hipSetDevice(device));
-    const hipError_t e = launch_qei_pass(A, lda, rows16, B, ldb, nB, K, alpha, C, ldc, nullptr, kmode, ksplit, sC);
-    if (e == hipErrorInvalidValue) return fail(ABO_EINVAL, "abo_test_qei_pass: launch_qei_pass refused rows16 = %d, nB = %lld, K = %d, lda = %lld, ldb = %lld, kmode = %d, ksplit = %d",
-                                                rows16, (long long)nB, K, (long long)lda, (long long)ldb, kmode, ksplit);
-    HIPCHK(e);
-    HIPCHK(wait_stream(nullptr));
-    return ABO_OK;
-}
-
-int32_t abo_test_splitk_reduce(int32_t device, const double* P, int64_t ldp, int64_t sP, int32_t nz, int32_t rows, int32_t cols, int32_t K,
-                               int32_t ksplit, int32_t kmode, double* out, int64_t ldo) {
-    if (!P || !out) return fail(ABO_EINVAL, "abo_test_splitk_reduce: null argument");
-    if (rows <= 0 || cols <= 0 || (cols & 1) || (ldp & 1) || (ldo & 1) || (sP & 1) || ldp < cols || ldo < cols || sP < 0 || nz < 1 || K <= 0 ||
-        ksplit <= 0 || ksplit % 128 || (int64_t)nz * ksplit < K)
-        return fail(ABO_EINVAL, "abo_test_splitk_reduce: rows > 0, cols > 0 and even, ldp / ldo / sP even, ldp, ldo >= cols, ksplit a multiple of 128, nz chunks covering K");
-    if (kmode != K_FULL && kmode != K_B_LOWER && kmode != K_B_UPPER) return fail(ABO_EINVAL, "abo_test_splitk_reduce: kmode must be K_FULL, K_B_LOWER or K_B_UPPER");
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(launch_splitk_reduce(P, ldp, sP, nz, rows, cols, K, ksplit, kmode, out, ldo, nullptr));
-    HIPCHK(wait_stream(nullptr));
-    return ABO_OK;
-}
-
-int32_t abo_test_var_gemm(int32_t device, const double* W, int64_t ldw, int32_t Np, int32_t nvalid, const double* Kxz, int64_t ldk, int32_t Mc,
-                          double* partial, int64_t ldp, int32_t variant) {
-    if (!W || !Kxz || !partial) return fail(ABO_EINVAL, "abo_test_var_gemm: null argument");
-    if (Np <= 0 || Np % TB || Mc <= 0 || Mc % TB || nvalid < 0 || nvalid > Np || ldw < Np || ldk < Np || (ldw & 1) || (ldk & 1) || ldp < Mc)
-        return fail(ABO_EINVAL, "abo_test_var_gemm: Np and Mc multiples of 128, nvalid <= Np, ldw / ldk even and >= Np, ldp >= Mc");
-    if (variant != 0 && variant != 1) return fail(ABO_EINVAL, "abo_test_var_gemm: variant 0 (the launcher's rule) or 1 (the 128-row kernel)");
-    HIPCHK(hipSetDevice(device));
-    VarGemmArgs va{};
-    va.W = W; va.Kxz = Kxz; va.partial = partial; va.ldw = ldw; va.ldk = ldk; va.ldp = ldp; va.Np = Np; va.Mc = Mc; va.nvalid = nvalid;
-    HIPCHK(launch_var_gemm(va, nullptr, variant));
-    HIPCHK(wait_stream(nullptr));
-    return ABO_OK;
-}
-
-// launch_kgen with every field of KgenArgs as the caller gives it: no decision about shape, engine or dispatch is taken here
-int32_t abo_test_kgen(int32_t device, const abo_test_kgen_args* t) {
-    if (!t || !t->Xs || !t->Z) return fail(ABO_EINVAL, "abo_test_kgen: null argument");
-    if (t->n_mean < 0 || t->n_mean > MAX_P || (t->n_mean > 0 && !t->mean_vec)) return fail(ABO_EINVAL, "abo_test_kgen: n_mean in [0, %d] with mean_vec given", MAX_P);
-    KgenArgs a{};
-    a.Xs = t->Xs; a.Z = t->Z; a.alpha = t->alpha; a.Kout = t->Kout; a.mu = t->mu; a.ldk = t->ldk; a.M = t->M; a.j0 = t->j0; a.Mc = t->Mc;
-    a.N = t->N; a.Np = t->Np; a.d = t->d; a.dp = t->dp; a.family = t->family; a.s = t->s; a.sigma_f2 = t->sigma_f2;
-    for (int q = 0; q < t->n_mean; ++q) a.mean_vec[q] = t->mean_vec[q];
-    a.mean_c = t->n_mean > 0 ? t->mean_vec[0] : 0.0;
-    a.pt = t->pt; a.pc = t->pc; a.point_major = t->point_major; a.dlogell = t->dlogell; a.rvalid = t->rvalid;
-    a.res = t->res; a.res_ld = t->res_ld; a.res_plane = t->res_plane; a.res_bad = t->res_bad; a.res_n = t->res_n; a.res_sK = t->res_sK;
-    a.res_ktg = t->res_ktg; a.res_kmax = t->res_kmax;
-    HIPCHK(hipSetDevice(device));
-    const hipError_t e = launch_kgen(a, nullptr);
-    if (e == hipErrorInvalidValue)
-        return fail(ABO_EINVAL, "abo_test_kgen: launch_kgen refused family = %d, dp = %d, pt = %d, dlogell = %d, res_n = %d, res_kmax = %d, Np = %d",
-                    a.family, a.dp, a.pt, a.dlogell, a.res ? a.res_n : 0, a.res_kmax, a.Np);
-    HIPCHK(e);
-    HIPCHK(wait_stream(nullptr));
-    return ABO_OK;
-}
-
-int32_t abo_test_cand_newcol(int32_t device, const double* Xs, const double* Z, double* Kzx, int64_t ld, int64_t M, int32_t col, int32_t grad,
-                             int32_t pt, int32_t q, int32_t d, int32_t dp, int32_t family, double s, double sigma_f2) {
-    if (!Xs || !Z || !Kzx) return fail(ABO_EINVAL, "abo_test_cand_newcol: null argument");
-    HIPCHK(hipSetDevice(device));
-    const hipError_t e = grad ? launch_cand_newcol_grad(Xs, Z, Kzx, ld, M, col, pt, q, d, dp, family, s, sigma_f2, nullptr)
-                              : launch_cand_newcol(Xs, Z, Kzx, ld, M, col, d, dp, family, s, sigma_f2, nullptr);
-    if (e == hipErrorInvalidValue) return fail(ABO_EINVAL, "abo_test_cand_newcol: the launcher refused family = %d (grad = %d)", family, grad);
-    HIPCHK(e);
-    HIPCHK(wait_stream(nullptr));
-    return ABO_OK;
-}
-#endif  // ABO_TEST_HOOKS
 
 }  // extern "C"

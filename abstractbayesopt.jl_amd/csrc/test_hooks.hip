@@ -1,0 +1,458 @@
+// The abo_test_* building blocks the GPU suite drives (include/abo_hip.h, last section) and nothing else: the one unit compiled with
+// -DABO_TEST_HOOKS (the public header declares the hooks under it) and linked into libabo_hip_test.so only.  The overrides of the
+// pruned selection (abo_state.h: g_prune_*) have their only writers here.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "abo_state.h"
+#include "kgen_core.h"
+
+using namespace abo;
+
+extern "C" {
+
+// value and gradient of the objective at M host points: one gradient-only refinement launch
+static int32_t acq_grad_impl(abo_gp* g, const AcqTerms& t, const double* Z, int64_t M, int32_t d, double* f, double* grad);
+int32_t abo_test_acq_grad_terms(abo_gp* g, const abo_acq_term* terms, int32_t nterms, const double* Z, int64_t M, int32_t d, double* f,
+                                double* grad) {
+    if (!g) return fail(ABO_EINVAL, "abo_test_acq_grad: null handle");
+    int32_t rc = check_refinable(g, d, "abo_test_acq_grad");
+    if (rc) return rc;
+    AcqTerms t{};
+    rc = make_terms(g, terms, nterms, &t, "abo_test_acq_grad");
+    if (rc) return rc;
+    if (M < 0 || M > 65535 || (M > 0 && (!Z || !f || !grad))) return fail(ABO_EINVAL, "abo_test_acq_grad: bad argument (M ≤ 65535)");
+    if (M == 0) return ABO_OK;
+    return acq_grad_impl(g, t, Z, M, d, f, grad);
+}
+
+static int32_t acq_grad_impl(abo_gp* g, const AcqTerms& t, const double* Z, int64_t M, int32_t d, double* f, double* grad) {
+    int32_t rc;
+    HIPCHK(hipSetDevice(g->prm.device));
+    hipStream_t s = g->stream;
+    const size_t ns = (size_t)M * d;
+    HIPCHK(g->Zdev.ensure(sizeof(double) * (2 * ns + M)));
+    double *sd = g->Zdev.as<double>(), *xd = sd + ns, *fd = xd + ns;
+    HIPCHK(hipMemcpyAsync(sd, Z, sizeof(double) * ns, hipMemcpyHostToDevice, s));
+    rc = refine_device(g, t, nullptr, sd, (int)M, refine_defaults(nullptr), xd, fd, nullptr, 1);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(grad, xd, sizeof(double) * ns, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(f, fd, sizeof(double) * M, hipMemcpyDeviceToHost, s));
+    HIPCHK(wait_stream(s));
+    return ABO_OK;
+}
+
+int32_t abo_test_acq_grad(abo_gp* g, int32_t kind, double p0, double best_y, const double* Z, int64_t M, int32_t d, double* f,
+                          double* grad) {
+    const abo_acq_term one{kind, 0, p0, best_y, 1.0};
+    return abo_test_acq_grad_terms(g, &one, 1, Z, M, d, f, grad);
+}
+
+int32_t abo_test_mes_partials(int32_t device, const double* mu, const double* var, int64_t M, const double* ystar, int32_t S, double* f,
+                              double* dmu, double* dvar) {
+    if (M < 0 || (M > 0 && (!mu || !var || !f || !dmu || !dvar))) return fail(ABO_EINVAL, "abo_test_mes_partials: bad argument");
+    int32_t rc = mes_check_samples(ystar, S, ABO_DEVICE, "abo_test_mes_partials");
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(launch_score_mes(mu, var, M, ystar, S, f, dmu, dvar, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_acq_grad_mes(abo_gp* g, const double* ystar, int32_t S, const double* Z, int64_t M, int32_t d, double* f, double* grad) {
+    int32_t rc = mes_check_samples(ystar, S, ABO_HOST, "abo_test_acq_grad_mes");
+    if (rc) return rc;
+    if (!g) return fail(ABO_EINVAL, "abo_test_acq_grad_mes: null handle");
+    rc = check_refinable(g, d, "abo_test_acq_grad_mes");
+    if (rc) return rc;
+    rc = mes_check_handle(g, "abo_test_acq_grad_mes");
+    if (rc) return rc;
+    if (M < 0 || M > 65535 || (M > 0 && (!Z || !f || !grad))) return fail(ABO_EINVAL, "abo_test_acq_grad_mes: bad argument (M ≤ 65535)");
+    if (M == 0) return ABO_OK;
+    AcqTerms t;
+    rc = mes_terms(g, ystar, S, ABO_HOST, &t);
+    if (rc) return rc;
+    return acq_grad_impl(g, t, Z, M, d, f, grad);
+}
+
+int32_t abo_test_acq_partials(int32_t device, const double* mu, const double* var, int64_t M, int32_t kind, double p0, double best_y,
+                              double* f, double* dmu, double* dvar) {
+    if (M < 0 || (M > 0 && (!mu || !var || !f || !dmu || !dvar))) return fail(ABO_EINVAL, "abo_test_acq_partials: bad argument");
+    if (!plain_kind(kind)) return fail(ABO_EINVAL, "abo_test_acq_partials: unknown acquisition kind %d", kind);
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(launch_score_partials(mu, var, f, dmu, dvar, M, kind, p0, best_y, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_prune_plan(int64_t rows, int64_t M, int32_t k, int32_t want_scores, int32_t kind, double p0, int32_t p_out, int32_t int8_fused,
+                            int32_t d, int64_t* out) {
+    if (!out) return fail(ABO_EINVAL, "abo_test_prune_plan: null argument");
+    const PrunePlan pp = prune_plan(rows, M, k, want_scores != 0, kind, p0, p_out, int8_fused != 0, d);
+    out[0] = pp.eligible; out[1] = pp.rblocks; out[2] = pp.k0; out[3] = pp.max_survivors;
+    return ABO_OK;
+}
+
+int32_t abo_test_prune_force(int32_t rblocks, int32_t mode) {
+    if (rblocks < 0 || mode < 0 || mode > 2) return fail(ABO_EINVAL, "abo_test_prune_force: rblocks = %d, mode = %d", rblocks, mode);
+    g_prune_force_rblocks.store(rblocks);
+    g_prune_force_mode.store(mode);
+    return ABO_OK;
+}
+
+int32_t abo_test_prune_levels(int32_t pre_rblocks, int64_t level2_min) {
+    if (pre_rblocks < -1 || level2_min < -1) return fail(ABO_EINVAL, "abo_test_prune_levels: pre_rblocks = %d, level2_min = %lld", pre_rblocks, (long long)level2_min);
+    g_prune_pre_rblocks.store(pre_rblocks);
+    g_prune_level2_min.store(level2_min);
+    return ABO_OK;
+}
+
+int32_t abo_test_prune_tail32(int32_t mode) {
+    if (mode < -1 || mode > 1) return fail(ABO_EINVAL, "abo_test_prune_tail32: mode = %d (-1 = the environment's, 0 = fp64, 1 = fp32)", mode);
+    g_prune_tail32.store(mode);
+    return ABO_OK;
+}
+
+int32_t abo_test_prune_head32(int32_t mode) {
+    if (mode < -1 || mode > 1) return fail(ABO_EINVAL, "abo_test_prune_head32: mode = %d (-1 = the environment's, 0 = int8 head, 1 = fused fp32 head)", mode);
+    g_prune_head32.store(mode);
+    return ABO_OK;
+}
+
+int32_t abo_test_bound_head32(abo_gp* g, const double* Z, int64_t M, int32_t rblocks, double* head, double* ssq, double* delta, double* l1) {
+    if (!g || !Z || !head || !ssq || !delta || !l1 || M <= 0 || rblocks <= 0) return fail(ABO_EINVAL, "abo_test_bound_head32: bad argument");
+    { int32_t rc = check_fitted(g, g->d); if (rc) return rc; }
+    if (g->p_out != 1) return fail(ABO_EINVAL, "abo_test_bound_head32: an ordinary model only");
+    const int rows = 256 * rblocks;
+    HIPCHK(hipSetDevice(g->prm.device));
+    hipStream_t s = g->stream;
+    // every output with one sentinel behind M / behind row R: the kernels write nothing there
+    ScratchBuf zd(g->prm.device, s), out(g->prm.device, s), wf(g->prm.device, s), dl(g->prm.device, s);
+    HIPCHK(zd.b.ensure(sizeof(double) * M * g->d));
+    HIPCHK(out.b.ensure(sizeof(double) * 2 * (M + 1)));
+    HIPCHK(wf.b.ensure(sizeof(float) * rows * rows));
+    HIPCHK(dl.b.ensure(sizeof(double) * 2 * (rows + 1)));
+    const std::vector<double> fill(2 * (size_t)(M + 1), -7.0), fill_r(2 * (size_t)(rows + 1), -7.0);
+    HIPCHK(hipMemcpyAsync(zd.b.p, Z, sizeof(double) * M * g->d, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(out.b.p, fill.data(), sizeof(double) * fill.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dl.b.p, fill_r.data(), sizeof(double) * fill_r.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(wait_stream(s));
+    OzPlan full;
+    if (!oz_make_plan(OZ_DEFAULT_NMOD, &full)) return fail(ABO_EINVAL, "abo_test_bound_head32: no plan");
+    KgenHead32Args ha{};
+    ha.Xs = g->st->Xs.as<double>(); ha.Z = zd.b.as<double>(); ha.alpha = g->alpha.as<double>(); ha.W = g->st->W.as<double>(); ha.ldw = g->st->cap;
+    ha.Wf = wf.b.as<float>(); ha.delta = dl.b.as<double>(); ha.l1 = dl.b.as<double>() + rows + 1;
+    ha.head = out.b.as<double>(); ha.ssq = out.b.as<double>() + M + 1;
+    ha.M = M; ha.N = (int)g->npts; ha.Np = (int)g->Np; ha.R = rows; ha.d = g->d; ha.dp = g->dp; ha.family = g->prm.family;
+    ha.s = 1.0 / g->prm.ell; ha.sigma_f2 = g->prm.sigma_f2; ha.mean_c = g->prm.mean_c;
+    ha.eP_full = full.eP; ha.sK_full = oz_k_scale(g->prm.sigma_f2);
+    ha.rec_full = (128.0 * full.n * full.n + 256.0 * full.n) * std::ldexp(1.0, full.eP - 91);
+    const hipError_t le = launch_kgen_head32(ha, s);
+    if (le == hipErrorInvalidValue) return fail(ABO_EINVAL, "abo_test_bound_head32: %d rows on a model of %lld points", rows, (long long)g->npts);
+    HIPCHK(le);
+    // head / ssq: M + 1 doubles each, delta / l1: rows + 1 — the last of each is the sentinel (−7) as the kernels left it
+    HIPCHK(hipMemcpyAsync(head, ha.head, sizeof(double) * (M + 1), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(ssq, ha.ssq, sizeof(double) * (M + 1), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(delta, ha.delta, sizeof(double) * (rows + 1), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(l1, ha.l1, sizeof(double) * (rows + 1), hipMemcpyDeviceToHost, s));
+    HIPCHK(wait_stream(s));
+    return ABO_OK;
+}
+
+int32_t abo_test_prune_plan_levels(int64_t rows, int64_t M, int32_t k, int32_t want_scores, int32_t kind, double p0, int32_t p_out,
+                                   int32_t int8_fused, int32_t d, int64_t* out) {
+    if (!out) return fail(ABO_EINVAL, "abo_test_prune_plan_levels: null argument");
+    const PrunePlan pp = prune_plan(rows, M, k, want_scores != 0, kind, p0, p_out, int8_fused != 0, d);
+    if (pp.rblocks0 >= pp.rblocks) return fail(ABO_EINVAL, "abo_test_prune_plan_levels: a first bound level of %d row blocks is not below the bound pass's %d", pp.rblocks0, pp.rblocks);
+    out[0] = pp.eligible; out[1] = pp.rblocks; out[2] = pp.k0; out[3] = pp.max_survivors; out[4] = pp.rblocks0;
+    return ABO_OK;
+}
+
+int32_t abo_test_prune_bound_moduli(int32_t n) {
+    if (n != 0 && n != 14 && !kgen_short_moduli(n)) return fail(ABO_EINVAL, "abo_test_prune_bound_moduli: n = %d (0 = default, 8, 9, 10, 14)", n);
+    g_prune_bound_moduli.store(n);
+    return ABO_OK;
+}
+
+int32_t abo_test_prune_bound_plan(abo_gp* g, int32_t* sexp_b, double* delta, int64_t n_rows) {
+    if (!g || !sexp_b || !delta || n_rows < 0) return fail(ABO_EINVAL, "abo_test_prune_bound_plan: bad argument");
+    if (!g->pst.bound_rows || g->pb_rows <= 0 || n_rows > g->pb_rows)
+        return fail(ABO_EINVAL, "abo_test_prune_bound_plan: the last abo_acq on this handle ran no bound pass on a short plan over %lld rows", (long long)n_rows);
+    HIPCHK(hipSetDevice(g->prm.device));
+    HIPCHK(hipMemcpyAsync(sexp_b, g->oz_sexpb.p, sizeof(int) * n_rows, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(delta, g->oz_delta.p, sizeof(double) * n_rows, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(wait_stream(g->stream));
+    return ABO_OK;
+}
+
+int32_t abo_test_prune_bounds(abo_gp* g, double* out, int64_t M) {
+    if (!g || !out || M < 0) return fail(ABO_EINVAL, "abo_test_prune_bounds: bad argument");
+    if (!g->pst.bound_rows || g->pr_ub.cap < sizeof(double) * (size_t)M) return fail(ABO_EINVAL, "abo_test_prune_bounds: the last abo_acq on this handle ran no bound pass over %lld candidates", (long long)M);
+    HIPCHK(hipSetDevice(g->prm.device));
+    HIPCHK(hipMemcpyAsync(out, g->pr_ub.p, sizeof(double) * M, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(wait_stream(g->stream));
+    return ABO_OK;
+}
+
+int32_t abo_test_prune_mean(abo_gp* g, double* mu, double* eps, int64_t M) {
+    if (!g || !mu || !eps || M < 0) return fail(ABO_EINVAL, "abo_test_prune_mean: bad argument");
+    if (!g->pst.bound_rows || g->pr_mut.cap < sizeof(double) * (size_t)M || g->pr_eps.cap < sizeof(double) * (size_t)M)
+        return fail(ABO_EINVAL, "abo_test_prune_mean: the last abo_acq on this handle ran no bound pass over %lld candidates", (long long)M);
+    HIPCHK(hipSetDevice(g->prm.device));
+    HIPCHK(hipMemcpyAsync(mu, g->pr_mut.p, sizeof(double) * M, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(eps, g->pr_eps.p, sizeof(double) * M, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(wait_stream(g->stream));
+    return ABO_OK;
+}
+
+int32_t abo_test_kappa_tail(int32_t device, int32_t family, const double* d2, double* out, int64_t n) {
+    if (!d2 || !out || n < 0) return fail(ABO_EINVAL, "abo_test_kappa_tail: bad argument");
+    if (family < ABO_KERNEL_SE || family > ABO_KERNEL_MATERN32) return fail(ABO_EINVAL, "abo_test_kappa_tail: unknown family");
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(launch_kappa_tail_test(family, d2, out, n, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_kappa_tail32(int32_t device, int32_t family, const double* d2, double* out, int64_t n) {
+    if (!d2 || !out || n < 0) return fail(ABO_EINVAL, "abo_test_kappa_tail32: bad argument");
+    if (family < ABO_KERNEL_SE || family > ABO_KERNEL_MATERN32) return fail(ABO_EINVAL, "abo_test_kappa_tail32: unknown family");
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(launch_kappa_tail32_test(family, d2, out, n, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_oz_plan(int32_t n, int32_t* p, double* tables, double* scal, int32_t* eP) {
+    if (!p || !tables || !scal || !eP) return fail(ABO_EINVAL, "abo_test_oz_plan: null argument");
+    OzPlan pl;
+    if (!oz_make_plan(n, &pl)) return fail(ABO_EINVAL, "abo_test_oz_plan: %d moduli not supported (8 … %d)", n, OZ_MAXMOD);
+    for (int l = 0; l < n; ++l) {
+        p[l] = pl.p[l];
+        tables[0 * OZ_MAXMOD + l] = pl.invp[l];
+        tables[1 * OZ_MAXMOD + l] = pl.c26[l];
+        tables[2 * OZ_MAXMOD + l] = pl.s1[l];
+        tables[3 * OZ_MAXMOD + l] = pl.s2[l];
+    }
+    scal[0] = pl.P1; scal[1] = pl.P2; scal[2] = pl.invP;
+    *eP = pl.eP;
+    return ABO_OK;
+}
+
+int32_t abo_test_oz_contract(int32_t device, const double* W, int64_t ldw, int32_t Np, int32_t nvalid, const double* Kxz, int64_t ldk,
+                             int32_t Mc, double kmax, int32_t nmod, double* partial, int64_t ldp) {
+    if (!W || !Kxz || !partial) return fail(ABO_EINVAL, "abo_test_oz_contract: null argument");
+    if (Np <= 0 || Np % TB || Mc <= 0 || Mc % TB || nvalid < 0 || nvalid > Np || ldw < Np || ldk < Np || ldp < Mc || !(kmax > 0.0))
+        return fail(ABO_EINVAL, "abo_test_oz_contract: Np and Mc multiples of 128, nvalid <= Np, leading dimensions >= Np / Mc, kmax > 0");
+    OzPlan pl;
+    if (!oz_make_plan(nmod, &pl)) return fail(ABO_EINVAL, "abo_test_oz_contract: %d moduli not supported", nmod);
+    HIPCHK(hipSetDevice(device));
+    const int64_t q = pad_up(Np, 256), mq = pad_up(Mc, 256);
+    ScratchBuf wr(device, nullptr), kr(device, nullptr), u(device, nullptr), ints(device, nullptr);
+    HIPCHK(wr.b.ensure(oz_w_bytes(nmod, Np)));
+    HIPCHK(kr.b.ensure(oz_k_bytes(nmod, Np, Mc)));
+    HIPCHK(u.b.ensure(oz_k_bytes(nmod, Np, Mc)));
+    HIPCHK(ints.b.ensure(sizeof(int) * (2 * q + mq + OZ_CTR_INTS)));
+    int* sexp = ints.b.as<int>();
+    HIPCHK(oz_prepare_w(pl, W, ldw, Np, nvalid, wr.b.as<int8_t>(), sexp, sexp + q, nullptr));
+    OzVarArgs oa{};
+    oa.plan = &pl; oa.Kxz = Kxz; oa.ldk = ldk; oa.WR = wr.b.as<int8_t>(); oa.sexp = sexp; oa.bad_row = sexp + q;
+    oa.KR = kr.b.as<int8_t>(); oa.U = u.b.as<int8_t>(); oa.bad_col = sexp + 2 * q; oa.partial = partial; oa.ldp = ldp;
+    oa.Np = Np; oa.Mc = Mc; oa.nvalid = nvalid; oa.sK = oz_k_scale(kmax);
+    HIPCHK(launch_var_ozaki(oa, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_oz_contract_bound(int32_t device, const double* W, int64_t ldw, int32_t Np, int32_t nvalid, const double* Kxz, int64_t ldk,
+                                   int32_t Mc, double kmax, int32_t nmod_b, int32_t rblocks, double* partial, int64_t ldp, double* delta) {
+    if (!W || !Kxz || !partial || !delta) return fail(ABO_EINVAL, "abo_test_oz_contract_bound: null argument");
+    const int rows = 256 * rblocks;
+    if (Np <= 0 || Np % TB || Mc <= 0 || Mc % TB || nvalid < 0 || nvalid > Np || ldw < Np || ldk < Np || ldp < Mc || !(kmax > 0.0) ||
+        rblocks <= 0 || rows > pad_up(Np, 256))
+        return fail(ABO_EINVAL, "abo_test_oz_contract_bound: Np and Mc multiples of 128, nvalid <= Np, leading dimensions >= Np / Mc, kmax > 0, 256·rblocks <= pad256(Np)");
+    OzPlan pl, full;
+    if (!oz_make_plan(nmod_b, &pl) || !oz_make_plan(14, &full)) return fail(ABO_EINVAL, "abo_test_oz_contract_bound: %d moduli not supported", nmod_b);
+    HIPCHK(hipSetDevice(device));
+    const int64_t q = pad_up(Np, 256), mq = pad_up(Mc, 256);
+    ScratchBuf wr(device, nullptr), kr(device, nullptr), u(device, nullptr), ints(device, nullptr);
+    HIPCHK(wr.b.ensure((size_t)nmod_b * rows * q));
+    HIPCHK(kr.b.ensure(oz_k_bytes(nmod_b, Np, Mc)));
+    HIPCHK(u.b.ensure(oz_k_bytes(nmod_b, Np, Mc)));
+    HIPCHK(ints.b.ensure(sizeof(int) * (2 * q + mq + OZ_CTR_INTS)));
+    int* sexp = ints.b.as<int>();
+    const int bK = oz_bound_kbits(pl.eP, rows);
+    const int sKb = oz_k_scale(kmax, bK);
+    HIPCHK(oz_prepare_w_bound(pl, full, W, ldw, Np, nvalid, rows, bK, sKb, oz_k_scale(kmax), kmax * (1.0 + 0x1p-40), wr.b.as<int8_t>(), sexp, sexp + q,
+                              delta, nullptr));
+    OzVarArgs oa{};
+    oa.plan = &pl; oa.Kxz = Kxz; oa.ldk = ldk; oa.WR = wr.b.as<int8_t>(); oa.sexp = sexp; oa.bad_row = sexp + q;
+    oa.KR = kr.b.as<int8_t>(); oa.U = u.b.as<int8_t>(); oa.bad_col = sexp + 2 * q; oa.partial = partial; oa.ldp = ldp;
+    oa.Np = Np; oa.Mc = Mc; oa.nvalid = nvalid; oa.sK = sKb; oa.rblocks = rblocks; oa.delta = delta; oa.w_plane = (int64_t)rows * q;
+    HIPCHK(launch_var_ozaki(oa, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_kappa(int32_t device, int32_t family, const double* d2, double* out, int64_t n) {
+    if (!d2 || !out || n < 0) return fail(ABO_EINVAL, "abo_test_kappa: bad argument");
+    if (family < ABO_KERNEL_SE || family > ABO_KERNEL_MATERN32) return fail(ABO_EINVAL, "abo_test_kappa: unknown family");
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(launch_kappa_test(family, d2, out, n, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_gemm_nt(int32_t device, const double* A, const double* B, double* C, int32_t M, int32_t N, int32_t K,
+                         int64_t lda, int64_t ldb, int64_t ldc, double alpha, double beta) {
+    if (!A || !B || !C) return fail(ABO_EINVAL, "abo_test_gemm_nt: null argument");
+    if (M <= 0 || N <= 0 || K <= 0 || M % 128 || N % 128 || K % 16 || (lda & 1) || (ldb & 1))
+        return fail(ABO_EINVAL, "abo_test_gemm_nt: M, N must be multiples of 128, K of 16, lda/ldb even");
+    HIPCHK(hipSetDevice(device));
+    GemmArgs a{};
+    a.A = A; a.B = B; a.C = C; a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.M = M; a.N = N; a.K = K;
+    a.kmode = K_FULL; a.batch = 1; a.alpha = alpha; a.beta = beta;
+    HIPCHK(launch_gemm_nt(a, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+// what the GEMM kernels assume of shapes and flags (no pointer is looked at): nullptr, or the text of the complaint
+static const char* gemm_args_complaint(const GemmArgs& a) {
+    if (a.M <= 0 || a.N <= 0 || a.M % TB || a.N % TB) return "M, N must be positive multiples of 128";
+    if (a.K <= 0 || a.K % 16) return "K must be a positive multiple of 16";
+    if (a.kmode < K_FULL || a.kmode > K_B_UPPER) return "unknown kmode";
+    if (a.batch < 1 || a.ksplit < 0 || a.mrows < 0) return "batch >= 1, ksplit >= 0, mrows >= 0";
+    if (a.ksplit && (a.K % 128 || a.ksplit % 128)) return "split-k: K and ksplit must be multiples of 128";
+    if (a.ksplit && (a.batch != 1 || a.beta != 0.0 || a.Ct)) return "split-k: batch == 1, beta == 0, no Ct";
+    return nullptr;
+}
+
+int32_t abo_test_gemm_path(int32_t M, int32_t N, int32_t K, int32_t kmode, int32_t lower_only, int32_t batch, int32_t ksplit,
+                           int32_t mrows, int32_t in_place, int32_t* path) {
+    if (!path) return fail(ABO_EINVAL, "abo_test_gemm_path: null argument");
+    static double op[3];                       // three distinct addresses; never dereferenced
+    GemmArgs a{};
+    a.A = &op[0]; a.B = &op[1]; a.C = in_place ? &op[0] : &op[2];
+    a.M = M; a.N = N; a.K = K; a.kmode = kmode; a.lower_only = lower_only; a.batch = batch; a.alpha = 1.0; a.ksplit = ksplit; a.mrows = mrows;
+    if (const char* why = gemm_args_complaint(a)) return fail(ABO_EINVAL, "abo_test_gemm_path: %s", why);
+    *path = gemm_nt_path(a);
+    return ABO_OK;
+}
+
+int32_t abo_test_gemm_swz_map(int32_t T, int32_t G, int32_t Q, int32_t* ti, int32_t* tj) {
+    if (!ti || !tj) return fail(ABO_EINVAL, "abo_test_gemm_swz_map: null argument");
+    if (T < 1 || T > 4096 || G < 1 || Q < 0 || Q >= T * (T + 1) / 2) return fail(ABO_EINVAL, "abo_test_gemm_swz_map: 1 <= T <= 4096, G >= 1, 0 <= Q < T(T+1)/2");
+    int i = -1, j = -1;
+    gemm_swz_tile(T, G, Q, i, j);
+    *ti = i; *tj = j;
+    return ABO_OK;
+}
+
+int32_t abo_test_gemm_swz_q(int32_t tiles, int32_t L, int32_t* Q) {
+    if (!Q) return fail(ABO_EINVAL, "abo_test_gemm_swz_q: null argument");
+    if (tiles < 1 || L < 0 || L >= (tiles + 7) / 8 * 8) return fail(ABO_EINVAL, "abo_test_gemm_swz_q: tiles >= 1, 0 <= L < ceil(tiles / 8) * 8");
+    *Q = gemm_swz_q(L, tiles);
+    return ABO_OK;
+}
+
+int32_t abo_test_gemm_args(int32_t device, const double* A, const double* B, double* C, double* Ct, int64_t lda, int64_t ldb, int64_t ldc,
+                           int64_t ldct, int64_t sA, int64_t sB, int64_t sC, int64_t sCt, int32_t M, int32_t N, int32_t K, int32_t kmode,
+                           int32_t lower_only, int32_t batch, double alpha, double beta, int32_t ksplit, int32_t mrows, const int64_t* info,
+                           int32_t* path) {
+    if (!A || !B || !C || !path) return fail(ABO_EINVAL, "abo_test_gemm_args: null argument");
+    GemmArgs a{};
+    a.A = A; a.B = B; a.C = C; a.Ct = Ct; a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.ldct = ldct; a.sA = sA; a.sB = sB; a.sC = sC; a.sCt = sCt;
+    a.M = M; a.N = N; a.K = K; a.kmode = kmode; a.lower_only = lower_only; a.batch = batch; a.alpha = alpha; a.beta = beta; a.info = info;
+    a.ksplit = ksplit; a.mrows = mrows;
+    if (const char* why = gemm_args_complaint(a)) return fail(ABO_EINVAL, "abo_test_gemm_args: %s", why);
+    if ((lda & 1) || (ldb & 1) || lda < K || ldb < K || ldc < N || (Ct && ldct < M) || ((sA | sB) & 1) || sA < 0 || sB < 0 || sC < 0 || sCt < 0)
+        return fail(ABO_EINVAL, "abo_test_gemm_args: lda, ldb even and >= K, ldc >= N, ldct >= M, batch strides >= 0 (those of A and B even)");
+    const int p = gemm_nt_path(a);
+    if (p == GEMM_PATH_SKINNY && (kmode == K_A_LOWER || kmode == K_A_UPPER))
+        return fail(ABO_EINVAL, "abo_test_gemm_args: the skinny split-k kernel knows K_FULL, K_B_LOWER and K_B_UPPER only");
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(launch_gemm_nt(a, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    *path = p;
+    return ABO_OK;
+}
+
+int32_t abo_test_qei_pass(int32_t device, const double* A, int64_t lda, int32_t rows16, const double* B, int64_t ldb, int64_t nB, int32_t K,
+                          double alpha, double* C, int64_t ldc, int32_t kmode, int32_t ksplit, int64_t sC) {
+    if (!A || !B || !C) return fail(ABO_EINVAL, "abo_test_qei_pass: null argument");
+    if (lda < K || ldb < K || ldc < nB || sC < 0) return fail(ABO_EINVAL, "abo_test_qei_pass: lda, ldb >= K, ldc >= nB, sC >= 0");
+    HIPCHK(hipSetDevice(device));
+    const hipError_t e = launch_qei_pass(A, lda, rows16, B, ldb, nB, K, alpha, C, ldc, nullptr, kmode, ksplit, sC);
+    if (e == hipErrorInvalidValue) return fail(ABO_EINVAL, "abo_test_qei_pass: launch_qei_pass refused rows16 = %d, nB = %lld, K = %d, lda = %lld, ldb = %lld, kmode = %d, ksplit = %d",
+                                                rows16, (long long)nB, K, (long long)lda, (long long)ldb, kmode, ksplit);
+    HIPCHK(e);
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_splitk_reduce(int32_t device, const double* P, int64_t ldp, int64_t sP, int32_t nz, int32_t rows, int32_t cols, int32_t K,
+                               int32_t ksplit, int32_t kmode, double* out, int64_t ldo) {
+    if (!P || !out) return fail(ABO_EINVAL, "abo_test_splitk_reduce: null argument");
+    if (rows <= 0 || cols <= 0 || (cols & 1) || (ldp & 1) || (ldo & 1) || (sP & 1) || ldp < cols || ldo < cols || sP < 0 || nz < 1 || K <= 0 ||
+        ksplit <= 0 || ksplit % 128 || (int64_t)nz * ksplit < K)
+        return fail(ABO_EINVAL, "abo_test_splitk_reduce: rows > 0, cols > 0 and even, ldp / ldo / sP even, ldp, ldo >= cols, ksplit a multiple of 128, nz chunks covering K");
+    if (kmode != K_FULL && kmode != K_B_LOWER && kmode != K_B_UPPER) return fail(ABO_EINVAL, "abo_test_splitk_reduce: kmode must be K_FULL, K_B_LOWER or K_B_UPPER");
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(launch_splitk_reduce(P, ldp, sP, nz, rows, cols, K, ksplit, kmode, out, ldo, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_var_gemm(int32_t device, const double* W, int64_t ldw, int32_t Np, int32_t nvalid, const double* Kxz, int64_t ldk, int32_t Mc,
+                          double* partial, int64_t ldp, int32_t variant) {
+    if (!W || !Kxz || !partial) return fail(ABO_EINVAL, "abo_test_var_gemm: null argument");
+    if (Np <= 0 || Np % TB || Mc <= 0 || Mc % TB || nvalid < 0 || nvalid > Np || ldw < Np || ldk < Np || (ldw & 1) || (ldk & 1) || ldp < Mc)
+        return fail(ABO_EINVAL, "abo_test_var_gemm: Np and Mc multiples of 128, nvalid <= Np, ldw / ldk even and >= Np, ldp >= Mc");
+    if (variant != 0 && variant != 1) return fail(ABO_EINVAL, "abo_test_var_gemm: variant 0 (the launcher's rule) or 1 (the 128-row kernel)");
+    HIPCHK(hipSetDevice(device));
+    VarGemmArgs va{};
+    va.W = W; va.Kxz = Kxz; va.partial = partial; va.ldw = ldw; va.ldk = ldk; va.ldp = ldp; va.Np = Np; va.Mc = Mc; va.nvalid = nvalid;
+    HIPCHK(launch_var_gemm(va, nullptr, variant));
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+// launch_kgen with every field of KgenArgs as the caller gives it: no decision about shape, engine or dispatch is taken here
+int32_t abo_test_kgen(int32_t device, const abo_test_kgen_args* t) {
+    if (!t || !t->Xs || !t->Z) return fail(ABO_EINVAL, "abo_test_kgen: null argument");
+    if (t->n_mean < 0 || t->n_mean > MAX_P || (t->n_mean > 0 && !t->mean_vec)) return fail(ABO_EINVAL, "abo_test_kgen: n_mean in [0, %d] with mean_vec given", MAX_P);
+    KgenArgs a{};
+    a.Xs = t->Xs; a.Z = t->Z; a.alpha = t->alpha; a.Kout = t->Kout; a.mu = t->mu; a.ldk = t->ldk; a.M = t->M; a.j0 = t->j0; a.Mc = t->Mc;
+    a.N = t->N; a.Np = t->Np; a.d = t->d; a.dp = t->dp; a.family = t->family; a.s = t->s; a.sigma_f2 = t->sigma_f2;
+    for (int q = 0; q < t->n_mean; ++q) a.mean_vec[q] = t->mean_vec[q];
+    a.mean_c = t->n_mean > 0 ? t->mean_vec[0] : 0.0;
+    a.pt = t->pt; a.pc = t->pc; a.point_major = t->point_major; a.dlogell = t->dlogell; a.rvalid = t->rvalid;
+    a.res = t->res; a.res_ld = t->res_ld; a.res_plane = t->res_plane; a.res_bad = t->res_bad; a.res_n = t->res_n; a.res_sK = t->res_sK;
+    a.res_ktg = t->res_ktg; a.res_kmax = t->res_kmax;
+    HIPCHK(hipSetDevice(device));
+    const hipError_t e = launch_kgen(a, nullptr);
+    if (e == hipErrorInvalidValue)
+        return fail(ABO_EINVAL, "abo_test_kgen: launch_kgen refused family = %d, dp = %d, pt = %d, dlogell = %d, res_n = %d, res_kmax = %d, Np = %d",
+                    a.family, a.dp, a.pt, a.dlogell, a.res ? a.res_n : 0, a.res_kmax, a.Np);
+    HIPCHK(e);
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_cand_newcol(int32_t device, const double* Xs, const double* Z, double* Kzx, int64_t ld, int64_t M, int32_t col, int32_t grad,
+                             int32_t pt, int32_t q, int32_t d, int32_t dp, int32_t family, double s, double sigma_f2) {
+    if (!Xs || !Z || !Kzx) return fail(ABO_EINVAL, "abo_test_cand_newcol: null argument");
+    HIPCHK(hipSetDevice(device));
+    const hipError_t e = grad ? launch_cand_newcol_grad(Xs, Z, Kzx, ld, M, col, pt, q, d, dp, family, s, sigma_f2, nullptr)
+                              : launch_cand_newcol(Xs, Z, Kzx, ld, M, col, d, dp, family, s, sigma_f2, nullptr);
+    if (e == hipErrorInvalidValue) return fail(ABO_EINVAL, "abo_test_cand_newcol: the launcher refused family = %d (grad = %d)", family, grad);
+    HIPCHK(e);
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+}  // extern "C"

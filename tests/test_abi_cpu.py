@@ -75,6 +75,29 @@ def test_argument_validation_needs_no_gpu():
     assert lib.abo_destroy(None) == abo._lib.ABO_OK
 
 
+def test_every_host_unit_reports_through_the_one_error_slot():
+    """The host driver is two translation units (api.hip, and test_hooks.hip in the test library) with ONE last-error slot per thread,
+    defined in api.hip: null-argument calls across its surfaces and into a hook — the argument check is the first thing each of these
+    does, no device is touched — return ABO_EINVAL, and abo_last_error then holds THAT call's message, the function's name in it.  A
+    unit with a private copy of the slot would leave the previous call's text (or none) there."""
+    lib = abo._lib.lib()
+    calls = [
+        ("abo_create", lambda: lib.abo_create(None, None)),
+        ("abo_fit", lambda: lib.abo_fit(None, None, 1, 1, None, 0, None)),
+        ("abo_nlml", lambda: lib.abo_nlml(None, None)),
+        ("abo_predict_cov", lambda: lib.abo_predict_cov(None, None, 1, None, 0, 1, 0, None, None, None, 0)),
+        ("abo_acq_lhs", lambda: lib.abo_acq_lhs(None, 1, 1, None, None, 0, 0, 0.0, 0.0, 1, None, None, None)),
+        ("abo_refine", lambda: lib.abo_refine(None, 0, 0.0, 0.0, None, None, 1, None, 0, None, None, None, None)),
+        ("abo_fit_acq", lambda: lib.abo_fit_acq(None, None, 1, 1, None, 0, None, None, 0, 0, 0, 0.0, 0.0, 0, None, 0, None, None, 0)),
+        ("abo_cand_create", lambda: lib.abo_cand_create(None, None, 0, 1, 0, None)),
+        ("abo_test_acq_grad", lambda: lib.abo_test_acq_grad(None, 0, 0.0, 0.0, None, 0, 1, None, None)),          # test_hooks.hip, the other unit
+    ]
+    for name, call in calls + calls[::-1]:              # both orders: every message replaces its predecessor's
+        assert call() == abo._lib.ABO_EINVAL, name
+        msg = abo._lib.last_error()
+        assert name in msg and "null" in msg, (name, msg)
+
+
 @pytest.mark.skipif(_has_gpu(), reason="only meaningful on a box without a GPU")
 def test_product_path_fails_loudly_without_gpu():
     gp = abo.HipStandardGP(abo.SqExponentialKernel(), 0.1)

@@ -307,3 +307,22 @@ def test_build_staleness_is_decided_by_content_not_by_time_stamps(monkeypatch, t
     assert not b._stale()
     lib.write_bytes(b"another library copied over it")           # the motivating case: the file is replaced, the manifest stays
     assert b._stale()
+
+
+def test_the_hooks_are_a_unit_of_their_own_and_nothing_is_compiled_twice():
+    """Nothing is compiled a second time under another flag (no HOOK_SOURCES): both libraries link the same objects, and every .hip of
+    csrc/ is linked — into both libraries, or, test_hooks.hip alone, into the test library."""
+    import importlib.util
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("_abo_build_u", os.path.join(root, "abstractbayesopt.jl_amd", "build.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    assert not hasattr(b, "HOOK_SOURCES")
+    assert len(set(b.SOURCES)) == len(b.SOURCES) and "test_hooks.hip" not in b.SOURCES
+    on_disk = sorted(f for f in os.listdir(b.CSRC) if f.endswith(".hip"))
+    assert on_disk == sorted(b.SOURCES + ["test_hooks.hip"])
+    # the hooks' compile flag is named by their unit and by no other file of csrc/
+    for f in os.listdir(b.CSRC):
+        if f != "test_hooks.hip":
+            assert "ABO_TEST_HOOKS" not in open(os.path.join(b.CSRC, f)).read(), f
