@@ -31,7 +31,9 @@ TEST_EXPORTS = ["abo_test_gemm_nt", "abo_test_kappa", "abo_test_oz_plan", "abo_t
                 "abo_test_acq_grad_terms", "abo_test_prune_plan", "abo_test_prune_force", "abo_test_prune_levels", "abo_test_prune_plan_levels", "abo_test_prune_bounds", "abo_test_prune_mean",
                 "abo_test_kappa_tail", "abo_test_prune_tail32", "abo_test_prune_head32", "abo_test_bound_head32", "abo_test_kappa_tail32", "abo_test_prune_bound_moduli", "abo_test_prune_bound_plan", "abo_test_oz_contract_bound", "abo_test_acq_partials", "abo_test_mes_partials", "abo_test_acq_grad_mes",
                 "abo_test_gemm_args", "abo_test_gemm_path", "abo_test_gemm_swz_q", "abo_test_gemm_swz_map", "abo_test_qei_pass", "abo_test_splitk_reduce",
-                "abo_test_var_gemm", "abo_test_kgen", "abo_test_cand_newcol"]
+                "abo_test_var_gemm", "abo_test_kgen", "abo_test_cand_newcol",
+                "abo_test_chol_diag", "abo_test_chol_panel", "abo_test_trtri_batched", "abo_test_chol_blocked", "abo_test_trmv",
+                "abo_test_nlml_terms", "abo_test_append"]
 # what launch_gemm_nt ran, as abo_test_gemm_args / abo_test_gemm_path report it (include/abo_hip.h: ABO_GEMM_PATH_*)
 GEMM_PATH_TILED, GEMM_PATH_SWIZZLED, GEMM_PATH_SMALL, GEMM_PATH_SKINNY, GEMM_PATH_SPLITK = range(5)
 K_FULL, K_A_LOWER, K_A_UPPER, K_B_LOWER, K_B_UPPER = range(5)
@@ -121,6 +123,13 @@ class AboTestKgenArgs(C.Structure):
                [(n, C.c_int32) for n in ("pt", "pc", "point_major", "dlogell", "rvalid", "n_mean")] + \
                [("res", C.c_void_p), ("res_ld", C.c_int64), ("res_plane", C.c_int64), ("res_bad", C.c_void_p)] + \
                [(n, C.c_int32) for n in ("res_n", "res_sK", "res_ktg", "res_kmax")]
+
+
+class AboTestAppendArgs(C.Structure):
+    """every field of the bordered append's argument block, for abo_test_append (include/abo_hip.h: abo_test_append_args; test build only)"""
+    _fields_ = [(n, C.c_void_p) for n in ("L", "W", "WT")] + [("ld", C.c_int64)] + \
+               [(n, C.c_void_p) for n in ("krow", "lvec", "vvec", "alpha_old", "alpha_new", "vext", "delta")] + \
+               [("N", C.c_int32), ("cap", C.c_int32), ("kss", C.c_double), ("scal", C.c_void_p), ("info", C.c_void_p)]
 
 
 class PosDefException(Exception):
@@ -237,6 +246,13 @@ def lib():
         L.abo_test_var_gemm.argtypes = [i32, vp, i64, i32, i32, vp, i64, i32, vp, i64, i32]
         L.abo_test_kgen.argtypes = [i32, C.POINTER(AboTestKgenArgs)]
         L.abo_test_cand_newcol.argtypes = [i32, vp, vp, vp, i64, i64, i32, i32, i32, i32, i32, i32, i32, f64, f64]
+        L.abo_test_chol_diag.argtypes = [i32, vp, vp, vp, i64, i32, vp]
+        L.abo_test_chol_panel.argtypes = [i32, vp, vp, vp, i64, i32, i32, i32, vp]
+        L.abo_test_trtri_batched.argtypes = [i32, vp, vp, vp, i64, i32, vp]
+        L.abo_test_chol_blocked.argtypes = [i32, vp, vp, vp, i64, i32, i32, i32, i32, vp]
+        L.abo_test_trmv.argtypes = [i32, vp, i64, vp, vp, i32, i32]
+        L.abo_test_nlml_terms.argtypes = [i32, vp, i64, vp, vp, i32, vp]
+        L.abo_test_append.argtypes = [i32, C.POINTER(AboTestAppendArgs)]
     L.abo_mgpu_create.argtypes = [C.POINTER(AboParams), i32, C.POINTER(i32), C.POINTER(vp)]
     L.abo_mgpu_create_grad.argtypes = [C.POINTER(AboParams), i32, vp, i32, C.POINTER(i32), C.POINTER(vp)]
     L.abo_mgpu_append_grad.argtypes = [vp, vp, i32, vp, C.POINTER(i64), vp]

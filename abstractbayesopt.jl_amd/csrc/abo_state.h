@@ -251,6 +251,15 @@ extern std::atomic<int64_t> g_prune_level2_min;     // … and the survivor coun
 extern std::atomic<int> g_prune_tail32;             // abo_test_prune_tail32: 0 / 1 = the first level's tail in fp64 / fp32, −1 = the environment's
 extern std::atomic<int> g_prune_head32;             // abo_test_prune_head32: 0 / 1 = the first level's head on the int8 engine / fused in fp32, −1 = the environment's
 
+// ---- the blocked factorisation on raw pointers (api.hip: factorise runs exactly these two, with the default blocking) -----------------
+// SW: columns of a strip, SSmax: of a super-strip, used while at least super_rows rows remain (multiples of 128, SSmax of SW)
+struct CholBlocking { int SW = 512, SSmax = 1024, super_rows = 6144; };
+// K [Np][ld] → L in place (lower), the 16×16 / 128×128 diagonal inverses in W / WT (rows < Np of both zeroed outside them when
+// Np > 128); T: TRSM_STREAM_BYTES of scratch.  Launches only; a failing pivot is reported in *info (device), preset by the caller.
+int32_t chol_blocked(double* K, double* W, double* WT, double* T, int64_t ld, int Np, int64_t* info, const CholBlocking& blk, hipStream_t s);
+// W = L⁻¹ (lower), WT = its transpose (upper) from the diagonal blocks' inverses, by recursive doubling; T: Np·Np doubles of scratch
+int32_t trinv_blocked(double* K, double* W, double* WT, double* T, int64_t ld, int Np, int64_t* info, hipStream_t s);
+
 struct RefineOpts { int max_iter, ls_max, history; double g_tol, f_abstol, x_abstol; };
 RefineOpts refine_defaults(const abo_refine_opts* o);
 int32_t check_refinable(abo_gp* g, int32_t d, const char* fn);

@@ -403,57 +403,25 @@ constexpr size_t EV_BASE = 16;        // 0-4 fit phases, 5-7 acquisition call, 8
                                       // posterior call, or (inside a fit) the strip events of the factorisation's look-ahead
 constexpr size_t EV_PER_CHUNK = 8;   // kgen 0-1, contraction 2-3, epilogue 4-5, int8 pipeline: end of quantisation 6, end of GEMM 7
 
-// Right-looking blocked Cholesky, 128-wide panels, then L⁻¹ by recursive doubling.
-// info_host == nullptr: launches only — the caller synchronises later and then looks at g->h_info / calls fit_collect().
-int32_t factorise(abo_gp* g, double noise, int64_t* info_host) {
-    hipStream_t s = g->stream;
-    Storage* st = g->st;
-    const int Np = (int)g->Np, N = (int)g->N;
-    const int64_t ld = st->cap;
-    double* K = st->K.as<double>();
-    double* W = st->W.as<double>();
-    double* WT = st->WT.as<double>();
-    HIPCHK(g->info.ensure(sizeof(int64_t)));
-    int64_t* info = g->info.as<int64_t>();              // the LAPACK-style status
+}  // namespace
 
-    HIPCHK(hipEventRecord(g->evs()[0], s));
-    // whole capacity region: zeros, identity on the padded diagonal (rows ≥ N), K on the active part.  With a panel chain (more than
-    // one block) rows < Np of W / WT are zeroed by the chain's own launches — the idle workgroups of each diagonal-block launch take
-    // that panel's rows (chol.hip: potf2_pipe_kernel) — instead of two whole-matrix memsets in front of the fit (148 µs at N = 8192).
+namespace abo {    // shared with test_hooks.hip (abo_state.h)
+
+// Right-looking blocked Cholesky of K [Np][ld], 128-wide panels; the 128×128 inverses of the diagonal blocks go to W / WT.
+int32_t chol_blocked(double* K, double* W, double* WT, double* T, int64_t ld, int Np, int64_t* info, const CholBlocking& blk, hipStream_t s) {
     const bool split = Np > TB;                            // a single block has no chain: factor + inverse in one launch
-    if (ld > Np) HIPCHK(hipMemsetAsync(K, 0, sizeof(double) * ld * ld, s));
-    if (!split) {
-        HIPCHK(hipMemsetAsync(W, 0, sizeof(double) * ld * ld, s));
-        HIPCHK(hipMemsetAsync(WT, 0, sizeof(double) * ld * ld, s));
-    } else if (ld > Np) {
-        HIPCHK(hipMemsetAsync(W + (int64_t)Np * ld, 0, sizeof(double) * (ld - Np) * ld, s));
-        HIPCHK(hipMemsetAsync(WT + (int64_t)Np * ld, 0, sizeof(double) * (ld - Np) * ld, s));
-    }
-    KgenArgs ka{};
-    ka.Xs = st->Xs.as<double>(); ka.Z = st->Xraw.as<double>(); ka.alpha = nullptr; ka.Kout = K; ka.mu = nullptr;
-    ka.ldk = ld; ka.M = g->npts; ka.j0 = 0; ka.Mc = Np; ka.N = (int)g->npts; ka.Np = Np; ka.d = g->d; ka.dp = g->dp;
-    ka.family = g->prm.family; ka.s = 1.0 / g->prm.ell; ka.sigma_f2 = g->prm.sigma_f2; ka.mean_c = 0.0;
-    ka.pt = g->p_out; ka.pc = g->p_out; ka.point_major = 1;      // K_XX: rows and columns point-major → symmetric
-    HIPCHK(launch_kgen(ka, s));
-    HIPCHK(launch_diag_fix(K, ld, N, (int)ld, noise, s, info));      // also resets the status word
-    if (ld > Np) {
-        HIPCHK(launch_set_diag(W, ld, Np, (int)ld, 1.0, s));
-        HIPCHK(launch_set_diag(WT, ld, Np, (int)ld, 1.0, s));
-    }
-    PHASE_EVENT(g->evs()[1], s);
-
     // Two-level blocking: inside a strip of SW columns the 128-wide panels update only the rest of the strip
     // (K = 128 products on a tall, narrow block); the matrix behind the strip is updated once per strip with
     // K = SW — a quarter of the read-modify-write passes over the trailing matrix and four times longer k loops
     // per tile than a panel-by-panel SYRK.
-    constexpr int SW = 512;
+    const int SW = blk.SW;
     // Third level: strips grouped into super-strips of 1024 columns — behind a strip only the rest of its super-strip is updated
     // (K = SW), the matrix behind the super-strip once per super-strip with K = SS: half the passes over the trailing matrix and
     // tiles twice as long (Cholesky at N = 16384 35.0 → 32.8 ms, at N = 8192 8.20 → 8.23: profiles/r03_chol_super_sweep.txt).  A
     // super-strip pays while the square update behind it is large — its in-super-strip update is a launch of 4 × T tiles that lasts
     // ≈ 150 µs whatever T is, against K = 1024 tiles at 70 TFLOP/s instead of 52 (profiles/r04_fit_trace_summary.txt) — so
     // super-strips are used while at least 6144 rows remain, plain strips from there on.
-    constexpr int SSmax = 1024, super_rows = 6144;
+    const int SSmax = blk.SSmax, super_rows = blk.super_rows;
     // Panel chain: potf2 of the diagonal block (potf2_pipe_kernel) → triangular solve of the rows below it from the operand stream that
     // kernel leaves (trsm_stream_kernel; the stream lives in T, which the factorisation does not use — the blocked inverse behind it
     // does) → in-strip update.  The 128×128 inverses of the diagonal blocks (the seeds of the blocked L⁻¹ below) are not on that chain:
@@ -461,8 +429,7 @@ int32_t factorise(abo_gp* g, double noise, int64_t* info_host) {
     // from the library in round 6): a two-stream look-ahead, one launch per panel with in-launch hand-overs, 256 × 128 trailing tiles;
     // round 6: the same look-ahead on CU-MASKED streams (hipExtStreamCreateWithCUMask: chain and trailing update on disjoint compute
     // units, so the chain never waits for a slot) — 7.4 – 9.1 ms against 7.0 at N = 8192 (profiles/r06_chol_lookahead_cumask_ab.txt).
-    if (split) HIPCHK(g->T.ensure(TRSM_STREAM_BYTES));
-    double* trsm_ops = g->T.as<double>();
+    double* trsm_ops = T;
     for (int S0 = 0, SS = SW; S0 < Np; S0 += SS) {
         SS = (Np - S0) >= super_rows ? SSmax : SW;
         const int ss = (Np - S0) < SS ? (Np - S0) : SS;
@@ -513,12 +480,13 @@ int32_t factorise(abo_gp* g, double noise, int64_t* info_host) {
         }
     }
     if (split) HIPCHK(launch_trtri_diag_batched(K, W, WT, ld, Np / TB, info, s));
-    PHASE_EVENT(g->evs()[2], s);
-    // no host round trip here: after a failed pivot every later kernel of the fit either exits on `info` (the GEMMs) or
-    // works on finite leftovers whose results are discarded; `info` is read once, with the scalars, at the end
+    return ABO_OK;
+}
 
+// L⁻¹ by recursive doubling from the diagonal blocks' inverses.
+int32_t trinv_blocked(double* K, double* W, double* WT, double* T, int64_t ld, int Np, int64_t* info, hipStream_t s) {
     // W = L⁻¹: [[W11,0],[−W22·L21·W11, W22]] level by level (block size s doubles each level)
-    double* Tt = g->T.as<double>();
+    double* Tt = T;
     for (int64_t sz = TB; sz < Np; sz *= 2) {
         const int64_t two = 2 * sz;
         const int nfull = (int)(Np / two);
@@ -550,6 +518,60 @@ int32_t factorise(abo_gp* g, double noise, int64_t* info_host) {
             HIPCHK(launch_gemm_nt(b, s));
         }
     }
+    return ABO_OK;
+}
+
+}  // namespace abo
+
+namespace {
+
+// Right-looking blocked Cholesky, 128-wide panels, then L⁻¹ by recursive doubling.
+// info_host == nullptr: launches only — the caller synchronises later and then looks at g->h_info / calls fit_collect().
+int32_t factorise(abo_gp* g, double noise, int64_t* info_host) {
+    hipStream_t s = g->stream;
+    Storage* st = g->st;
+    const int Np = (int)g->Np, N = (int)g->N;
+    const int64_t ld = st->cap;
+    double* K = st->K.as<double>();
+    double* W = st->W.as<double>();
+    double* WT = st->WT.as<double>();
+    HIPCHK(g->info.ensure(sizeof(int64_t)));
+    int64_t* info = g->info.as<int64_t>();              // the LAPACK-style status
+
+    HIPCHK(hipEventRecord(g->evs()[0], s));
+    // whole capacity region: zeros, identity on the padded diagonal (rows ≥ N), K on the active part.  With a panel chain (more than
+    // one block) rows < Np of W / WT are zeroed by the chain's own launches — the idle workgroups of each diagonal-block launch take
+    // that panel's rows (chol.hip: potf2_pipe_kernel) — instead of two whole-matrix memsets in front of the fit (148 µs at N = 8192).
+    const bool split = Np > TB;                            // a single block has no chain: factor + inverse in one launch
+    if (ld > Np) HIPCHK(hipMemsetAsync(K, 0, sizeof(double) * ld * ld, s));
+    if (!split) {
+        HIPCHK(hipMemsetAsync(W, 0, sizeof(double) * ld * ld, s));
+        HIPCHK(hipMemsetAsync(WT, 0, sizeof(double) * ld * ld, s));
+    } else if (ld > Np) {
+        HIPCHK(hipMemsetAsync(W + (int64_t)Np * ld, 0, sizeof(double) * (ld - Np) * ld, s));
+        HIPCHK(hipMemsetAsync(WT + (int64_t)Np * ld, 0, sizeof(double) * (ld - Np) * ld, s));
+    }
+    KgenArgs ka{};
+    ka.Xs = st->Xs.as<double>(); ka.Z = st->Xraw.as<double>(); ka.alpha = nullptr; ka.Kout = K; ka.mu = nullptr;
+    ka.ldk = ld; ka.M = g->npts; ka.j0 = 0; ka.Mc = Np; ka.N = (int)g->npts; ka.Np = Np; ka.d = g->d; ka.dp = g->dp;
+    ka.family = g->prm.family; ka.s = 1.0 / g->prm.ell; ka.sigma_f2 = g->prm.sigma_f2; ka.mean_c = 0.0;
+    ka.pt = g->p_out; ka.pc = g->p_out; ka.point_major = 1;      // K_XX: rows and columns point-major → symmetric
+    HIPCHK(launch_kgen(ka, s));
+    HIPCHK(launch_diag_fix(K, ld, N, (int)ld, noise, s, info));      // also resets the status word
+    if (ld > Np) {
+        HIPCHK(launch_set_diag(W, ld, Np, (int)ld, 1.0, s));
+        HIPCHK(launch_set_diag(WT, ld, Np, (int)ld, 1.0, s));
+    }
+    PHASE_EVENT(g->evs()[1], s);
+
+    // (the operand stream of the panel solve lives in T, which the factorisation does not use — the blocked inverse behind it does)
+    if (split) HIPCHK(g->T.ensure(TRSM_STREAM_BYTES));
+    { const int32_t rc = chol_blocked(K, W, WT, g->T.as<double>(), ld, Np, info, CholBlocking{}, s); if (rc) return rc; }
+    PHASE_EVENT(g->evs()[2], s);
+    // no host round trip here: after a failed pivot every later kernel of the fit either exits on `info` (the GEMMs) or
+    // works on finite leftovers whose results are discarded; `info` is read once, with the scalars, at the end
+
+    { const int32_t rc = trinv_blocked(K, W, WT, g->T.as<double>(), ld, Np, info, s); if (rc) return rc; }
     PHASE_EVENT(g->evs()[3], s);
     // alpha = Wᵀ(W·delta)
     HIPCHK(launch_trmv(W, ld, st->delta.as<double>(), g->tvec.as<double>(), Np, 1, s));

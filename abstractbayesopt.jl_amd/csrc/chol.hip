@@ -65,7 +65,8 @@ __device__ __forceinline__ double readlane_f64(double v, int l) {
 // lane, the pivot tests are compares on wave-uniform arguments accumulated on the scalar unit.
 // cb: 2 × 64 doubles of LDS per wave; dinv_out: 16 doubles of LDS that receive 1/L_jj (the wave that owns the block's dinv passes it,
 // the others a scratch row).  Returns the mask of columns whose pivot was not a positive normal number (bit j; wave-uniform; NaN
-// included; LAPACK's info is its lowest set bit).
+// included; LAPACK's info is its lowest set bit).  +Inf is the one exception: it passes the compare, its reciprocal square root is 0,
+// columns of its pair become NaN and the NEXT pair's first pivot fails — the failure is reported, at the start of the next pair.
 typedef __attribute__((address_space(3))) double lds_f64;
 __device__ __forceinline__ unsigned register_potf2_step_lds(double (&x)[16], int lane, lds_f64* cb, lds_f64* dinv_out) {
     constexpr int SBX = 16;
@@ -393,18 +394,37 @@ __global__ void __launch_bounds__(DT) chol_diag_kernel(double* K, double* W, dou
     PROBE(5);
     if constexpr (MODE == 3) {
         // α = L⁻ᵀ(L⁻¹δ) from the block in LDS: X = L⁻¹ has its diagonal in dinv and its strict lower part transposed in the
-        // strict upper triangle (a[k][i] = X[i][k], k < i).  One thread per row, sums in index order (deterministic).
-        if (t < NB) {
-            double acc = dinv[t] * dl[t];
-            for (int k = 0; k < t; ++k) acc = fma(AA(k, t), dl[k], acc);
-            tv[t] = acc;
+        // strict upper triangle (a[k][i] = X[i][k], k < i).  Both products in trmv_kernel's order of summation — a wave per row,
+        // lane l takes the pair k0 + 2l, k0 + 2l + 1 of the row group's k range (k0 = 0 … row0 + 3 below, row0 … 127 above the diagonal,
+        // row0 = 4·(row / 4); structural zeros where that kernel reads them from W / WT), then the xor tree — so that a model's α has
+        // the same bits whichever path fitted it (this launch, or kernel matrix + mode 0 + launch_trmv when it has spare capacity).
+        for (int r = wave; r < NB; r += DT / 64) {
+            const int k = 2 * lane;
+            double acc = 0.0;
+            if (k < (r & ~3) + 4) {
+                const double x0 = k < r ? AA(k, r) : (k == r ? dinv[r] : 0.0);
+                const double x1 = k + 1 < r ? AA(k + 1, r) : (k + 1 == r ? dinv[r] : 0.0);
+                acc = fma(x1, dl[k + 1], fma(x0, dl[k], 0.0));
+            }
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o);
+            if (lane == 0) tv[r] = acc;
         }
         __syncthreads();
-        if (t < NB) {
-            double acc = dinv[t] * tv[t];
-            for (int i = t + 1; i < NB; ++i) acc = fma(AA(t, i), tv[i], acc);
-            fs.alpha[t] = acc;
-            dl[t] = dl[t] * acc;                                     // δ_i α_i (zero on padding rows); dl[t] is this thread's own
+        for (int r = wave; r < NB; r += DT / 64) {
+            const int k = (r & ~3) + 2 * lane;
+            double acc = 0.0;
+            if (k < NB) {
+                const double x0 = k > r ? AA(r, k) : (k == r ? dinv[r] : 0.0);
+                const double x1 = k + 1 > r ? AA(r, k + 1) : (k + 1 == r ? dinv[r] : 0.0);
+                acc = fma(x1, tv[k + 1], fma(x0, tv[k], 0.0));
+            }
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o);
+            if (lane == 0) {
+                fs.alpha[r] = acc;
+                dl[r] = dl[r] * acc;                                 // δ_i α_i (zero on padding rows); no other wave reads dl here
+            }
         }
         __syncthreads();                                             // every tv[i] has been read
         if (t < NB) tv[t] = t < fs.N ? 2.0 * log(AA(t, t)) : 0.0;    // log-determinant terms

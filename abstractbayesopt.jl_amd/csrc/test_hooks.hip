@@ -455,4 +455,91 @@ int32_t abo_test_cand_newcol(int32_t device, const double* Xs, const double* Z, 
     return ABO_OK;
 }
 
+// ---- the factorisation family (csrc/chol.hip, and the blocked driver of api.hip), piece by piece: every hook passes its arguments to
+// ---- ONE launcher (the panel pair: two) on the null stream and decides nothing about shape or dispatch
+int32_t abo_test_chol_diag(int32_t device, double* K, double* W, double* WT, int64_t ld, int32_t r0, int64_t* info) {
+    if (!K || !W || !WT || !info) return fail(ABO_EINVAL, "abo_test_chol_diag: null argument");
+    if (r0 < 0 || ld < (int64_t)r0 + 128) return fail(ABO_EINVAL, "abo_test_chol_diag: r0 >= 0, ld >= r0 + 128");
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(launch_chol_diag(K, W, WT, ld, r0, info, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_chol_panel(int32_t device, double* K, double* W, double* WT, int64_t ld, int32_t r0, int32_t nrows, int32_t zero_rows,
+                            int64_t* info) {
+    if (!K || !W || !WT || !info) return fail(ABO_EINVAL, "abo_test_chol_panel: null argument");
+    if (r0 < 0 || r0 % 128 || nrows < 0 || nrows % 16 || ld <= 0 || ld % 128 || ld < (int64_t)r0 + 128)
+        return fail(ABO_EINVAL, "abo_test_chol_panel: r0 a multiple of 128, nrows of 16, ld of 128 and >= r0 + 128");
+    HIPCHK(hipSetDevice(device));
+    ScratchBuf ops(device, nullptr);
+    HIPCHK(ops.b.ensure(TRSM_STREAM_BYTES));
+    HIPCHK(launch_potf2_diag(K, W, WT, ld, r0, info, nullptr, ops.b.as<double>(), zero_rows != 0));
+    if (nrows > 0) HIPCHK(launch_trsm_stream(K, ops.b.as<double>(), ld, r0, nrows, info, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_trtri_batched(int32_t device, double* K, double* W, double* WT, int64_t ld, int32_t nblocks, int64_t* info) {
+    if (!K || !W || !WT || !info) return fail(ABO_EINVAL, "abo_test_trtri_batched: null argument");
+    if (nblocks < 1 || ld < 128 * (int64_t)nblocks) return fail(ABO_EINVAL, "abo_test_trtri_batched: nblocks >= 1, ld >= 128 * nblocks");
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(launch_trtri_diag_batched(K, W, WT, ld, nblocks, info, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_chol_blocked(int32_t device, double* K, double* W, double* WT, int64_t ld, int32_t Np, int32_t sw, int32_t ss,
+                              int32_t super_rows, int64_t* info) {
+    if (!K || !W || !WT || !info) return fail(ABO_EINVAL, "abo_test_chol_blocked: null argument");
+    if (Np <= 0 || Np % 128 || ld % 128 || ld < Np || sw <= 0 || sw % 128 || ss <= 0 || ss % 128 || ss % sw || super_rows < 0)
+        return fail(ABO_EINVAL, "abo_test_chol_blocked: Np, ld, sw, ss positive multiples of 128, ld >= Np, ss a multiple of sw, super_rows >= 0");
+    HIPCHK(hipSetDevice(device));
+    ScratchBuf t(device, nullptr);
+    const size_t tb = sizeof(double) * (size_t)Np * (size_t)Np;          // as abo_fit sizes the handle's T
+    HIPCHK(t.b.ensure(tb > TRSM_STREAM_BYTES ? tb : TRSM_STREAM_BYTES));
+    CholBlocking blk;
+    blk.SW = sw; blk.SSmax = ss; blk.super_rows = super_rows;
+    int32_t rc = chol_blocked(K, W, WT, t.b.as<double>(), ld, Np, info, blk, nullptr);
+    if (rc) return rc;
+    rc = trinv_blocked(K, W, WT, t.b.as<double>(), ld, Np, info, nullptr);
+    if (rc) return rc;
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_trmv(int32_t device, const double* Wm, int64_t ld, const double* v, double* out, int32_t Np, int32_t lower) {
+    if (!Wm || !v || !out) return fail(ABO_EINVAL, "abo_test_trmv: null argument");
+    if (Np < 1 || (ld & 1) || ld < (int64_t)Np + (Np & 1) || (lower != 0 && lower != 1))
+        return fail(ABO_EINVAL, "abo_test_trmv: Np >= 1, ld even and >= Np rounded up to even (the rows are read in pairs), lower 0 or 1");
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(launch_trmv(Wm, ld, v, out, Np, lower, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_nlml_terms(int32_t device, const double* L, int64_t ld, const double* delta, const double* alpha, int32_t N, double* out) {
+    if (!L || !delta || !alpha || !out) return fail(ABO_EINVAL, "abo_test_nlml_terms: null argument");
+    if (N < 1 || ld < N) return fail(ABO_EINVAL, "abo_test_nlml_terms: N >= 1, ld >= N");
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(launch_nlml_terms(L, ld, delta, alpha, N, out, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_append(int32_t device, const abo_test_append_args* t) {
+    if (!t || !t->L || !t->W || !t->WT || !t->krow || !t->lvec || !t->vvec || !t->alpha_old || !t->alpha_new || !t->vext || !t->delta ||
+        !t->scal || !t->info)
+        return fail(ABO_EINVAL, "abo_test_append: null argument");
+    if (t->N < 0 || t->cap <= t->N || t->ld <= t->N) return fail(ABO_EINVAL, "abo_test_append: N >= 0, cap > N, ld > N");
+    AppendArgs a{};
+    a.L = t->L; a.W = t->W; a.WT = t->WT; a.ld = t->ld; a.krow = t->krow; a.lvec = t->lvec; a.vvec = t->vvec;
+    a.alpha_old = t->alpha_old; a.alpha_new = t->alpha_new; a.vext = t->vext; a.delta = t->delta; a.N = t->N; a.cap = t->cap;
+    a.kss = t->kss; a.scal = t->scal; a.info = t->info;
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(launch_append(a, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
 }  // extern "C"

@@ -993,6 +993,43 @@ int32_t abo_test_kgen(int32_t device, const abo_test_kgen_args* args);
  * (point pt, output q) against the function value of every candidate, written to column `col`) */
 int32_t abo_test_cand_newcol(int32_t device, const double* Xs, const double* Z, double* Kzx, int64_t ld, int64_t M, int32_t col, int32_t grad,
                              int32_t pt, int32_t q, int32_t d, int32_t dp, int32_t family, double s, double sigma_f2);
+/* --- the factorisation family (csrc/chol.hip and the blocked driver of csrc/api.hip), piece by piece ---
+ * Every pointer is DEVICE memory; info is a device int64 the caller presets (0: run; anything else: every kernel leaves its outputs
+ * alone, but for the zeroing workgroups of the panel's diagonal-block launch).  Each hook hands its arguments to the launcher(s) named,
+ * on the null stream, and waits; ABO_EINVAL, and no launch, for arguments the launcher cannot take.
+ * launch_chol_diag (mode 0): the 128×128 block at (r0, r0) of K [..][ld] → L in place (zeros above the diagonal), its inverse to the
+ * same block of W (lower) and WT (upper, the transpose); a pivot that is no positive normal number: *info = r0 + j + 1, nothing written. */
+int32_t abo_test_chol_diag(int32_t device, double* K, double* W, double* WT, int64_t ld, int32_t r0, int64_t* info);
+/* launch_potf2_diag into a scratch operand stream, then (nrows > 0) launch_trsm_stream from it: the block at (r0, r0) → L, the eight
+ * 16×16 diagonal sub-blocks of its inverse to W / WT, rows r0+128 … r0+128+nrows of columns r0 … r0+127 → A·L⁻ᵀ in place; zero_rows:
+ * rows r0 … r0+127 of W and WT are zeroed over all ld columns outside the diagonal block.  r0, ld multiples of 128, nrows of 16. */
+int32_t abo_test_chol_panel(int32_t device, double* K, double* W, double* WT, int64_t ld, int32_t r0, int32_t nrows, int32_t zero_rows,
+                            int64_t* info);
+/* launch_trtri_diag_batched (mode 2): the inverses of the first nblocks 128×128 diagonal blocks of a finished L, to W and WT */
+int32_t abo_test_trtri_batched(int32_t device, double* K, double* W, double* WT, int64_t ld, int32_t nblocks, int64_t* info);
+/* chol_blocked then trinv_blocked (what a fit runs on its kernel matrix) on the caller's K [Np][ld] with strips of sw columns,
+ * super-strips of ss while at least super_rows rows remain (the library's own: 512, 1024, 6144): L → K, L⁻¹ → W, L⁻ᵀ → WT.
+ * Np, ld, sw, ss multiples of 128, ss of sw.  With Np > 128 rows < Np of W / WT are zeroed by the chain; with Np = 128 only the block is
+ * written. */
+int32_t abo_test_chol_blocked(int32_t device, double* K, double* W, double* WT, int64_t ld, int32_t Np, int32_t sw, int32_t ss,
+                              int32_t super_rows, int64_t* info);
+/* launch_trmv: out[r] = Σ_k Wm[r][k]·v[k] over the triangle (lower = 1: k ≤ r, 0: r ≤ k < Np), r < Np; ld even */
+int32_t abo_test_trmv(int32_t device, const double* Wm, int64_t ld, const double* v, double* out, int32_t Np, int32_t lower);
+/* launch_nlml_terms: out[0] = 2·Σ_{i<N} log L[i][i], out[1] = Σ_{i<N} delta[i]·alpha[i] */
+int32_t abo_test_nlml_terms(int32_t device, const double* L, int64_t ld, const double* delta, const double* alpha, int32_t N, double* out);
+/* launch_append with every field of its argument block (csrc/abo_kernels.h: AppendArgs) */
+typedef struct abo_test_append_args {
+    double* L; double* W; double* WT;
+    int64_t ld;
+    const double* krow; const double* lvec; const double* vvec;
+    const double* alpha_old; double* alpha_new; double* vext;
+    const double* delta;
+    int32_t N, cap;
+    double kss;
+    double* scal;
+    int64_t* info;
+} abo_test_append_args;
+int32_t abo_test_append(int32_t device, const abo_test_append_args* args);
 #endif /* ABO_TEST_HOOKS */
 
 #ifdef __cplusplus
