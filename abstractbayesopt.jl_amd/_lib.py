@@ -33,7 +33,14 @@ TEST_EXPORTS = ["abo_test_gemm_nt", "abo_test_kappa", "abo_test_oz_plan", "abo_t
                 "abo_test_gemm_args", "abo_test_gemm_path", "abo_test_gemm_swz_q", "abo_test_gemm_swz_map", "abo_test_qei_pass", "abo_test_splitk_reduce",
                 "abo_test_var_gemm", "abo_test_kgen", "abo_test_cand_newcol",
                 "abo_test_chol_diag", "abo_test_chol_panel", "abo_test_trtri_batched", "abo_test_chol_blocked", "abo_test_trmv",
-                "abo_test_nlml_terms", "abo_test_append"]
+                "abo_test_nlml_terms", "abo_test_append",
+                "abo_test_topk_plan", "abo_test_topk", "abo_test_prune_compact", "abo_test_prune_min_scatter", "abo_test_prune_map",
+                "abo_test_finalize", "abo_test_cand_gemv", "abo_test_downdate", "abo_test_grad_cov", "abo_test_gather_points",
+                "abo_test_pick_record", "abo_test_score"]
+# what launch_topk runs, as abo_test_topk_plan reports it (include/abo_hip.h: ABO_TOPK_PATH_*)
+TOPK_PATH_NONE, TOPK_PATH_SMALL, TOPK_PATH_SLICES, TOPK_PATH_ARGMAX, TOPK_PATH_BLOCKSORT = -1, 0, 1, 2, 3
+# margins of the pruned selection's guard (csrc/abo_kernels.h)
+PRUNE_REL, PRUNE_ABS, PRUNE_ABS_LOGEI = 2.0 ** -30, 2.0 ** -1022, 2.0 ** -30
 # what launch_gemm_nt ran, as abo_test_gemm_args / abo_test_gemm_path report it (include/abo_hip.h: ABO_GEMM_PATH_*)
 GEMM_PATH_TILED, GEMM_PATH_SWIZZLED, GEMM_PATH_SMALL, GEMM_PATH_SKINNY, GEMM_PATH_SPLITK = range(5)
 K_FULL, K_A_LOWER, K_A_UPPER, K_B_LOWER, K_B_UPPER = range(5)
@@ -130,6 +137,13 @@ class AboTestAppendArgs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("L", "W", "WT")] + [("ld", C.c_int64)] + \
                [(n, C.c_void_p) for n in ("krow", "lvec", "vvec", "alpha_old", "alpha_new", "vext", "delta")] + \
                [("N", C.c_int32), ("cap", C.c_int32), ("kss", C.c_double), ("scal", C.c_void_p), ("info", C.c_void_p)]
+
+
+class AboTestFinalizeArgs(C.Structure):
+    """every field of the epilogue's argument block, for abo_test_finalize (include/abo_hip.h: abo_test_finalize_args; test build only)"""
+    _fields_ = [(n, C.c_void_p) for n in ("partial", "mu_in", "mu_out", "var_out", "score_out", "mu_tail", "mu_eps", "head_g", "ssq_g")] + \
+               [(n, C.c_int64) for n in ("ldp", "j0", "M", "Mpts")] + [(n, C.c_double) for n in ("sigma_f2", "p0", "best_y", "prior_grad")] + \
+               [(n, C.c_int32) for n in ("T", "Mc", "kind", "pc", "point_major", "reserved")]
 
 
 class PosDefException(Exception):
@@ -253,6 +267,18 @@ def lib():
         L.abo_test_trmv.argtypes = [i32, vp, i64, vp, vp, i32, i32]
         L.abo_test_nlml_terms.argtypes = [i32, vp, i64, vp, vp, i32, vp]
         L.abo_test_append.argtypes = [i32, C.POINTER(AboTestAppendArgs)]
+        L.abo_test_topk_plan.argtypes = [i64, i32, vp]
+        L.abo_test_topk.argtypes = [i32, vp, i64, i32, i64, vp, vp, C.POINTER(i32)]
+        L.abo_test_prune_compact.argtypes = [i32, vp, i64, vp, f64, vp, vp]
+        L.abo_test_prune_min_scatter.argtypes = [i32, vp, vp, vp, i64]
+        L.abo_test_prune_map.argtypes = [i32, vp, i32, vp, i64]
+        L.abo_test_finalize.argtypes = [i32, C.POINTER(AboTestFinalizeArgs)]
+        L.abo_test_cand_gemv.argtypes = [i32, vp, i64, vp, i32, i64, vp]
+        L.abo_test_downdate.argtypes = [i32, vp, vp, vp, i64, f64, f64]
+        L.abo_test_grad_cov.argtypes = [i32, vp, vp, i64, i32, i32, i64, f64, f64, f64, vp, vp, vp, i32]
+        L.abo_test_gather_points.argtypes = [i32, vp, vp, i64, i32, i32, vp]
+        L.abo_test_pick_record.argtypes = [i32, vp, vp, i64, vp, vp, i32, vp]
+        L.abo_test_score.argtypes = [i32, vp, vp, vp, i64, i32, f64, f64]
     L.abo_mgpu_create.argtypes = [C.POINTER(AboParams), i32, C.POINTER(i32), C.POINTER(vp)]
     L.abo_mgpu_create_grad.argtypes = [C.POINTER(AboParams), i32, vp, i32, C.POINTER(i32), C.POINTER(vp)]
     L.abo_mgpu_append_grad.argtypes = [vp, vp, i32, vp, C.POINTER(i64), vp]

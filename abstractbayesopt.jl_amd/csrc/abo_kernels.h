@@ -646,6 +646,24 @@ struct TopkWork {            // scratch sized by topk_workspace_entries()
     int64_t* idx[2];
 };
 int64_t topk_workspace_entries(int64_t M, int k);
+// Which kernels launch_topk gives a selection of k out of M (== ABO_TOPK_PATH_* of include/abo_hip.h): the one place the choice is
+// made — pure host code, no GPU call (misc.hip documents the rule)
+enum TopkPath {
+    TOPK_PATH_NONE = -1,       // k ≤ 0: nothing to do
+    TOPK_PATH_SMALL = 0,       // topk_small_kernel<0>: the whole batch in one workgroup's radix select
+    TOPK_PATH_SLICES = 1,      // topk_small_kernel<1> per slice, then one merge by topk_small_kernel<2>
+    TOPK_PATH_ARGMAX = 2,      // argmax_partial_kernel + argmax_final_kernel (k = 1)
+    TOPK_PATH_BLOCKSORT = 3    // the block-sort chain, in threshold rounds of 1024 for k > 1024
+};
+struct TopkPlan {
+    int path;
+    int kreal;                 // entries that come from scores: min(k, max(M, 1)); the rest of the k requested is (NaN, −1)
+    int slice;                 // SLICES: scores per workgroup of the first launch
+    int64_t pairs;             // SLICES: (key, index) pairs the merge reads
+    int rounds;                // BLOCKSORT: ⌈kreal/1024⌉ threshold rounds
+    int passes;                // BLOCKSORT: launches of topk_pass_kernel in the first round
+};
+TopkPlan topk_plan(int64_t M, int k);
 // top-k of scores[0..M) in Julia's `sortperm(scores; rev=true)` order; writes k (val, idx) pairs
 // (idx + idx_base; tail (NaN, −1) when M < k) to device arrays top_val/top_idx.
 hipError_t launch_topk(const double* scores, int64_t M, int k, int64_t idx_base, TopkWork w,

@@ -625,44 +625,75 @@ int64_t topk_workspace_entries(int64_t M, int k) {
     return (blocks < 1 ? 1 : blocks) * (int64_t)kp + 2;   // + {key, idx} of the last entry taken (k > 1024 rounds)
 }
 
-// k ≤ 1024: one round (block-wise bitonic sort, keep the first kp per block, repeat until one block is left).
-// k > 1024 (n_local is a free Int in the reference, acq_utils.jl:33-52): rounds of 1024 — each round selects, among the
-// entries strictly after the last one taken so far, the next 1024 in order; ⌈k/1024⌉ passes over the scores, no host
-// round trip (the threshold stays on the device).
+// The one place the route of a selection is chosen (launch_topk switches on it; abo_test_topk_plan hands it to the tests):
+//   SMALL      k ≤ 1024 and M ≤ TKS_SPLIT_M: topk_small_kernel<0>, one workgroup, one launch (an empty batch, M ≤ 0, included: the
+//              radix select finds nothing and every entry comes out as (NaN, −1))
+//   SLICES     1 < k ≤ 1024 above that: topk_small_kernel<1> per slice + one merge <2> — two launches while the slices' picks fit one
+//              workgroup.  One workgroup's selection costs ≈ 3.5 µs per 1024 entries: the slices are as short as keeps the merge at
+//              ≤ 8192 pairs (M = 65 536, k = 100: 32 slices of 2048, 3200 pairs); a merge of more than TKS_MAXM pairs falls through
+//   ARGMAX     k = 1 above TKS_MAXM: one workspace entry per block of TK_E scores — topk_workspace_entries(M, 1) holds them
+//   BLOCKSORT  everything else.  k ≤ 1024: one round (block-wise bitonic sort, keep the first kp per block, repeat until one block is
+//              left).  k > 1024 (n_local is a free Int in the reference, acq_utils.jl:33-52): rounds of 1024 — each round selects,
+//              among the entries strictly after the last one taken so far, the next 1024 in order; ⌈k/1024⌉ passes over the scores,
+//              no host round trip (the threshold stays on the device).
+TopkPlan topk_plan(int64_t M, int k) {
+    TopkPlan p{TOPK_PATH_NONE, 0, 0, 0, 0, 0};
+    if (k <= 0) return p;
+    // sortperm(...)[1:min(n_local, M)] (acq_utils.jl:52): at most M real entries; the tail of a longer request is (NaN, −1)
+    k = p.kreal = (int64_t)k < M ? k : (int)(M < 1 ? 1 : M);
+    if (k <= 1024 && (M <= TKS_SPLIT_M || (M <= TKS_MAXM && (k == 1 || 4 * (int64_t)k > M)))) {
+        p.path = TOPK_PATH_SMALL;
+        return p;
+    }
+    if (k > 1 && k <= 1024 && M > TKS_SPLIT_M) {
+        int slice = 2048;
+        auto pairs = [&](int sl) { const int64_t G = (M + sl - 1) / sl, last = M - (G - 1) * sl; return (G - 1) * k + (last < k ? last : k); };
+        while (slice < TKS_MAXM && (pairs(slice) > 8192 || slice < 2 * k)) slice *= 2;
+        const int64_t n = pairs(slice);
+        if (n <= TKS_MAXM && slice >= k) {
+            p.path = TOPK_PATH_SLICES; p.slice = slice; p.pairs = n;
+            return p;
+        }
+    }
+    if (k == 1 && M > TKS_MAXM) {
+        p.path = TOPK_PATH_ARGMAX;
+        return p;
+    }
+    p.path = TOPK_PATH_BLOCKSORT;
+    p.rounds = (k + TK_KMAX - 1) / TK_KMAX;
+    const int kp = pow2_at_least(k < TK_KMAX ? k : TK_KMAX);
+    int64_t blocks = (M + TK_E - 1) / TK_E;
+    p.passes = 1;
+    while (blocks > 1) { blocks = (blocks * kp + TK_E - 1) / TK_E; ++p.passes; }
+    return p;
+}
+
 hipError_t launch_topk(const double* scores, int64_t M, int k, int64_t idx_base, TopkWork w, double* top_val,
                        int64_t* top_idx, hipStream_t s) {
-    if (k <= 0) return hipSuccess;
+    const TopkPlan plan = topk_plan(M, k);
+    if (plan.path == TOPK_PATH_NONE) return hipSuccess;
     uint64_t* thr = w.keys[0] + (topk_workspace_entries(M, k) - 2);
-    // sortperm(...)[1:min(n_local, M)] (acq_utils.jl:52): at most M real entries; the tail of a longer request is (NaN, −1)
-    const int kreal = (int64_t)k < M ? k : (int)(M < 1 ? 1 : M);
-    if (kreal < k) hipLaunchKernelGGL(topk_fill_kernel, dim3((k - kreal + 255) / 256), dim3(256), 0, s, top_val, top_idx, kreal, k);
-    k = kreal;
-    if (M >= 1 && k <= 1024 && (M <= TKS_SPLIT_M || (M <= TKS_MAXM && (k == 1 || 4 * (int64_t)k > M)))) {
+    if (plan.kreal < k) hipLaunchKernelGGL(topk_fill_kernel, dim3((k - plan.kreal + 255) / 256), dim3(256), 0, s, top_val, top_idx, plan.kreal, k);
+    k = plan.kreal;
+    if (plan.path == TOPK_PATH_SMALL) {
         int kp = pow2_at_least(k);
         if (kp < 2) kp = 2;
         hipLaunchKernelGGL(topk_small_kernel<0>, dim3(1), dim3(TKS_T), 0, s, scores, M, k, kp, idx_base, top_val, top_idx, nullptr, nullptr,
                            nullptr, nullptr, TKS_MAXM);
         return hipGetLastError();
     }
-    if (k > 1 && k <= 1024 && M > TKS_SPLIT_M) {
-        // slices, then one merge — two launches while the slices' picks fit one workgroup.  One workgroup's selection costs ≈ 3.5 µs per
-        // 1024 entries: the slices are as short as keeps the merge at ≤ 8192 pairs (M = 65 536, k = 100: 32 slices of 2048, 3200 pairs)
-        int slice = 2048;
-        auto pairs = [&](int sl) { const int64_t G = (M + sl - 1) / sl, last = M - (G - 1) * sl; return (G - 1) * k + (last < k ? last : k); };
-        while (slice < TKS_MAXM && (pairs(slice) > 8192 || slice < 2 * k)) slice *= 2;
-        const int64_t n = pairs(slice);
-        if (n <= TKS_MAXM && slice >= k) {
-            const int64_t G = (M + slice - 1) / slice;
-            int kp = pow2_at_least(k);
-            if (kp < 2) kp = 2;
-            hipLaunchKernelGGL(topk_small_kernel<1>, dim3((unsigned)G), dim3(TKS_T), 0, s, scores, M, k, kp, idx_base, nullptr, nullptr, nullptr,
-                               nullptr, w.keys[0], w.idx[0], slice);
-            hipLaunchKernelGGL(topk_small_kernel<2>, dim3(1), dim3(TKS_T), 0, s, scores, n, k, kp, idx_base, top_val, top_idx, w.keys[0],
-                               w.idx[0], nullptr, nullptr, TKS_MAXM);
-            return hipGetLastError();
-        }
+    if (plan.path == TOPK_PATH_SLICES) {
+        const int slice = plan.slice;
+        const int64_t n = plan.pairs, G = (M + slice - 1) / slice;
+        int kp = pow2_at_least(k);
+        if (kp < 2) kp = 2;
+        hipLaunchKernelGGL(topk_small_kernel<1>, dim3((unsigned)G), dim3(TKS_T), 0, s, scores, M, k, kp, idx_base, nullptr, nullptr, nullptr,
+                           nullptr, w.keys[0], w.idx[0], slice);
+        hipLaunchKernelGGL(topk_small_kernel<2>, dim3(1), dim3(TKS_T), 0, s, scores, n, k, kp, idx_base, top_val, top_idx, w.keys[0],
+                           w.idx[0], nullptr, nullptr, TKS_MAXM);
+        return hipGetLastError();
     }
-    if (k == 1 && M > TKS_MAXM) {       // one workspace entry per block of TK_E scores: topk_workspace_entries(M, 1) holds them
+    if (plan.path == TOPK_PATH_ARGMAX) {
         const int64_t nb = (M + TK_E - 1) / TK_E;
         hipLaunchKernelGGL(argmax_partial_kernel, dim3((unsigned)nb), dim3(AM_T), 0, s, scores, M, w.keys[0], w.idx[0]);
         hipLaunchKernelGGL(argmax_final_kernel, dim3(1), dim3(AM_T), 0, s, scores, w.keys[0], w.idx[0], (int)nb, M, idx_base, top_val,

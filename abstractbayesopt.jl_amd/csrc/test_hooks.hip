@@ -542,4 +542,153 @@ int32_t abo_test_append(int32_t device, const abo_test_append_args* t) {
     return ABO_OK;
 }
 
+// ---- the selection family (csrc/misc.hip): the same rule — every hook passes its arguments to ONE launcher on the null stream and
+// ---- decides nothing about route or shape
+int32_t abo_test_topk_plan(int64_t M, int32_t k, int64_t* out) {
+    if (!out) return fail(ABO_EINVAL, "abo_test_topk_plan: null argument");
+    const TopkPlan p = topk_plan(M, k);
+    out[0] = p.path; out[1] = p.kreal; out[2] = p.slice; out[3] = p.pairs; out[4] = p.rounds; out[5] = p.passes;
+    return ABO_OK;
+}
+
+int32_t abo_test_topk(int32_t device, const double* scores, int64_t M, int32_t k, int64_t idx_base, double* top_val, int64_t* top_idx,
+                      int32_t* guards_ok) {
+    if (!scores || !top_val || !top_idx || !guards_ok) return fail(ABO_EINVAL, "abo_test_topk: null argument");
+    if (M < 0 || k < 0 || idx_base < 0) return fail(ABO_EINVAL, "abo_test_topk: M >= 0, k >= 0, idx_base >= 0");
+    HIPCHK(hipSetDevice(device));
+    // four buffers of exactly the entries the callers allocate, each followed by GUARD sentinel entries (every byte 0x5a; the
+    // workspace itself starts as the same bytes: nothing of it may be read before it is written)
+    constexpr int64_t GUARD = 1024;
+    constexpr uint64_t SENTINEL = 0x5a5a5a5a5a5a5a5aull;
+    const int64_t n = topk_workspace_entries(M, k), stride = n + GUARD;
+    ScratchBuf ws(device, nullptr);
+    HIPCHK(ws.b.ensure(sizeof(uint64_t) * 4 * stride));
+    HIPCHK(hipMemsetAsync(ws.b.p, 0x5a, sizeof(uint64_t) * 4 * stride, nullptr));
+    uint64_t* base = ws.b.as<uint64_t>();
+    TopkWork w;
+    w.keys[0] = base; w.keys[1] = base + stride;
+    w.idx[0] = reinterpret_cast<int64_t*>(base + 2 * stride); w.idx[1] = reinterpret_cast<int64_t*>(base + 3 * stride);
+    HIPCHK(launch_topk(scores, M, k, idx_base, w, top_val, top_idx, nullptr));
+    std::vector<uint64_t> guards(4 * GUARD);
+    for (int b = 0; b < 4; ++b)
+        HIPCHK(hipMemcpyAsync(guards.data() + b * GUARD, base + b * stride + n, sizeof(uint64_t) * GUARD, hipMemcpyDeviceToHost, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    int32_t ok = 1;
+    for (uint64_t g : guards) if (g != SENTINEL) ok = 0;
+    *guards_ok = ok;
+    return ABO_OK;
+}
+
+int32_t abo_test_prune_compact(int32_t device, const double* ub, int64_t M, const double* tau, double abs_margin, int64_t* sel, int64_t* count) {
+    if (!ub || !tau || !sel || !count) return fail(ABO_EINVAL, "abo_test_prune_compact: null argument");
+    HIPCHK(hipSetDevice(device));
+    // one int of scan scratch per workgroup of the compaction; a count the launcher refuses gets one (it launches nothing)
+    const bool fits = M > 0 && M < ((int64_t)1 << 31);
+    ScratchBuf blk(device, nullptr);
+    HIPCHK(blk.b.ensure(sizeof(int) * (size_t)(fits ? (M + PRUNE_SCAN_E - 1) / PRUNE_SCAN_E : 1)));
+    const hipError_t e = launch_prune_compact(ub, M, tau, abs_margin, blk.b.as<int>(), sel, count, nullptr);
+    if (e == hipErrorInvalidValue) return fail(ABO_EINVAL, "abo_test_prune_compact: launch_prune_compact refused M = %lld (1 <= M < 2^31)", (long long)M);
+    HIPCHK(e);
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_prune_min_scatter(int32_t device, double* ub, const int64_t* sel, const double* ub2, int64_t n) {
+    if (!ub || !sel || !ub2) return fail(ABO_EINVAL, "abo_test_prune_min_scatter: null argument");
+    if (n < 0) return fail(ABO_EINVAL, "abo_test_prune_min_scatter: n >= 0");
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(launch_prune_min_scatter(ub, sel, ub2, n, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_prune_map(int32_t device, int64_t* top_idx, int32_t k, const int64_t* sel, int64_t idx_base) {
+    if (!top_idx || !sel) return fail(ABO_EINVAL, "abo_test_prune_map: null argument");
+    if (k < 0) return fail(ABO_EINVAL, "abo_test_prune_map: k >= 0");
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(launch_prune_map(top_idx, k, sel, idx_base, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_finalize(int32_t device, const abo_test_finalize_args* t) {
+    if (!t) return fail(ABO_EINVAL, "abo_test_finalize: null argument");
+    if ((t->T > 0 && !t->partial) || (!t->head_g && !t->mu_in) || (t->mu_tail && !t->mu_eps))
+        return fail(ABO_EINVAL, "abo_test_finalize: null argument (partial with T > 0, mu_in without head_g, mu_eps with mu_tail)");
+    if (t->T < 0 || t->Mc < 0 || t->j0 < 0 || t->M < 0 || t->ldp < t->Mc || t->pc < 1 || (t->pc > 1 && !t->point_major && t->Mpts <= 0))
+        return fail(ABO_EINVAL, "abo_test_finalize: T, Mc, j0, M >= 0, ldp >= Mc, pc >= 1, Mpts > 0 for rows by outputs");
+    FinalizeArgs a{};
+    a.partial = t->partial; a.mu_in = t->mu_in; a.mu_out = t->mu_out; a.var_out = t->var_out; a.score_out = t->score_out;
+    a.ldp = t->ldp; a.j0 = t->j0; a.M = t->M; a.T = t->T; a.Mc = t->Mc; a.kind = t->kind;
+    a.sigma_f2 = t->sigma_f2; a.p0 = t->p0; a.best_y = t->best_y; a.prior_grad = t->prior_grad;
+    a.pc = t->pc; a.point_major = t->point_major; a.Mpts = t->Mpts;
+    a.mu_tail = t->mu_tail; a.mu_eps = t->mu_eps; a.head_g = t->head_g; a.ssq_g = t->ssq_g;
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(launch_finalize(a, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_cand_gemv(int32_t device, const double* Kzx, int64_t ld, const double* v, int32_t n, int64_t M, double* c) {
+    if (!Kzx || !v || !c) return fail(ABO_EINVAL, "abo_test_cand_gemv: null argument");
+    if (n < 0 || M < 0 || (ld & 1) || ld < (int64_t)n + 1 || ((uintptr_t)Kzx & 15) || ((uintptr_t)v & 15))
+        return fail(ABO_EINVAL, "abo_test_cand_gemv: n, M >= 0, ld even and >= n + 1, Kzx and v 16-byte aligned (the rows are read in pairs)");
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(launch_cand_gemv(Kzx, ld, v, n, M, c, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_downdate(int32_t device, double* mu, double* var, const double* c, int64_t M, double beta, double s2) {
+    if (!mu || !var || !c) return fail(ABO_EINVAL, "abo_test_downdate: null argument");
+    if (M < 0) return fail(ABO_EINVAL, "abo_test_downdate: M >= 0");
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(launch_downdate(mu, var, c, M, beta, s2, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_grad_cov(int32_t device, const double* V, const double* mu_rows, int64_t ldv, int32_t R, int32_t p, int64_t pt0,
+                          double prior0, double prior_g, double beta, double* cov_out, double* mu_out, double* score_out, int32_t npoints) {
+    if (!V || !mu_rows) return fail(ABO_EINVAL, "abo_test_grad_cov: null argument");
+    if (p < 1 || R < 0 || ldv < R || pt0 < 0 || npoints < 0) return fail(ABO_EINVAL, "abo_test_grad_cov: p >= 1, R >= 0, ldv >= R, pt0 >= 0, npoints >= 0");
+    GradCovArgs a{};
+    a.V = V; a.mu_rows = mu_rows; a.ldv = ldv; a.R = R; a.p = p; a.pt0 = pt0; a.prior0 = prior0; a.prior_g = prior_g; a.beta = beta;
+    a.cov_out = cov_out; a.mu_out = mu_out; a.score_out = score_out;
+    HIPCHK(hipSetDevice(device));
+    const hipError_t e = launch_grad_cov(a, npoints, nullptr);
+    if (e == hipErrorInvalidValue) return fail(ABO_EINVAL, "abo_test_grad_cov: launch_grad_cov refused p = %d (C and m do not fit a workgroup's LDS)", p);
+    HIPCHK(e);
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_gather_points(int32_t device, const double* Z, const int64_t* idx, int64_t idx_base, int32_t k, int32_t d, double* out) {
+    if (!Z || !idx || !out) return fail(ABO_EINVAL, "abo_test_gather_points: null argument");
+    if (k < 0 || d < 1) return fail(ABO_EINVAL, "abo_test_gather_points: k >= 0, d >= 1");
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(launch_gather_points(Z, idx, idx_base, k, d, out, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_pick_record(int32_t device, const double* tv, const int64_t* ti, int64_t idx_base, const double* Z, const double* mu,
+                             int32_t d, double* rec) {
+    if (!tv || !ti || !Z || !mu || !rec) return fail(ABO_EINVAL, "abo_test_pick_record: null argument");
+    if (d < 1) return fail(ABO_EINVAL, "abo_test_pick_record: d >= 1");
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(launch_pick_record(tv, ti, idx_base, Z, mu, d, rec, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_score(int32_t device, const double* mu, const double* var, double* score, int64_t M, int32_t kind, double p0, double best_y) {
+    if (!mu || !var || !score) return fail(ABO_EINVAL, "abo_test_score: null argument");
+    if (M < 0 || !plain_kind(kind)) return fail(ABO_EINVAL, "abo_test_score: M >= 0 and a plain acquisition kind (got %d)", kind);
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(launch_score(mu, var, score, M, kind, p0, best_y, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
 }  // extern "C"

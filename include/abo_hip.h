@@ -1030,6 +1030,58 @@ typedef struct abo_test_append_args {
     int64_t* info;
 } abo_test_append_args;
 int32_t abo_test_append(int32_t device, const abo_test_append_args* args);
+/* --- the selection family (csrc/misc.hip): epilogue, top-k on every route, survivor bookkeeping, streaming pieces ---
+ * Every pointer is DEVICE memory unless stated otherwise.  Each hook hands its arguments to ONE launcher on the null stream and waits;
+ * ABO_EINVAL, and no launch, for null pointers and for shapes the launcher cannot take.
+ * Route ids: what launch_topk runs for k out of M. */
+#define ABO_TOPK_PATH_NONE (-1)    /* k <= 0: nothing */
+#define ABO_TOPK_PATH_SMALL 0      /* one workgroup's radix select (k <= 1024, M <= 16384) */
+#define ABO_TOPK_PATH_SLICES 1     /* radix select per slice, then one merge (1 < k <= 1024) */
+#define ABO_TOPK_PATH_ARGMAX 2     /* two plain reductions (k = 1, M > 16384) */
+#define ABO_TOPK_PATH_BLOCKSORT 3  /* the block-sort chain; threshold rounds of 1024 for k > 1024 */
+/* The launcher's choice alone (no GPU needed; out is HOST memory): out[6] = {route, kreal = min(k, max(M, 1)), SLICES: slice length and
+ * pairs the merge reads, BLOCKSORT: threshold rounds and launches of the first round's sort}; zeros where a field does not apply */
+int32_t abo_test_topk_plan(int64_t M, int32_t k, int64_t* out);
+/* launch_topk of scores[0..M) → top_val / top_idx [k].  The hook owns the workspace: each of its four buffers has exactly
+ * topk_workspace_entries(M, k) entries — what every caller in the library allocates — and a sentinel region behind them;
+ * *guards_ok (HOST) = 1 when every sentinel of the four regions survived the call, 0 otherwise. */
+int32_t abo_test_topk(int32_t device, const double* scores, int64_t M, int32_t k, int64_t idx_base, double* top_val, int64_t* top_idx,
+                      int32_t* guards_ok);
+/* launch_prune_compact: sel[0 .. *count) = the j < M, ascending, with !(ub[j] + |ub[j]|·2⁻³⁰ + abs_margin < *tau); the scan's scratch
+ * is the hook's.  ABO_EINVAL, before any launch, where the launcher refuses (M <= 0, M >= 2^31). */
+int32_t abo_test_prune_compact(int32_t device, const double* ub, int64_t M, const double* tau, double abs_margin, int64_t* sel, int64_t* count);
+/* launch_prune_min_scatter: ub[sel[i]] = min(ub[sel[i]], ub2[i]), i < n, NaN on either side giving NaN */
+int32_t abo_test_prune_min_scatter(int32_t device, double* ub, const int64_t* sel, const double* ub2, int64_t n);
+/* launch_prune_map: top_idx[e] = sel[top_idx[e]] + idx_base for e < k, −1 stays */
+int32_t abo_test_prune_map(int32_t device, int64_t* top_idx, int32_t k, const int64_t* sel, int64_t idx_base);
+/* launch_finalize with every field of its argument block (csrc/abo_kernels.h: FinalizeArgs).  partial may be null when T = 0, mu_in
+ * when head_g is given; mu_eps goes with mu_tail; by outputs (pc > 1, point_major = 0) needs Mpts > 0. */
+typedef struct abo_test_finalize_args {
+    const double* partial; const double* mu_in;
+    double* mu_out; double* var_out; double* score_out;
+    double* mu_tail; const double* mu_eps; const double* head_g; const double* ssq_g;
+    int64_t ldp, j0, M, Mpts;
+    double sigma_f2, p0, best_y, prior_grad;
+    int32_t T, Mc, kind, pc, point_major, reserved;
+} abo_test_finalize_args;
+int32_t abo_test_finalize(int32_t device, const abo_test_finalize_args* args);
+/* launch_cand_gemv: c[j] = Σ_{k<n} Kzx[j][k]·v[k], j < M.  ld even and >= n + 1 (rows and v are read in pairs: v holds n rounded up to
+ * even entries; Kzx and v 16-byte aligned) */
+int32_t abo_test_cand_gemv(int32_t device, const double* Kzx, int64_t ld, const double* v, int32_t n, int64_t M, double* c);
+/* launch_downdate: mu[j] = fma(c[j], beta, mu[j]); var[j] = var[j] − c[j]·c[j]/s2, j < M */
+int32_t abo_test_downdate(int32_t device, double* mu, double* var, const double* c, int64_t M, double beta, double s2);
+/* launch_grad_cov with every field of its argument block (GradCovArgs) and the number of points (one workgroup each): V [npoints·p][ldv],
+ * mu_rows [npoints·p]; cov_out / mu_out / score_out (each may be null) are indexed from point pt0.  ABO_EINVAL where the launcher
+ * refuses (p·p + p doubles beyond the LDS of a workgroup). */
+int32_t abo_test_grad_cov(int32_t device, const double* V, const double* mu_rows, int64_t ldv, int32_t R, int32_t p, int64_t pt0,
+                          double prior0, double prior_g, double beta, double* cov_out, double* mu_out, double* score_out, int32_t npoints);
+/* launch_gather_points: out[j][0..d) = Z[idx[j] − idx_base][0..d), zeros for idx[j] < 0, j < k */
+int32_t abo_test_gather_points(int32_t device, const double* Z, const int64_t* idx, int64_t idx_base, int32_t k, int32_t d, double* out);
+/* launch_pick_record: rec[3 + d] = {tv[0], (double)ti[0], mu[ti[0] − idx_base], Z[ti[0] − idx_base][0..d)}, zeros behind ti[0] < 0 */
+int32_t abo_test_pick_record(int32_t device, const double* tv, const int64_t* ti, int64_t idx_base, const double* Z, const double* mu,
+                             int32_t d, double* rec);
+/* launch_score: score[j] = the epilogue `kind` at (mu[j], var[j]) by the plain scoring kernel — what finalize's score is held against */
+int32_t abo_test_score(int32_t device, const double* mu, const double* var, double* score, int64_t M, int32_t kind, double p0, double best_y);
 #endif /* ABO_TEST_HOOKS */
 
 #ifdef __cplusplus

@@ -219,11 +219,13 @@ def acquisition(kind, mu, var, p0, best_y):
 def top_k(scores, k):
     """`sortperm(scores; rev=true)[1:min(k,end)]` (src/acquisition_functions/acq_utils.jl:51-52).
     Julia's sortperm is stable, so equal scores keep the lowest index first; NaN sorts as the
-    largest value under isless, i.e. first under rev=true.  Returns 0-based indices."""
+    largest value under isless, i.e. first under rev=true; isless(-0.0, 0.0) holds, so 0.0 comes
+    ahead of −0.0 (−key alone cannot tell them apart: −0.0 == 0.0).  Returns 0-based indices."""
     scores = np.asarray(scores, dtype=np.float64)
     key = np.where(np.isnan(scores), np.inf, scores)
     nan_rank = np.isnan(scores).astype(np.int8)           # NaNs ahead of +Inf
-    order = np.lexsort((np.arange(scores.shape[0]), -key, -nan_rank))
+    neg_zero = ((key == 0.0) & np.signbit(key)).astype(np.int8)
+    order = np.lexsort((np.arange(scores.shape[0]), neg_zero, -key, -nan_rank))
     idx = order[: min(k, scores.shape[0])]
     return scores[idx], idx.astype(np.int64)
 

@@ -48,7 +48,10 @@ def test_shipped_library_exports_the_documented_surface_and_nothing_else():
     assert abo_syms == shipped, (sorted(set(abo_syms) - set(shipped)), sorted(set(shipped) - set(abo_syms)))
     assert not any(h in syms for h in hooks)
     # the generators' pass-through hooks among them: declared, in the test build, absent from the shipped library
-    for h in ("abo_test_kgen", "abo_test_cand_newcol"):
+    # … and those of the selection family
+    for h in ("abo_test_kgen", "abo_test_cand_newcol", "abo_test_topk_plan", "abo_test_topk", "abo_test_prune_compact",
+              "abo_test_prune_min_scatter", "abo_test_prune_map", "abo_test_finalize", "abo_test_cand_gemv", "abo_test_downdate",
+              "abo_test_grad_cov", "abo_test_gather_points", "abo_test_pick_record", "abo_test_score"):
         assert h in hooks and h in abo._lib.TEST_EXPORTS and h not in syms
     out_t = subprocess.run(["nm", "-D", "--defined-only", abo._lib.LIB_TEST_PATH], capture_output=True, text=True, check=True).stdout
     syms_t = {ln.split()[-1] for ln in out_t.splitlines() if ln.strip()}
