@@ -36,7 +36,8 @@ TEST_EXPORTS = ["abo_test_gemm_nt", "abo_test_kappa", "abo_test_oz_plan", "abo_t
                 "abo_test_nlml_terms", "abo_test_append",
                 "abo_test_topk_plan", "abo_test_topk", "abo_test_prune_compact", "abo_test_prune_min_scatter", "abo_test_prune_map",
                 "abo_test_finalize", "abo_test_cand_gemv", "abo_test_downdate", "abo_test_grad_cov", "abo_test_gather_points",
-                "abo_test_pick_record", "abo_test_score"]
+                "abo_test_pick_record", "abo_test_score",
+                "abo_test_oz_rowscale", "abo_test_oz_quant", "abo_test_oz_gemm", "abo_test_oz_crt", "abo_test_oz_modpack", "abo_test_oz_tickets"]
 # what launch_topk runs, as abo_test_topk_plan reports it (include/abo_hip.h: ABO_TOPK_PATH_*)
 TOPK_PATH_NONE, TOPK_PATH_SMALL, TOPK_PATH_SLICES, TOPK_PATH_ARGMAX, TOPK_PATH_BLOCKSORT = -1, 0, 1, 2, 3
 # margins of the pruned selection's guard (csrc/abo_kernels.h)
@@ -144,6 +145,14 @@ class AboTestFinalizeArgs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("partial", "mu_in", "mu_out", "var_out", "score_out", "mu_tail", "mu_eps", "head_g", "ssq_g")] + \
                [(n, C.c_int64) for n in ("ldp", "j0", "M", "Mpts")] + [(n, C.c_double) for n in ("sigma_f2", "p0", "best_y", "prior_grad")] + \
                [(n, C.c_int32) for n in ("T", "Mc", "kind", "pc", "point_major", "reserved")]
+
+
+class AboTestOzQuantArgs(C.Structure):
+    """every field of the residue quantiser's argument block but the plan, for abo_test_oz_quant (include/abo_hip.h: abo_test_oz_quant_args; test build only)"""
+    _fields_ = [("in_", C.c_void_p), ("ldin", C.c_int64)] + \
+               [(n, C.c_int32) for n in ("rows_in", "cols_in", "rows_out", "cols_out", "lower", "sconst")] + [("srow", C.c_void_p)] + \
+               [(n, C.c_int32) for n in ("kper", "ktg", "rmode", "rper", "rtg", "nmod")] + [("r0", C.c_int64), ("rpts", C.c_int64)] + \
+               [("out", C.c_void_p), ("ld", C.c_int64), ("plane", C.c_int64), ("bad", C.c_void_p)]
 
 
 class PosDefException(Exception):
@@ -279,6 +288,12 @@ def lib():
         L.abo_test_gather_points.argtypes = [i32, vp, vp, i64, i32, i32, vp]
         L.abo_test_pick_record.argtypes = [i32, vp, vp, i64, vp, vp, i32, vp]
         L.abo_test_score.argtypes = [i32, vp, vp, vp, i64, i32, f64, f64]
+        L.abo_test_oz_rowscale.argtypes = [i32, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, f64, f64, f64, vp, vp]
+        L.abo_test_oz_quant.argtypes = [i32, C.POINTER(AboTestOzQuantArgs)]
+        L.abo_test_oz_gemm.argtypes = [i32, vp, vp, i32, i32, i32, i32, i64, vp, i32]
+        L.abo_test_oz_crt.argtypes = [i32, vp, i32, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i64, i64, vp, vp, i64, vp, i64, i32, vp]
+        L.abo_test_oz_modpack.argtypes = [i32, vp, i64, i32, vp]
+        L.abo_test_oz_tickets.argtypes = [i32, i32, i32, vp, C.POINTER(i64)]
     L.abo_mgpu_create.argtypes = [C.POINTER(AboParams), i32, C.POINTER(i32), C.POINTER(vp)]
     L.abo_mgpu_create_grad.argtypes = [C.POINTER(AboParams), i32, vp, i32, C.POINTER(i32), C.POINTER(vp)]
     L.abo_mgpu_append_grad.argtypes = [vp, vp, i32, vp, C.POINTER(i64), vp]

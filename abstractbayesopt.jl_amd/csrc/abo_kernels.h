@@ -174,6 +174,63 @@ struct OzVarArgs {
 };
 hipError_t launch_var_ozaki(const OzVarArgs& a, hipStream_t s);
 
+// ---- the stages of launch_var_ozaki / oz_prepare_w / oz_prepare_w_bound, one launcher each, on raw pointers (ozaki.hip).  Each returns
+// hipErrorInvalidValue, and launches nothing, for arguments its kernel cannot take.
+constexpr int OZ_SEXP_MAX = 960;            // no row scale above this (oz_row_scale: the clamp)
+constexpr int OZ_SEXP_BAD = -(1 << 20);     // the row scale of a row whose norm is not finite or ≥ 1e300: flagged by the quantiser, NaN in V
+// the guard of a short plan (ozaki.hip: "the guarded bound"); delta == nullptr: none
+struct OzGuardArgs {
+    double* delta;          // [Np256] or nullptr: no guard (every plan but the short one)
+    int eP_full, sK_b, sK_full;
+    double kmax, rec_b, rec_full;
+};
+// oz_rowscale_kernel: sexp[0 .. rows256) (and gd.delta) from the first nrows rows of the lower-triangular W; rows ≥ nrows get 0
+hipError_t launch_oz_rowscale(const double* W, int64_t ldw, int nrows, int rows256, int eP, int* sexp, int kper, int ktg, int kbits,
+                              const OzGuardArgs& gd, hipStream_t s);
+// oz_quant_kernel: fp64 → n residue planes in the device layout (abo_oz_dev.h: oz_plane_off)
+struct OzQuantArgs {
+    const double* in;
+    int64_t ldin;
+    int rows_in, cols_in, rows_out, cols_out;
+    int lower;                 // 1: entries with k > r are zero (W = L⁻¹; the stored zeros are not even read)
+    const int* srow;
+    int sconst;
+    int kper, ktg;             // columns k with k % kper != 0 get 2^ktg on top (kper ≤ 1: none)
+    int rmode, rper, rtg;      // rows whose output index (oz_row_output) is not 0 get 2^rtg on top (rmode 0: none)
+    int64_t r0, rpts;
+    int8_t* out;
+    int64_t ld, plane;
+    int* bad;                  // [rows_out] or nullptr
+    OzPlan pl;
+};
+hipError_t launch_oz_quant(const OzQuantArgs& q, hipStream_t s);
+// 256-row blocks of W the residue GEMM, U and the reconstruction cover: all Np256 / 256 of them, or the first rblocks (OzVarArgs::rblocks)
+inline int oz_gemm_row_blocks(int Np256, int rblocks) { return rblocks > 0 && rblocks < Np256 / 256 ? rblocks : Np256 / 256; }
+// the persistent residue GEMM: U (oz_u_block layout, row blocks as above × Mc256 / 256 column blocks × pl.n moduli) from the planes
+// KR [n][Mc256][Np256] and WR [n][·][Np256] (plane stride w_plane bytes, 0 = Np256²; LOWER-TRIANGULAR: the kernel skips the units of
+// a diagonal block that lie above the diagonal).  ctr: 8 tile counters, zero on entry; the kernel leaves them advanced.
+hipError_t launch_oz_gemm(const OzPlan& pl, const int8_t* KR, const int8_t* WR, int8_t* U, int Np256, int Mc256, int rblocks, int64_t w_plane,
+                          int* ctr, hipStream_t s);
+// the tile list of that launch as the kernel decodes it (host): tiles[8·per_list] = the decoded ticket of every (list y, q < per_list),
+// y-major — ti | tj << 9 | l << 20, or −1 for a padding block; returns 8·per_list, the launcher's `blocks` (tiles may be null)
+int64_t oz_gemm_tickets(int Ti, int Tj, int n, int32_t* tiles);
+// the reconstruction: V itself (V != nullptr: oz_crt_v_kernel), or the column sums of squares per 128-row block (oz_crt_kernel: exact,
+// or guarded when delta is given; the compile-time moduli count where there is one, unless generic is set)
+struct OzCrtLaunch {
+    const OzPlan* plan;
+    const int8_t* U; int Ti;
+    const int* sexp; int sK;
+    const int* bad_row; const int* bad_col;
+    int Np, Mc, nvalid;
+    int rmode, rper, rtg; int64_t r0, rpts;
+    int* ctr_reset;            // the GEMM's counters, zeroed by the kernel (or nullptr)
+    const double* delta;       // the guard (sums only)
+    double* partial; int64_t ldp;
+    double* V; int64_t ldv;
+    int generic;               // 1: the run-time moduli loop (NM = 0) also at 14 and 8 moduli
+};
+hipError_t launch_oz_crt(const OzCrtLaunch& c, hipStream_t s);
+
 // ---- kernel-matrix generation (kgen.hip) ----------------------------------------------------
 struct KgenArgs {
     const double* Xs;     // [Np][dp]   training points, pre-scaled by 1/ell, zero padded

@@ -94,4 +94,29 @@ __device__ __forceinline__ void oz_residue_pair(double x0, double x1, Emit&& emi
     }
 }
 
+// ---- the residue GEMM's epilogue arithmetic (ozaki.hip: oz16p_epilogue) ----------------------------------------------------------------------
+// four accumulators (four consecutive candidates of one W row) → their symmetric residues mod p, one byte each: q = rint(x/p) is exact
+// (|x| < 2^31, so x/p in fp64 is far closer to the true quotient than 1/(2p)) and r = x − q·p lands in [−p/2, p/2].
+// Three VALU operations per accumulator (the persistent kernel's epilogue: its residue
+// arithmetic is issue-bound, two waves per SIMD taking turns — 4.7 of a tile's 52 µs with the matrix pipe idle): the product x·(1/p)
+// is rounded to the nearest integer by adding 1.5·2^52 inside the fma (one rounding instead of two, the same integer: x/p is at
+// least 1/(2p) away from a half-integer for odd p), the quotient is then the low dword of the sum's mantissa as it stands — no
+// v_rndne, no conversion back —, and r = x − q·p is one v_mad_i32_i24 (|q| ≤ 2^30/199 < 2^23 for every row count the engine takes).
+// p = 256: ties round to even.
+__device__ __forceinline__ int oz_mod_pack4_mad(int a0, int a1, int a2, int a3, double invp, int p) {
+    const int v[4] = {a0, a1, a2, a3};
+    int r[4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        const double t = __builtin_fma((double)v[b], invp, 6755399441055744.0);
+        const int q = __double2loint(t);
+        // (as asm: from C the compiler picks the quarter-rate v_mul_lo_u32)
+        asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r[b]) : "v"(q), "s"(-p), "v"(v[b]));
+    }
+    // the four low bytes into one dword: three v_perm_b32 (selector bytes 0-3: second source, 4-7: first source)
+    const unsigned lo = __builtin_amdgcn_perm((unsigned)r[1], (unsigned)r[0], 0x0c0c0400u);
+    const unsigned hi = __builtin_amdgcn_perm((unsigned)r[3], (unsigned)r[2], 0x0c0c0400u);
+    return (int)__builtin_amdgcn_perm(hi, lo, 0x05040100u);
+}
+
 }  // namespace abo

@@ -123,17 +123,18 @@ bool oz_make_plan(int n, OzPlan* out) {
 // shaved by 1 − (R + 16)·2^-52 on top — not needed while the two passes share their summation order; it keeps the claim true should
 // they ever stop sharing it.)  A row with a non-finite or overflowing norm gets delta = +Inf (it contributes 0, and bad_row makes
 // the bound NaN: kept, as today); an all-zero row 0.
-struct OzGuardArgs {
-    double* delta;          // [Np256] or nullptr: no guard (every plan but the short one)
-    int eP_full, sK_b, sK_full;
-    double kmax, rec_b, rec_full;
-};
-
 // THE row-scale rule, for every plan: the full plan's scales (oz_prepare_w) and the guard's re-derivation of them go through this one
 // function, so δ cannot drift from the scale the full pass actually uses (e1 = e(L1), e2 = e(max))
-__device__ __forceinline__ int oz_row_scale(int eP, int kbits, int e1, int e2) {
-    const int sa = eP - kbits - e1, sb = 52 - e2;
-    return sa < sb ? sa : sb;
+// The clamp: a smaller s than the rule's is always safe (the P/4 bound needs s ≤ rule only; the row keeps fewer bits), and the
+// quantiser forms 2^(s + ktg) as a double: s ≤ OZ_SEXP_MAX − max(ktg, 0) keeps it finite for rows of norm below about 2^-905 (2^s was
+// +Inf from 2^-970 down: every residue of such a row garbage, its V finite and wrong, nothing flagged).  Downwards nothing is needed: a
+// row with L1 < 1e300 has s ≥ eP − kbits − 997 > −1022, and a row beyond that is flagged (OZ_SEXP_BAD, below).  The other factor, 2^−(s + sK),
+// depends on the chunk and is looked at where it is formed (oz_crt_kernel, oz_crt_v_kernel: OZ_CRT_EXP_OK).  Held on a norm ladder
+// 2^-1040 … 2^990 by tests/test_gpu_oz_family.py.
+__device__ __forceinline__ int oz_row_scale(int eP, int kbits, int e1, int e2, int ktg = 0) {
+    const int sa = eP - kbits - e1, sb = 52 - e2, sc = OZ_SEXP_MAX - (ktg > 0 ? ktg : 0);
+    const int s = sa < sb ? sa : sb;
+    return s < sc ? s : sc;
 }
 constexpr int OZ_FULL_KBITS = 53;      // the full-width image of K: what oz_prepare_w scales the handle's plan for
 
@@ -163,11 +164,11 @@ __global__ void __launch_bounds__(256) oz_rowscale_kernel(const double* __restri
     if (lane == 0) {
         int s = 0;
         double dl = 0.0;
-        if (mx > 0.0 && l1 < 1.0e300) {                // a NaN/Inf row keeps s = 0: its residues are garbage, its V is flagged
+        if (mx > 0.0 && l1 < 1.0e300) {
             int e1, e2;
             (void)frexp(l1, &e1);
             (void)frexp(mx, &e2);
-            s = oz_row_scale(eP, kbits, e1, e2);
+            s = oz_row_scale(eP, kbits, e1, e2, kper > 1 ? ktg : 0);
             if (gd.delta) {
                 // the full plan's scale of this row: same kernel, same l1 / mx (kper = 1: the bound pass is StandardGP only), same rule
                 const int sf = oz_row_scale(gd.eP_full, OZ_FULL_KBITS, e1, e2);
@@ -178,7 +179,13 @@ __global__ void __launch_bounds__(256) oz_rowscale_kernel(const double* __restri
                      0x1p-50 * (l1u * gd.kmax + Ab + Af);
                 dl *= 1.0 + 0x1p-40;
             }
-        } else if (!(mx == 0.0)) dl = __builtin_inf();
+        } else if (!(mx == 0.0)) {
+            // a NaN / Inf row, or one whose norm overflows although every entry is below 1e300 (the quantiser looks at entries only: such a
+            // row was not flagged, its residues at s = 0 garbage): the scale says so, the quantiser flags the row (bad[r]) on seeing it,
+            // and no reconstruction can form 2^−(s + sK) from it
+            dl = __builtin_inf();
+            s = OZ_SEXP_BAD;
+        }
         sexp[row] = s;
         if (gd.delta) gd.delta[row] = dl;
     }
@@ -195,22 +202,6 @@ __device__ __forceinline__ int oz_row_output(int rmode, int rper, int64_t r0, in
 // out[l][r][k] (int8, ld bytes per row, plane stride `plane`) = sym_residue(rint(in[r][k]·2^s), p_l) for r < rows_in, k < cols_in;
 // zeros elsewhere up to rows_out × cols_out.  s = srow[r] when given, else sconst.  A thread converts 16 consecutive k of one row.
 // bad[r] is set when a row holds a non-finite value (its residues mean nothing; the reconstruction writes NaN for that row).
-struct OzQuantArgs {
-    const double* in;
-    int64_t ldin;
-    int rows_in, cols_in, rows_out, cols_out;
-    int lower;                 // 1: entries with k > r are zero (W = L⁻¹; the stored zeros are not even read)
-    const int* srow;
-    int sconst;
-    int kper, ktg;             // columns k with k % kper != 0 get 2^ktg on top (kper ≤ 1: none)
-    int rmode, rper, rtg;      // rows whose output index (oz_row_output) is not 0 get 2^rtg on top (rmode 0: none)
-    int64_t r0, rpts;
-    int8_t* out;
-    int64_t ld, plane;
-    int* bad;                  // [rows_out] or nullptr
-    OzPlan pl;
-};
-
 __global__ void __launch_bounds__(256) oz_quant_kernel(OzQuantArgs a) {
     const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int cpr = a.cols_out >> 4;                   // 16-byte groups per output row
@@ -221,7 +212,9 @@ __global__ void __launch_bounds__(256) oz_quant_kernel(OzQuantArgs a) {
     bool bad = false;
     if (live) {
         const int rt = oz_row_output(a.rmode, a.rper, a.r0, a.rpts, r) != 0 ? a.rtg : 0;
-        const double sc = __builtin_ldexp(1.0, (a.srow ? a.srow[r] : a.sconst) + rt);
+        const int s0 = a.srow ? a.srow[r] : a.sconst;
+        bad = a.srow && s0 == OZ_SEXP_BAD;              // oz_rowscale_kernel: the row's norm is not finite or overflows
+        const double sc = __builtin_ldexp(1.0, s0 + rt);
         const double cw = __builtin_ldexp(1.0, a.ktg);
         const double* src = a.in + (int64_t)r * a.ldin + kc;
 #pragma unroll
@@ -282,31 +275,7 @@ struct OzGemmArgs {
 // in L2 only while they walk k together; L2 hit rate 60 % → 78 %).  Row groups innermost: the residue planes of one modulus for 64
 // column blocks (128 MB at N = 8192) are swept by all row groups back to back and stay in the Infinity Cache meanwhile.
 
-// ---- epilogue pieces shared by the GEMM kernels -------------------------------------------------------------------------------------------
-// four accumulators (four consecutive candidates of one W row) → their symmetric residues mod p, one byte each: q = rint(x/p) is exact
-// (|x| < 2^31, so x/p in fp64 is far closer to the true quotient than 1/(2p)) and r = x − q·p lands in [−p/2, p/2].
-// Three VALU operations per accumulator (the persistent kernel's epilogue: its residue
-// arithmetic is issue-bound, two waves per SIMD taking turns — 4.7 of a tile's 52 µs with the matrix pipe idle): the product x·(1/p)
-// is rounded to the nearest integer by adding 1.5·2^52 inside the fma (one rounding instead of two, the same integer: x/p is at
-// least 1/(2p) away from a half-integer for odd p), the quotient is then the low dword of the sum's mantissa as it stands — no
-// v_rndne, no conversion back —, and r = x − q·p is one v_mad_i32_i24 (|q| ≤ 2^30/199 < 2^23 for every row count the engine takes).
-// p = 256: ties round to even.
-__device__ __forceinline__ int oz_mod_pack4_mad(int a0, int a1, int a2, int a3, double invp, int p) {
-    const int v[4] = {a0, a1, a2, a3};
-    int r[4];
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-        const double t = __builtin_fma((double)v[b], invp, 6755399441055744.0);
-        const int q = __double2loint(t);
-        // (as asm: from C the compiler picks the quarter-rate v_mul_lo_u32)
-        asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r[b]) : "v"(q), "s"(-p), "v"(v[b]));
-    }
-    // the four low bytes into one dword: three v_perm_b32 (selector bytes 0-3: second source, 4-7: first source)
-    const unsigned lo = __builtin_amdgcn_perm((unsigned)r[1], (unsigned)r[0], 0x0c0c0400u);
-    const unsigned hi = __builtin_amdgcn_perm((unsigned)r[3], (unsigned)r[2], 0x0c0c0400u);
-    return (int)__builtin_amdgcn_perm(hi, lo, 0x05040100u);
-}
-
+// (the epilogue's residue arithmetic, oz_mod_pack4_mad, lives in abo_oz_dev.h: the test build applies it to chosen integers)
 struct OzFragA { v4i_t a[4]; };
 struct OzFragB { v4i_t b[4]; };
 
@@ -520,7 +489,7 @@ __device__ __forceinline__ void oz16p_epilogue(const OzGemmArgs& a, char* slot3,
 
 // x / d and x % d for 0 ≤ x < 2^23, 0 < d < 2^23 without the integer-division expansion (one thread decodes a ticket per tile: the
 // seven divisions of the plain decode were 0.7 µs in front of a workgroup barrier): fp32 estimate, one correction step each way
-__device__ __forceinline__ void oz_divmod(int x, int d, float rd, int& q, int& r) {
+__host__ __device__ __forceinline__ void oz_divmod(int x, int d, float rd, int& q, int& r) {
     q = (int)((float)x * rd);
     r = x - q * d;
     if (r < 0) { --q; r += d; }
@@ -529,7 +498,7 @@ __device__ __forceinline__ void oz_divmod(int x, int d, float rd, int& q, int& r
 
 // ticket q of list y → the tile (ti, tj, l) packed as ti | tj << 9 | l << 20, or −1 for a padding block: block
 // (q / cpx)·per_group + (q % cpx)·8 + y of the order described at OzGemmArgs
-__device__ __forceinline__ int oz16p_decode_ticket(const OzGemmArgs& a, int q, int y) {
+__host__ __device__ __forceinline__ int oz16p_decode_ticket(const OzGemmArgs& a, int q, int y) {
     const int cpx = a.tjg >> 1, cols_x = a.tjg >> 3;           // per_group / 8, column blocks per XCD patch
     const int ngi = (a.Ti + 3) / 4;
     int grp, c, t, gg, gh, gl, ro, cc;
@@ -675,6 +644,10 @@ __global__ void __launch_bounds__(512) oz_gemm16p_kernel(OzGemmArgs a, int total
 }
 
 // ---- reconstruction + squares + column sums ------------------------------------------------------------------------------------------
+// The scaling 2^−(s_i + sK) is formed as a double: exact from 2^-1074 to 2^1023, and V = C'·2^−(s_i + sK) is then one correctly rounded
+// product (a subnormal result errs by < 2^-1075, half an integer unit of the image at most).  Outside that range the factor is 0 or
+// +Inf and V would be finite and wrong (0) or ±Inf: such a row is treated as a flagged one — NaN, as for bad_row.
+#define OZ_CRT_EXP_OK(ex) ((unsigned)((ex) + 1074) <= 2097u)
 // partial[tb][j] = Σ_{i in row block tb (128 rows), i < nvalid} V[i][j]²,  V = CRT(U[·][i][j])·2^−(s_i + sK).
 struct OzCrtArgs {
     const int8_t* U;       // oz_u_block layout
@@ -731,10 +704,11 @@ __global__ void __launch_bounds__(256) oz_crt_kernel(OzCrtArgs a) {
 #pragma unroll
                 for (int l = 0; l < NM; ++l) wl[l] = __builtin_nontemporal_load(reinterpret_cast<const v4i_t*>(u + (int64_t)l * (OZ_T * OZ_T)));
             }
-            const double sc = __builtin_ldexp(1.0, -(a.sexp[i] + a.sK));
+            const int ex = -(a.sexp[i] + a.sK);
+            const double sc = __builtin_ldexp(1.0, ex);
             double dl = 0.0;
             if constexpr (GUARD) dl = a.delta[i];
-            if (a.bad_row && a.bad_row[i]) bad = true;
+            if ((a.bad_row && a.bad_row[i]) || !OZ_CRT_EXP_OK(ex)) bad = true;
             // four candidates (one dword of every plane) at a time: 8 partial sums live instead of 32 — 4 waves per SIMD instead of 3
 #pragma unroll
             for (int g4 = 0; g4 < 4; ++g4) {
@@ -851,8 +825,9 @@ __global__ void __launch_bounds__(256) oz_crt_v_kernel(OzCrtVArgs a) {
                         c2[b] = __builtin_fma(ud, s2, c2[b]);
                     }
                 }
-                const double sc = __builtin_ldexp(1.0, -(a.sexp[i] + a.sK));
-                const bool rbad = a.bad_row && a.bad_row[i];
+                const int ex = -(a.sexp[i] + a.sK);
+                const double sc = __builtin_ldexp(1.0, ex);
+                const bool rbad = (a.bad_row && a.bad_row[i]) || !OZ_CRT_EXP_OK(ex);
 #pragma unroll
                 for (int b = 0; b < 4; ++b) {
                     const double Q = __builtin_rint((c1[b] + c2[b]) * a.pl.invP);
@@ -893,13 +868,11 @@ hipError_t oz_prepare_w(const OzPlan& pl, const double* W, int64_t ldw, int Np, 
     const int Np256 = (int)pad_up(Np, OZ_T);
     hipError_t e = hipMemsetAsync(bad_row, 0, sizeof(int) * Np256, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(oz_rowscale_kernel, dim3((Np256 + 3) / 4), dim3(256), 0, s, W, ldw, nvalid, Np256, pl.eP, sexp, kper, ktg, OZ_FULL_KBITS, OzGuardArgs{});
+    if ((e = launch_oz_rowscale(W, ldw, nvalid, Np256, pl.eP, sexp, kper, ktg, OZ_FULL_KBITS, OzGuardArgs{}, s)) != hipSuccess) return e;
     OzQuantArgs q{};
     q.in = W; q.ldin = ldw; q.rows_in = nvalid; q.cols_in = Np; q.rows_out = Np256; q.cols_out = Np256; q.lower = 1;
     q.srow = sexp; q.sconst = 0; q.kper = kper; q.ktg = ktg; q.rmode = 0; q.rper = 1; q.rtg = 0; q.r0 = 0; q.rpts = 1; q.out = WR; q.ld = Np256; q.plane = (int64_t)Np256 * Np256; q.bad = bad_row; q.pl = pl;
-    const int64_t threads = (int64_t)Np256 * (Np256 / 16);
-    hipLaunchKernelGGL(oz_quant_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, q);
-    return hipGetLastError();
+    return launch_oz_quant(q, s);
 }
 
 // sK: K' = rint(K·2^sK) < 2^53 for K ≤ kmax (kmax = σ_f²: the stationary kernels of this library peak at distance 0)
@@ -930,14 +903,123 @@ hipError_t oz_prepare_w_bound(const OzPlan& pl, const OzPlan& full, const double
     gd.delta = delta; gd.eP_full = full.eP; gd.sK_b = sK_b; gd.sK_full = sK_full; gd.kmax = kmax;
     gd.rec_b = (128.0 * pl.n * pl.n + 256.0 * pl.n) * std::ldexp(1.0, pl.eP - 91);
     gd.rec_full = (128.0 * full.n * full.n + 256.0 * full.n) * std::ldexp(1.0, full.eP - 91);
-    hipLaunchKernelGGL(oz_rowscale_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, W, ldw, nv, rows, pl.eP, sexp_b, 1, 0, kbits, gd);
+    if ((e = launch_oz_rowscale(W, ldw, nv, rows, pl.eP, sexp_b, 1, 0, kbits, gd, s)) != hipSuccess) return e;
     // rows × rows of the triangle, in planes that keep the full planes' row stride (block (R, H) of a plane at (R·nhs + H)·16 KB,
     // nhs = Np256 / 64): the bytes k ≥ rows of a row are neither written here nor read by a contraction limited to these rows
     OzQuantArgs q{};
     q.in = W; q.ldin = ldw; q.rows_in = nv; q.cols_in = Np < rows ? Np : rows; q.rows_out = rows; q.cols_out = rows; q.lower = 1;
     q.srow = sexp_b; q.sconst = 0; q.kper = 1; q.ktg = 0; q.rmode = 0; q.rper = 1; q.rtg = 0; q.r0 = 0; q.rpts = 1; q.out = WRb; q.ld = Np256; q.plane = (int64_t)rows * Np256; q.bad = bad_row_b; q.pl = pl;
-    const int64_t threads = (int64_t)rows * (rows / 16);
+    return launch_oz_quant(q, s);
+}
+
+// ---- the stage launchers ---------------------------------------------------------------------------------------------------------------
+hipError_t launch_oz_rowscale(const double* W, int64_t ldw, int nrows, int rows256, int eP, int* sexp, int kper, int ktg, int kbits,
+                              const OzGuardArgs& gd, hipStream_t s) {
+    // ktg: 2^ktg and, with the clamp of oz_row_scale (s + ktg ≤ OZ_SEXP_MAX; s > −962 for a row that is not flagged), 2^(s + ktg) stay
+    // normal numbers (a gradient-enhanced model's 2^ktg ≈ √c/ℓ)
+    if (!W || !sexp || nrows < 0 || rows256 <= 0 || nrows > rows256 || ldw < nrows || kper < 1 || ktg < -60 || ktg > 900 || kbits < 2 || kbits > 53)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(oz_rowscale_kernel, dim3((rows256 + 3) / 4), dim3(256), 0, s, W, ldw, nrows, rows256, eP, sexp, kper, ktg, kbits, gd);
+    return hipGetLastError();
+}
+
+hipError_t launch_oz_quant(const OzQuantArgs& q, hipStream_t s) {
+    if (!q.in || !q.out || q.rows_out <= 0 || q.cols_out <= 0 || q.cols_out % 16 || q.ld % 64 || q.cols_out > q.ld || q.rows_in < 0 ||
+        q.rows_in > q.rows_out || q.cols_in < 0 || q.cols_in > q.cols_out || q.ldin < q.cols_in || q.pl.n < 1 || q.pl.n > OZ_MAXMOD ||
+        (q.rmode && (q.rper < 1 || q.rpts < 1)))
+        return hipErrorInvalidValue;
+    // the scale is formed as doubles 2^(s + rtg) and 2^ktg and their product: with one scale for the whole operand (the chunk's sK) all
+    // three must be normal numbers — a kmax below about 2^-900 or above 2^1000 is refused here; per-row scales come clamped from
+    // oz_rowscale_kernel
+    const int kt = q.kper > 1 ? q.ktg : 0, rt = q.rmode ? q.rtg : 0;
+    if (!q.srow) {
+        const int lo = q.sconst + (rt < 0 ? rt : 0) + (kt < 0 ? kt : 0), hi = q.sconst + (rt > 0 ? rt : 0) + (kt > 0 ? kt : 0);
+        if (lo < -1022 || hi > 1023) return hipErrorInvalidValue;
+    } else if (kt < -60 || kt > 900 || rt < -60 || rt > 60) return hipErrorInvalidValue;      // (as launch_oz_rowscale; 2^(s + rtg) likewise)
+    const int64_t threads = (int64_t)q.rows_out * (q.cols_out / 16);
     hipLaunchKernelGGL(oz_quant_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, q);
+    return hipGetLastError();
+}
+
+// the tile list's shape: everything of OzGemmArgs the ticket decode reads; returns the launch's `blocks` (8 lists of blocks / 8 tickets)
+static unsigned oz_gemm_shape(int Ti, int Tj, int n, OzGemmArgs& g) {
+    g.Ti = Ti; g.Tj = Tj; g.n = n;
+    g.tjg = g.Tj >= 64 ? 64 : (int)pad_up(g.Tj, 8);
+    const int ngj = (g.Tj + g.tjg - 1) / g.tjg, ngi = (g.Ti + 3) / 4;
+    return (unsigned)(ngi * n * ngj * 4 * g.tjg);
+}
+
+// what the kernel's packing (ti < 512, tj < 2048 in ti | tj << 9 | l << 20), oz_divmod (tickets and divisors below 2^23) and the int32
+// accumulators (k·2^14 ≤ 2^30) can take — the engine's own limits (api.hip: wants_int8 up to 65536 padded rows, pick_chunk up to
+// 65536 candidates) lie inside: Ti ≤ 256, Tj ≤ 256, at most 1024 tickets a list (tests/test_oz_ref_cpu.py walks that launch)
+static bool oz_gemm_shape_ok(int Ti, int Tj, int n, int Np256) {
+    if (Ti < 1 || Tj < 1 || Ti > 256 || Tj > 2047 || n < 1 || n > OZ_MAXMOD || Np256 > 65536) return false;
+    OzGemmArgs g{};
+    return (oz_gemm_shape(Ti, Tj, n, g) >> 3) < (1u << 23);
+}
+
+int64_t oz_gemm_tickets(int Ti, int Tj, int n, int32_t* tiles) {
+    if (!oz_gemm_shape_ok(Ti, Tj, n, 0)) return -1;
+    OzGemmArgs g{};
+    const int64_t blocks = oz_gemm_shape(Ti, Tj, n, g);
+    const int per_list = (int)(blocks >> 3);
+    if (tiles)
+        for (int y = 0; y < 8; ++y)
+            for (int q = 0; q < per_list; ++q) tiles[(int64_t)y * per_list + q] = oz16p_decode_ticket(g, q, y);
+    return blocks;
+}
+
+hipError_t launch_oz_gemm(const OzPlan& pl, const int8_t* KR, const int8_t* WR, int8_t* U, int Np256, int Mc256, int rblocks, int64_t w_plane,
+                          int* ctr, hipStream_t s) {
+    if (!KR || !WR || !U || !ctr || Np256 <= 0 || Np256 % OZ_T || Mc256 <= 0 || Mc256 % OZ_T || w_plane < 0) return hipErrorInvalidValue;
+    OzGemmArgs g{};
+    g.KR = KR; g.WR = WR; g.U = U;
+    g.nhs = Np256 / 64;
+    g.sK = (int64_t)Mc256 * Np256; g.sW = w_plane > 0 ? w_plane : (int64_t)Np256 * Np256;
+    // (rblocks: the tile list, the layout of U and the reconstruction cover the first row blocks only; nhs, the stride between the
+    // row blocks of a plane, stays that of the buffers)
+    if (!oz_gemm_shape_ok(oz_gemm_row_blocks(Np256, rblocks), Mc256 / OZ_T, pl.n, Np256)) return hipErrorInvalidValue;
+    const unsigned blocks = oz_gemm_shape(oz_gemm_row_blocks(Np256, rblocks), Mc256 / OZ_T, pl.n, g);
+    for (int l = 0; l < pl.n; ++l) {
+        g.invp[l] = pl.invp[l]; g.p[l] = pl.p[l];
+    }
+    // persistent: one workgroup per CU
+    static const int cus = [] { int d = 0; hipDeviceProp_t pr; return (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&pr, d) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256; }();
+    const int G = (unsigned)cus < blocks ? cus : (int)blocks;
+    hipLaunchKernelGGL(oz_gemm16p_kernel, dim3(G), dim3(512), 0, s, g, (int)blocks, ctr);
+    return hipGetLastError();
+}
+
+hipError_t launch_oz_crt(const OzCrtLaunch& v, hipStream_t s) {
+    if (!v.plan || !v.U || !v.sexp || v.Ti < 1 || v.Np <= 0 || v.Np % 128 || v.Mc <= 0 || v.Mc % 128 || v.nvalid < 0 || v.nvalid > v.Np ||
+        (v.rmode && (v.rper < 1 || v.rpts < 1)))
+        return hipErrorInvalidValue;
+    const OzPlan& pl = *v.plan;
+    if (v.V) {
+        if (v.delta || v.ldv < v.nvalid || v.nvalid > v.Ti * OZ_T) return hipErrorInvalidValue;
+        OzCrtVArgs c{};
+        c.U = v.U; c.Ti = v.Ti; c.sexp = v.sexp; c.sK = v.sK; c.bad_row = v.bad_row; c.bad_col = v.bad_col;
+        c.V = v.V; c.ldv = v.ldv; c.Mc = v.Mc; c.nvalid = v.nvalid; c.pl = pl;
+        c.rmode = v.rmode; c.rper = v.rper; c.rtg = v.rtg; c.r0 = v.r0; c.rpts = v.rpts;
+        c.ctr_reset = v.ctr_reset;
+        hipLaunchKernelGGL(oz_crt_v_kernel, dim3((v.Mc + 255) / 256, v.Np / 128), dim3(256), 0, s, c);
+        return hipGetLastError();
+    }
+    if (!v.partial || v.ldp < v.Mc) return hipErrorInvalidValue;
+    OzCrtArgs c{};
+    c.U = v.U; c.Ti = v.Ti; c.sexp = v.sexp; c.sK = v.sK; c.bad_row = v.bad_row; c.bad_col = v.bad_col;
+    c.partial = v.partial; c.ldp = v.ldp; c.Mc = v.Mc; c.nvalid = v.nvalid < v.Ti * OZ_T ? v.nvalid : v.Ti * OZ_T; c.pl = pl;
+    c.rmode = v.rmode; c.rper = v.rper; c.rtg = v.rtg; c.r0 = v.r0; c.rpts = v.rpts;
+    c.ctr_reset = v.ctr_reset;
+    const int tbs = 2 * v.Ti < v.Np / 128 ? 2 * v.Ti : v.Np / 128;      // 128-row blocks of partial
+    const dim3 grid((v.Mc + 255) / 256, tbs);
+    if (v.delta) {             // the guarded bound of a short plan
+        if (v.rmode) return hipErrorInvalidValue;
+        c.delta = v.delta; c.shave = 1.0 - (double)(c.nvalid + 16) * 0x1p-52;
+        if (pl.n == 8 && !v.generic) hipLaunchKernelGGL((oz_crt_kernel<8, true>), grid, dim3(256), 0, s, c);
+        else hipLaunchKernelGGL((oz_crt_kernel<0, true>), grid, dim3(256), 0, s, c);
+    } else if (pl.n == 14 && !v.generic) hipLaunchKernelGGL(oz_crt_kernel<14>, grid, dim3(256), 0, s, c);
+    else hipLaunchKernelGGL(oz_crt_kernel<0>, grid, dim3(256), 0, s, c);
     return hipGetLastError();
 }
 
@@ -950,61 +1032,26 @@ hipError_t launch_var_ozaki(const OzVarArgs& v, hipStream_t s) {
         OzQuantArgs q{};
         q.in = v.Kxz; q.ldin = v.ldk; q.rows_in = v.Mc; q.cols_in = v.Np; q.rows_out = Mc256; q.cols_out = Np256; q.lower = 0;
         q.srow = nullptr; q.sconst = v.sK; q.kper = v.kper; q.ktg = -v.ktg; q.rmode = v.rmode; q.rper = v.rper; q.rtg = -v.ktg; q.r0 = v.r0; q.rpts = v.rpts; q.out = v.KR; q.ld = Np256; q.plane = (int64_t)Mc256 * Np256; q.bad = v.bad_col; q.pl = pl;
-        const int64_t threads = (int64_t)Mc256 * (Np256 / 16);
-        hipLaunchKernelGGL(oz_quant_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, q);
+        if ((e = launch_oz_quant(q, s)) != hipSuccess) return e;
     }
     if (v.ev_quant && (e = hipEventRecord(v.ev_quant, s)) != hipSuccess) return e;
 
-    OzGemmArgs g{};
-    g.KR = v.KR; g.WR = v.WR; g.U = v.U;
-    g.nhs = Np256 / 64;
-    g.sK = (int64_t)Mc256 * Np256; g.sW = v.w_plane > 0 ? v.w_plane : (int64_t)Np256 * Np256;
-    // (rblocks: the tile list, the layout of U and the reconstruction cover the first row blocks only; nhs, the stride between the
-    // row blocks of a plane, stays that of the buffers)
-    g.Ti = v.rblocks > 0 && v.rblocks < Np256 / OZ_T ? v.rblocks : Np256 / OZ_T; g.Tj = Mc256 / OZ_T; g.n = pl.n;
-    g.tjg = g.Tj >= 64 ? 64 : (int)pad_up(g.Tj, 8);
-    for (int l = 0; l < pl.n; ++l) {
-        g.invp[l] = pl.invp[l]; g.p[l] = pl.p[l];
-    }
-    const int ngj = (g.Tj + g.tjg - 1) / g.tjg, ngi = (g.Ti + 3) / 4;
-    const unsigned blocks = (unsigned)(ngi * pl.n * ngj * 4 * g.tjg);
-    {
-        // persistent: one workgroup per CU; the tile counters (one per XCD list) sit behind the chunk's bad_col flags
-        static const int cus = [] { int d = 0; hipDeviceProp_t pr; return (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&pr, d) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256; }();
-        int* ctr = v.bad_col + Mc256;
-        if (!(v.ctr_clean && *v.ctr_clean == ctr) && (e = hipMemsetAsync(ctr, 0, sizeof(int) * 8, s)) != hipSuccess) return e;
-        if (v.ctr_clean) *v.ctr_clean = nullptr;
-        const int G = (unsigned)cus < blocks ? cus : (int)blocks;
-        hipLaunchKernelGGL(oz_gemm16p_kernel, dim3(G), dim3(512), 0, s, g, (int)blocks, ctr);
-    }
+    // the tile counters (one per XCD list) sit behind the chunk's bad_col flags
+    int* ctr = v.bad_col + Mc256;
+    if (!(v.ctr_clean && *v.ctr_clean == ctr) && (e = hipMemsetAsync(ctr, 0, sizeof(int) * 8, s)) != hipSuccess) return e;
+    if (v.ctr_clean) *v.ctr_clean = nullptr;
+    if ((e = launch_oz_gemm(pl, v.KR, v.WR, v.U, Np256, Mc256, v.rblocks, v.w_plane, ctr, s)) != hipSuccess) return e;
     if (v.ev_gemm && (e = hipEventRecord(v.ev_gemm, s)) != hipSuccess) return e;
 
-    if (v.Vout) {
-        OzCrtVArgs c{};
-        c.U = v.U; c.Ti = g.Ti; c.sexp = v.sexp; c.sK = v.sK; c.bad_row = v.bad_row; c.bad_col = v.bad_col;
-        c.V = v.Vout; c.ldv = v.ldv; c.Mc = v.Mc; c.nvalid = v.nvalid; c.pl = pl;
-        c.rmode = v.rmode; c.rper = v.rper; c.rtg = v.ktg; c.r0 = v.r0; c.rpts = v.rpts;
-        c.ctr_reset = v.ctr_clean ? v.bad_col + Mc256 : nullptr;
-        hipLaunchKernelGGL(oz_crt_v_kernel, dim3((v.Mc + 255) / 256, v.Np / 128), dim3(256), 0, s, c);
-        e = hipGetLastError();
-        if (e == hipSuccess && v.ctr_clean) *v.ctr_clean = v.bad_col + Mc256;
-        return e;
-    }
-    OzCrtArgs c{};
-    c.U = v.U; c.Ti = g.Ti; c.sexp = v.sexp; c.sK = v.sK; c.bad_row = v.bad_row; c.bad_col = v.bad_col;
-    c.partial = v.partial; c.ldp = v.ldp; c.Mc = v.Mc; c.nvalid = v.nvalid < g.Ti * OZ_T ? v.nvalid : g.Ti * OZ_T; c.pl = pl;
+    if (!v.Vout && v.delta && !(v.rblocks > 0)) return hipErrorInvalidValue;
+    OzCrtLaunch c{};
+    c.plan = &pl; c.U = v.U; c.Ti = oz_gemm_row_blocks(Np256, v.rblocks); c.sexp = v.sexp; c.sK = v.sK; c.bad_row = v.bad_row; c.bad_col = v.bad_col;
+    c.Np = v.Np; c.Mc = v.Mc; c.nvalid = v.nvalid;
     c.rmode = v.rmode; c.rper = v.rper; c.rtg = v.ktg; c.r0 = v.r0; c.rpts = v.rpts;
-    c.ctr_reset = v.ctr_clean ? v.bad_col + Mc256 : nullptr;
-    const int tbs = 2 * g.Ti < v.Np / 128 ? 2 * g.Ti : v.Np / 128;      // 128-row blocks of partial
-    if (v.delta) {             // the guarded bound of a short plan
-        if (!(v.rblocks > 0) || v.rmode) return hipErrorInvalidValue;
-        c.delta = v.delta; c.shave = 1.0 - (double)(c.nvalid + 16) * 0x1p-52;
-        if (pl.n == 8) hipLaunchKernelGGL((oz_crt_kernel<8, true>), dim3((v.Mc + 255) / 256, tbs), dim3(256), 0, s, c);
-        else hipLaunchKernelGGL((oz_crt_kernel<0, true>), dim3((v.Mc + 255) / 256, tbs), dim3(256), 0, s, c);
-    } else if (pl.n == 14) hipLaunchKernelGGL(oz_crt_kernel<14>, dim3((v.Mc + 255) / 256, tbs), dim3(256), 0, s, c);
-    else hipLaunchKernelGGL(oz_crt_kernel<0>, dim3((v.Mc + 255) / 256, tbs), dim3(256), 0, s, c);
-    e = hipGetLastError();
-    if (e == hipSuccess && v.ctr_clean) *v.ctr_clean = v.bad_col + Mc256;
+    c.ctr_reset = v.ctr_clean ? ctr : nullptr;
+    c.delta = v.Vout ? nullptr : v.delta; c.partial = v.partial; c.ldp = v.ldp; c.V = v.Vout; c.ldv = v.ldv;
+    e = launch_oz_crt(c, s);
+    if (e == hipSuccess && v.ctr_clean) *v.ctr_clean = ctr;
     return e;
 }
 

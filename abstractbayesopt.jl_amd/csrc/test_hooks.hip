@@ -7,6 +7,7 @@
 #include <cstring>
 #include <vector>
 
+#include "abo_oz_dev.h"
 #include "abo_state.h"
 #include "kgen_core.h"
 
@@ -294,6 +295,141 @@ int32_t abo_test_oz_contract_bound(int32_t device, const double* W, int64_t ldw,
     oa.Np = Np; oa.Mc = Mc; oa.nvalid = nvalid; oa.sK = sKb; oa.rblocks = rblocks; oa.delta = delta; oa.w_plane = (int64_t)rows * q;
     HIPCHK(launch_var_ozaki(oa, nullptr));
     HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+// ---- the residue engine (csrc/ozaki.hip), stage by stage: every hook passes its arguments to ONE stage launcher on the null stream (the
+// ---- GEMM hook with launches = 2: GEMM, reconstruction, GEMM — the counter protocol of production) and decides nothing itself
+int32_t abo_test_oz_rowscale(int32_t device, const double* W, int64_t ldw, int32_t nrows, int32_t rows256, int32_t nmod, int32_t kper, int32_t ktg,
+                             int32_t kbits, int32_t g_eP_full, int32_t g_sK_b, int32_t g_sK_full, double g_kmax, double g_rec_b, double g_rec_full,
+                             int32_t* sexp, double* delta) {
+    if (!W || !sexp) return fail(ABO_EINVAL, "abo_test_oz_rowscale: null argument");
+    OzPlan pl;
+    if (!oz_make_plan(nmod, &pl)) return fail(ABO_EINVAL, "abo_test_oz_rowscale: %d moduli not supported (8 … %d)", nmod, OZ_MAXMOD);
+    if (rows256 <= 0 || rows256 % 256) return fail(ABO_EINVAL, "abo_test_oz_rowscale: rows256 must be a positive multiple of 256");
+    if (delta && kper != 1) return fail(ABO_EINVAL, "abo_test_oz_rowscale: the guard is for kper = 1 (the bound pass is StandardGP only)");
+    OzGuardArgs gd{};
+    gd.delta = delta; gd.eP_full = g_eP_full; gd.sK_b = g_sK_b; gd.sK_full = g_sK_full; gd.kmax = g_kmax; gd.rec_b = g_rec_b; gd.rec_full = g_rec_full;
+    HIPCHK(hipSetDevice(device));
+    const hipError_t e = launch_oz_rowscale(W, ldw, nrows, rows256, pl.eP, sexp, kper, ktg, kbits, gd, nullptr);
+    if (e == hipErrorInvalidValue)
+        return fail(ABO_EINVAL, "abo_test_oz_rowscale: launch_oz_rowscale refused nrows = %d, rows256 = %d, ldw = %lld, kper = %d, ktg = %d, kbits = %d (0 <= nrows <= rows256, ldw >= nrows, kper >= 1, -60 <= ktg <= 900, 2 <= kbits <= 53)",
+                    nrows, rows256, (long long)ldw, kper, ktg, kbits);
+    HIPCHK(e);
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_oz_quant(int32_t device, const abo_test_oz_quant_args* t) {
+    if (!t || !t->in || !t->out) return fail(ABO_EINVAL, "abo_test_oz_quant: null argument");
+    OzQuantArgs q{};
+    if (!oz_make_plan(t->nmod, &q.pl)) return fail(ABO_EINVAL, "abo_test_oz_quant: %d moduli not supported (8 … %d)", t->nmod, OZ_MAXMOD);
+    // what the layout asks of the caller's buffer: whole 256-row blocks, planes that do not overlap
+    if (t->rows_out <= 0 || t->rows_out % 256 || t->ld <= 0 || t->plane < (int64_t)t->rows_out * t->ld)
+        return fail(ABO_EINVAL, "abo_test_oz_quant: rows_out a positive multiple of 256, plane >= rows_out * ld");
+    q.in = t->in; q.ldin = t->ldin; q.rows_in = t->rows_in; q.cols_in = t->cols_in; q.rows_out = t->rows_out; q.cols_out = t->cols_out;
+    q.lower = t->lower; q.srow = t->srow; q.sconst = t->sconst; q.kper = t->kper; q.ktg = t->ktg; q.rmode = t->rmode; q.rper = t->rper;
+    q.rtg = t->rtg; q.r0 = t->r0; q.rpts = t->rpts; q.out = t->out; q.ld = t->ld; q.plane = t->plane; q.bad = t->bad;
+    HIPCHK(hipSetDevice(device));
+    const hipError_t e = launch_oz_quant(q, nullptr);
+    if (e == hipErrorInvalidValue)
+        return fail(ABO_EINVAL, "abo_test_oz_quant: launch_oz_quant refused rows %d of %d, cols %d of %d, ld = %lld, ldin = %lld, sconst = %d, ktg = %d, rtg = %d (cols_out a multiple of 16 and <= ld, ld of 64, rows_in <= rows_out, cols_in <= cols_out and ldin, scales inside the normal range)",
+                    t->rows_in, t->rows_out, t->cols_in, t->cols_out, (long long)t->ld, (long long)t->ldin, t->sconst, t->ktg, t->rtg);
+    HIPCHK(e);
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+// PRECONDITION of the kernel, not checked here: the planes of WR are lower-triangular (byte [i][k] = 0 for k > i) — the GEMM skips
+// the units of a diagonal block above the diagonal and stops each tile's k range at its diagonal block.  The bytes k >= 256·(row
+// blocks covered) of a row are never read.
+int32_t abo_test_oz_gemm(int32_t device, const int8_t* KR, const int8_t* WR, int32_t Np256, int32_t Mc256, int32_t nmod, int32_t rblocks,
+                         int64_t w_plane, int8_t* U, int32_t launches) {
+    if (!KR || !WR || !U) return fail(ABO_EINVAL, "abo_test_oz_gemm: null argument");
+    OzPlan pl;
+    if (!oz_make_plan(nmod, &pl)) return fail(ABO_EINVAL, "abo_test_oz_gemm: %d moduli not supported (8 … %d)", nmod, OZ_MAXMOD);
+    if (launches != 1 && launches != 2) return fail(ABO_EINVAL, "abo_test_oz_gemm: launches = 1 or 2");
+    if (Np256 <= 0 || Np256 % 256 || Mc256 <= 0 || Mc256 % 256 || rblocks < 0 || rblocks > Np256 / 256 ||
+        (w_plane != 0 && w_plane < (int64_t)256 * oz_gemm_row_blocks(Np256, rblocks) * Np256))
+        return fail(ABO_EINVAL, "abo_test_oz_gemm: Np256, Mc256 positive multiples of 256, 0 <= rblocks <= Np256 / 256, w_plane 0 or >= 256 * row blocks * Np256");
+    HIPCHK(hipSetDevice(device));
+    const int Ti = oz_gemm_row_blocks(Np256, rblocks);
+    // the counters behind Mc256 flag ints, as launch_var_ozaki places them; zeroed ONCE
+    ScratchBuf ints(device, nullptr), u1(device, nullptr), part(device, nullptr);
+    HIPCHK(ints.b.ensure(sizeof(int) * ((size_t)Mc256 + OZ_CTR_INTS + Np256)));
+    HIPCHK(hipMemsetAsync(ints.b.p, 0, sizeof(int) * ((size_t)Mc256 + OZ_CTR_INTS + Np256), nullptr));
+    int* ctr = ints.b.as<int>() + Mc256;
+    int8_t* first = U;
+    if (launches == 2) {
+        HIPCHK(u1.b.ensure((size_t)nmod * Ti * 256 * Mc256));
+        first = u1.b.as<int8_t>();
+    }
+    hipError_t e = launch_oz_gemm(pl, KR, WR, first, Np256, Mc256, rblocks, w_plane, ctr, nullptr);
+    if (e == hipErrorInvalidValue) return fail(ABO_EINVAL, "abo_test_oz_gemm: launch_oz_gemm refused Np256 = %d, Mc256 = %d, rblocks = %d", Np256, Mc256, rblocks);
+    HIPCHK(e);
+    if (launches == 2) {
+        // a reconstruction of the first launch's U into a throw-away buffer resets the counters (ctr_reset), as it does between two
+        // chunks of a posterior call; the second GEMM then runs WITHOUT a memset and writes the caller's U
+        HIPCHK(part.b.ensure(sizeof(double) * (size_t)(2 * Ti) * Mc256));
+        OzCrtLaunch c{};
+        c.plan = &pl; c.U = first; c.Ti = Ti; c.sexp = ctr + OZ_CTR_INTS; c.sK = 0; c.Np = 256 * Ti; c.Mc = Mc256; c.nvalid = 256 * Ti;
+        c.rper = 1; c.rpts = 1; c.ctr_reset = ctr; c.partial = part.b.as<double>(); c.ldp = Mc256;
+        HIPCHK(launch_oz_crt(c, nullptr));
+        HIPCHK(launch_oz_gemm(pl, KR, WR, U, Np256, Mc256, rblocks, w_plane, ctr, nullptr));
+    }
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_oz_crt(int32_t device, const int8_t* U, int32_t Ti, int32_t nmod, const int32_t* sexp, int32_t sK, const int32_t* bad_row,
+                        const int32_t* bad_col, int32_t Np, int32_t Mc, int32_t nvalid, int32_t rmode, int32_t rper, int32_t rtg, int64_t r0,
+                        int64_t rpts, const double* delta, double* partial, int64_t ldp, double* V, int64_t ldv, int32_t generic,
+                        int32_t* ctr_reset) {
+    if (!U || !sexp || (!partial && !V)) return fail(ABO_EINVAL, "abo_test_oz_crt: null argument");
+    OzPlan pl;
+    if (!oz_make_plan(nmod, &pl)) return fail(ABO_EINVAL, "abo_test_oz_crt: %d moduli not supported (8 … %d)", nmod, OZ_MAXMOD);
+    if (generic != 0 && generic != 1) return fail(ABO_EINVAL, "abo_test_oz_crt: generic = 0 or 1");
+    OzCrtLaunch c{};
+    c.plan = &pl; c.U = U; c.Ti = Ti; c.sexp = sexp; c.sK = sK; c.bad_row = bad_row; c.bad_col = bad_col; c.Np = Np; c.Mc = Mc; c.nvalid = nvalid;
+    c.rmode = rmode; c.rper = rper; c.rtg = rtg; c.r0 = r0; c.rpts = rpts; c.ctr_reset = ctr_reset; c.delta = delta; c.partial = partial; c.ldp = ldp;
+    c.V = V; c.ldv = ldv; c.generic = generic;
+    HIPCHK(hipSetDevice(device));
+    const hipError_t e = launch_oz_crt(c, nullptr);
+    if (e == hipErrorInvalidValue)
+        return fail(ABO_EINVAL, "abo_test_oz_crt: launch_oz_crt refused Ti = %d, Np = %d, Mc = %d, nvalid = %d, rmode = %d (Np, Mc positive multiples of 128, 0 <= nvalid <= Np, ldp >= Mc; V: ldv >= nvalid, nvalid <= 256 Ti, no delta; delta: rmode 0)",
+                    Ti, Np, Mc, nvalid, rmode);
+    HIPCHK(e);
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+// oz_mod_pack4_mad on quads of integers: packed[i] = the four residue bytes of x[4i .. 4i+3] modulo p_l (l uniform: the asm takes −p
+// from a scalar register, as the GEMM's epilogue does)
+__global__ void __launch_bounds__(256) oz_modpack_test_kernel(const int* __restrict__ x, int64_t n4, double invp, int p, int* __restrict__ packed) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n4) return;
+    const int pu = __builtin_amdgcn_readfirstlane(p);
+    packed[i] = oz_mod_pack4_mad(x[4 * i], x[4 * i + 1], x[4 * i + 2], x[4 * i + 3], invp, pu);
+}
+
+int32_t abo_test_oz_modpack(int32_t device, const int32_t* x, int64_t n4, int32_t l, int32_t* packed) {
+    if (!x || !packed) return fail(ABO_EINVAL, "abo_test_oz_modpack: null argument");
+    if (n4 < 0 || n4 > ((int64_t)1 << 28) || l < 0 || l >= OZ_MAXMOD) return fail(ABO_EINVAL, "abo_test_oz_modpack: 0 <= n4 <= 2^28, 0 <= l < %d", OZ_MAXMOD);
+    if (n4 == 0) return ABO_OK;
+    OzPlan pl;
+    if (!oz_make_plan(OZ_MAXMOD, &pl)) return fail(ABO_EINVAL, "abo_test_oz_modpack: no plan");
+    HIPCHK(hipSetDevice(device));
+    hipLaunchKernelGGL(oz_modpack_test_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, nullptr, x, n4, pl.invp[l], pl.p[l], packed);
+    HIPCHK(hipGetLastError());
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_oz_tickets(int32_t Ti, int32_t Tj, int32_t nmod, int32_t* tiles, int64_t* count) {
+    if (!count) return fail(ABO_EINVAL, "abo_test_oz_tickets: null argument");
+    const int64_t blocks = oz_gemm_tickets(Ti, Tj, nmod, tiles);
+    if (blocks < 0) return fail(ABO_EINVAL, "abo_test_oz_tickets: launch_oz_gemm refuses Ti = %d, Tj = %d, nmod = %d (1 <= Ti <= 256, 1 <= Tj <= 2047, 1 <= nmod <= %d)", Ti, Tj, nmod, OZ_MAXMOD);
+    *count = blocks;
     return ABO_OK;
 }
 

@@ -1082,6 +1082,49 @@ int32_t abo_test_pick_record(int32_t device, const double* tv, const int64_t* ti
                              int32_t d, double* rec);
 /* launch_score: score[j] = the epilogue `kind` at (mu[j], var[j]) by the plain scoring kernel — what finalize's score is held against */
 int32_t abo_test_score(int32_t device, const double* mu, const double* var, double* score, int64_t M, int32_t kind, double p0, double best_y);
+/* --- the int8 residue engine (csrc/ozaki.hip), stage by stage ---
+ * Every pointer is DEVICE memory unless stated otherwise.  Each hook hands its arguments to ONE stage launcher (launch_oz_rowscale,
+ * launch_oz_quant, launch_oz_gemm, launch_oz_crt) on the null stream and waits; ABO_EINVAL, and no launch, for what the launcher
+ * cannot take.  Layouts: a residue plane is blocks of 256 rows x 64 k-bytes (oz_plane_off), U blocks of one 256 x 256 tile and
+ * modulus (oz_u_block); tests/oz_ref.py packs and unpacks both.
+ * Row scales: sexp[0 .. rows256) of the first nrows rows of the lower-triangular W [nrows][ldw] under the nmod-modulus plan and
+ * kbits bits of K; columns k % kper != 0 weighted by 2^ktg.  delta non-null: the guard of a short plan from the g_* fields (OzGuardArgs:
+ * eP and sK of the full plan, sK of the short one, kmax, the two reconstruction bounds); kper = 1 then. */
+int32_t abo_test_oz_rowscale(int32_t device, const double* W, int64_t ldw, int32_t nrows, int32_t rows256, int32_t nmod, int32_t kper, int32_t ktg,
+                             int32_t kbits, int32_t g_eP_full, int32_t g_sK_b, int32_t g_sK_full, double g_kmax, double g_rec_b, double g_rec_full,
+                             int32_t* sexp, double* delta);
+/* oz_quant_kernel with every field of OzQuantArgs but the plan (nmod in its place): out = nmod planes, `plane` bytes apart, of
+ * rows_out (a multiple of 256) rows with ld bytes each, of which cols_out are written: residues of rint(in * 2^s) for r < rows_in,
+ * k < cols_in (lower: k <= r), zeros elsewhere; s = srow[r] when given, else sconst; bad[r] = 1 for rows holding a value that is not
+ * below 1e300 (never cleared here). */
+typedef struct abo_test_oz_quant_args {
+    const double* in; int64_t ldin;
+    int32_t rows_in, cols_in, rows_out, cols_out, lower, sconst;
+    const int32_t* srow;
+    int32_t kper, ktg, rmode, rper, rtg, nmod;
+    int64_t r0, rpts;
+    int8_t* out; int64_t ld, plane;
+    int32_t* bad;
+} abo_test_oz_quant_args;
+int32_t abo_test_oz_quant(int32_t device, const abo_test_oz_quant_args* args);
+/* the persistent residue GEMM on given planes: KR [nmod][Mc256][Np256], WR [nmod][.][Np256] with w_plane bytes between planes (0:
+ * Np256^2) -> U for the first rblocks (0: all) 256-row blocks.  PRECONDITION (not checked): WR is lower-triangular.  The tile counters
+ * are the hook's, behind Mc256 flag ints as in production, zeroed once.  launches = 2: GEMM into a scratch U, a reconstruction of it
+ * into a throw-away buffer (which resets the counters), and the GEMM again WITHOUT a memset, into U. */
+int32_t abo_test_oz_gemm(int32_t device, const int8_t* KR, const int8_t* WR, int32_t Np256, int32_t Mc256, int32_t nmod, int32_t rblocks,
+                         int64_t w_plane, int8_t* U, int32_t launches);
+/* the reconstruction of U (Ti row blocks): V non-null -> V [Mc][ldv] itself (oz_crt_v_kernel), else partial [Np/128][ldp], the column
+ * sums of squares per 128-row block — guarded when delta is given.  nmod 14 and 8 run the compile-time forms unless generic = 1.
+ * ctr_reset (or null): 8 ints the kernel zeroes. */
+int32_t abo_test_oz_crt(int32_t device, const int8_t* U, int32_t Ti, int32_t nmod, const int32_t* sexp, int32_t sK, const int32_t* bad_row,
+                        const int32_t* bad_col, int32_t Np, int32_t Mc, int32_t nvalid, int32_t rmode, int32_t rper, int32_t rtg, int64_t r0,
+                        int64_t rpts, const double* delta, double* partial, int64_t ldp, double* V, int64_t ldv, int32_t generic,
+                        int32_t* ctr_reset);
+/* the GEMM epilogue's residue arithmetic (oz_mod_pack4_mad) on quads: packed[i] = the bytes of x[4i .. 4i+3] mod the l-th modulus */
+int32_t abo_test_oz_modpack(int32_t device, const int32_t* x, int64_t n4, int32_t l, int32_t* packed);
+/* HOST only, no device: the tile list of a residue GEMM over Ti x Tj tiles and nmod moduli as the kernel decodes it: *count = 8 * per_list
+ * (the launcher's `blocks`), tiles[y * per_list + q] = ti | tj << 9 | l << 20, or -1 for a padding block (tiles may be null) */
+int32_t abo_test_oz_tickets(int32_t Ti, int32_t Tj, int32_t nmod, int32_t* tiles, int64_t* count);
 #endif /* ABO_TEST_HOOKS */
 
 #ifdef __cplusplus

@@ -51,7 +51,9 @@ def test_shipped_library_exports_the_documented_surface_and_nothing_else():
     # … and those of the selection family
     for h in ("abo_test_kgen", "abo_test_cand_newcol", "abo_test_topk_plan", "abo_test_topk", "abo_test_prune_compact",
               "abo_test_prune_min_scatter", "abo_test_prune_map", "abo_test_finalize", "abo_test_cand_gemv", "abo_test_downdate",
-              "abo_test_grad_cov", "abo_test_gather_points", "abo_test_pick_record", "abo_test_score"):
+              "abo_test_grad_cov", "abo_test_gather_points", "abo_test_pick_record", "abo_test_score",
+              # … and those of the residue engine's stages
+              "abo_test_oz_rowscale", "abo_test_oz_quant", "abo_test_oz_gemm", "abo_test_oz_crt", "abo_test_oz_modpack", "abo_test_oz_tickets"):
         assert h in hooks and h in abo._lib.TEST_EXPORTS and h not in syms
     out_t = subprocess.run(["nm", "-D", "--defined-only", abo._lib.LIB_TEST_PATH], capture_output=True, text=True, check=True).stdout
     syms_t = {ln.split()[-1] for ln in out_t.splitlines() if ln.strip()}
