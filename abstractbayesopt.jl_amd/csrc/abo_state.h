@@ -141,6 +141,8 @@ inline void storage_unref(Storage* st) {
 //   cov_Zs, cov_V, cov_C         abo_predict_cov: the scaled points of both sets, V_a / V_b = K_ZX·L⁻ᵀ, the padded covariance block
 //   pr_head … pr_hdl             the fused first-level head (kgen_head32.hip): head of μ̃ and S̃ of every candidate, fp32 fragments of
 //                                W's head, δ and ‖W_i‖₁
+//   pr_ti0                       the K0 candidates of the threshold pass, in the order of their exact scores in pr_sc (pr_ti is
+//                                overwritten by the threshold's own selection)
 #define ABO_GP_BUFS(X)                                                                                                              \
     X(alpha) X(vext) X(tvec) X(T) X(info) X(scal)                                                                                   \
     X(Zdev) X(Kxz) X(partial) X(mu_c) X(mu_all) X(var_all) X(score_all) X(tk_keys0) X(tk_keys1) X(tk_idx0) X(tk_idx1) X(top_val) X(top_idx) \
@@ -148,7 +150,7 @@ inline void storage_unref(Storage* st) {
     X(pr_ub) X(pr_z) X(pr_sc) X(pr_sel) X(pr_blk) X(pr_tv) X(pr_ti)                                                                 \
     X(pr_mut) X(pr_eps) X(pr_nrm) X(pr_ub2) X(pr_mut2) X(pr_eps2)                                                                   \
     X(ystar) X(oz_WRb) X(oz_sexpb) X(oz_badrb) X(oz_delta) X(loo_T) X(cov_Zs) X(cov_V) X(cov_C)                                     \
-    X(pr_head) X(pr_ssq) X(pr_wf) X(pr_hdl)
+    X(pr_head) X(pr_ssq) X(pr_wf) X(pr_hdl) X(pr_ti0)
 
 struct abo_gp {
     std::atomic<int> refs{1};
@@ -190,9 +192,11 @@ struct abo_gp {
     // the posterior passes of the current call, in launch order (their per-chunk events are read back with them): the pruned top-k
     // selection of abo_acq runs up to five (two bound levels, threshold, survivors or the fallback's full pass), everything else one
     struct PostPass { int64_t chunk0, nchunk, M, rows; int nmod; bool head32 = false; };   // first chunk's event slot, chunks, candidate rows, rows of W contracted, moduli launched
+                                                                                       // (nchunk = 0: nothing was launched — the survivors whose scores came from the threshold pass, counted in the work figures alone)
                                                                                        // (0 and head32: the fused fp32 head of a first bound level, one launch, timed in its first chunk's contraction slot)
     std::vector<PostPass> passes;
     int ph_rows = 0;                                           // rows of the last fused head (0: the last bound pass ran none)
+    bool pr_reused = false;                                    // the last abo_acq took its survivors' scores from its threshold pass (abo_test_prune_reused)
     abo_prune_stats pst{};
     struct PruneLevels { int64_t rows1, s1, rows2, s2; double ms1, ms2; } plv{};      // abo_get_prune_levels
     abo::OzPlan oz_plan_b{};                                   // the bound pass's short residue plan
@@ -239,8 +243,15 @@ struct PrunePlan {
     int64_t level2_min;     // the pass at rblocks runs on the first level's survivors when there are more than this many
     bool tail32;            // the first level's tail of the mean in fp32 (kgen_tail32.hip); nothing without a first level
     bool head32;            // … and its head — head of the mean, guarded sum of squares — by the fused fp32-MFMA kernel (kgen_head32.hip)
+    bool reuse;             // survivors that the threshold pass has scored (S ≤ K0, no second level) are not evaluated again
 };
 PrunePlan prune_plan(int64_t rows, int64_t M, int k, bool want_scores, int kind, double p0, int p_out, bool int8_fused, int d);
+// misc.hip: sc[p] = sc0[q] for the q with idx0[q] == sel[p], p < S = *count (device) — the exact scores of the survivors out of those
+// of the threshold pass's K0 candidates; nothing for S > K0; a survivor that is not among the K0 gets NaN and sets *missing (preset to
+// 0 by the caller) to 1.  K0 ≤ PRUNE_REUSE_SLOTS / 2.
+constexpr int PRUNE_REUSE_SLOTS = 8192;         // ints of LDS (32 KiB): K0 ≤ 4096
+hipError_t launch_prune_reuse_scores(const int64_t* sel, const int64_t* count, const int64_t* idx0, const double* sc0, int64_t K0, double* sc,
+                                     int64_t* missing, hipStream_t s);
 // Overrides of the pruned selection's decisions, "not set" by default and for ever in the shipped library: nothing there writes them, so
 // every decision is what the environment and the defaults give.  The abo_test_prune_* hooks (test_hooks.hip) are their only writers.
 extern std::atomic<int> g_prune_bound_moduli;       // abo_test_prune_bound_moduli: 0 = the environment's / the default
@@ -249,6 +260,7 @@ extern std::atomic<int> g_prune_force_mode;         // of −Inf (every candidat
 extern std::atomic<int> g_prune_pre_rblocks;        // abo_test_prune_levels: row blocks of the first level (−1 = none, 0 = the rule)
 extern std::atomic<int64_t> g_prune_level2_min;     // … and the survivor count above which the second runs (−1 = the rule)
 extern std::atomic<int> g_prune_tail32;             // abo_test_prune_tail32: 0 / 1 = the first level's tail in fp64 / fp32, −1 = the environment's
+extern std::atomic<int> g_prune_reuse;              // abo_test_prune_reuse: 0 / 1 = survivors always evaluated / taken from the threshold pass where it holds them, −1 = the environment's
 extern std::atomic<int> g_prune_head32;             // abo_test_prune_head32: 0 / 1 = the first level's head on the int8 engine / fused in fp32, −1 = the environment's
 
 // ---- the blocked factorisation on raw pointers (api.hip: factorise runs exactly these two, with the default blocking) -----------------

@@ -1014,7 +1014,8 @@ int32_t grad_eval_device(abo_gp* g, const double* Zd, int64_t M, double beta, do
 }
 
 // phase times and algorithmic work of the call's posterior passes (what was launched: a bound pass counts its R rows, a survivor pass
-// its survivors)
+// its survivors — with ONE exception: survivors whose scores were taken from the threshold pass, prune_select step 4, are counted as if
+// their pass had been launched; the pass of no chunks that stands for them adds work and no time)
 void collect_posterior_timings(abo_gp* g, bool with_var) {
     double kx = 0, vg = 0, fi = 0, oq = 0, og = 0, oc = 0, work = 0, ozops = 0;
     const bool oz = with_var && g->tm.contraction_engine == ABO_CONTRACT_INT8;
@@ -1869,6 +1870,7 @@ std::atomic<int> g_prune_pre_rblocks{0};
 std::atomic<int64_t> g_prune_level2_min{-1};
 std::atomic<int> g_prune_tail32{-1};
 std::atomic<int> g_prune_head32{-1};
+std::atomic<int> g_prune_reuse{-1};
 }  // namespace abo
 
 namespace {
@@ -1878,6 +1880,14 @@ namespace {
 bool prune_tail32() {
     static const bool on = [] { const char* e = getenv("ABO_PRUNE_TAIL32"); return !(e && e[0] == '0'); }();
     if (g_prune_tail32.load(std::memory_order_relaxed) >= 0) return g_prune_tail32.load(std::memory_order_relaxed) != 0;
+    return on;
+}
+
+// Survivors that the threshold pass has scored are not evaluated again (prune_select, step 4).  ABO_PRUNE_REUSE=0 (read once) runs the
+// survivor pass on them as before, for A/B runs.
+bool prune_reuse() {
+    static const bool on = [] { const char* e = getenv("ABO_PRUNE_REUSE"); return !(e && e[0] == '0'); }();
+    if (g_prune_reuse.load(std::memory_order_relaxed) >= 0) return g_prune_reuse.load(std::memory_order_relaxed) != 0;
     return on;
 }
 
@@ -1931,6 +1941,7 @@ PrunePlan prune_plan(int64_t rows, int64_t M, int k, bool want_scores, int kind,
     pp.rblocks0 = rb0;
     pp.tail32 = rb0 > 0 && prune_tail32();
     pp.head32 = pp.tail32 && prune_head32();
+    pp.reuse = prune_reuse();
     pp.k0 = k > 0 ? ((int64_t)4 * k > 1024 ? (int64_t)4 * k : 1024) : 0;
     // below 4·K0 survivors the full pass on them costs less than the ≈ 16 launches of another bound pass
     pp.level2_min = 4 * pp.k0;
@@ -1962,11 +1973,13 @@ int32_t prune_select(abo_gp* g, const double* Zd, int64_t M, const AcqTerms& t, 
     const int64_t nb = (M + PRUNE_SCAN_E - 1) / PRUNE_SCAN_E;
     HIPCHK(g->pr_ub.ensure(sizeof(double) * M));
     HIPCHK(g->pr_z.ensure(sizeof(double) * K0 * d));
-    HIPCHK(g->pr_sc.ensure(sizeof(double) * K0));
+    HIPCHK(g->pr_sc.ensure(sizeof(double) * 2 * K0));            // the threshold pass's scores, then those of ≤ K0 survivors taken from them
     HIPCHK(g->pr_sel.ensure(sizeof(int64_t) * M));
     HIPCHK(g->pr_blk.ensure(sizeof(int) * nb + 16));
-    HIPCHK(g->pr_tv.ensure(sizeof(double) * (K0 + 2)));          // K0 values, then {survivor count, −Inf (test hook)}
+    HIPCHK(g->pr_tv.ensure(sizeof(double) * (K0 + 3)));          // K0 values, then {survivor count, −Inf (test hook), the reuse's "not found" flag}
     HIPCHK(g->pr_ti.ensure(sizeof(int64_t) * K0));
+    HIPCHK(g->pr_ti0.ensure(sizeof(int64_t) * K0));              // the threshold pass's K0 candidates
+    g->pr_reused = false;
     double* ub = g->pr_ub.as<double>();
     int64_t* count_d = reinterpret_cast<int64_t*>(g->pr_tv.as<double>() + K0);
     HIPCHK(g->events(EV_BASE));
@@ -1990,6 +2003,8 @@ int32_t prune_select(abo_gp* g, const double* Zd, int64_t M, const AcqTerms& t, 
     further.more = true;
     rc = posterior(g, g->pr_z.as<double>(), K0, kind, p0, best_y, nullptr, nullptr, g->pr_sc.as<double>(), further);
     if (rc) return rc;
+    // (the selection below overwrites pr_ti: the candidates that pr_sc's scores belong to are kept for step 4)
+    if (pp.reuse) HIPCHK(hipMemcpyAsync(g->pr_ti0.p, g->pr_ti.p, sizeof(int64_t) * K0, hipMemcpyDeviceToDevice, s));
     HIPCHK(launch_topk(g->pr_sc.as<double>(), K0, k, 0, w, g->pr_tv.as<double>(), g->pr_ti.as<int64_t>(), s));
     const double* tau = g->pr_tv.as<double>() + (k - 1);
     if (g_prune_force_mode.load(std::memory_order_relaxed) == 1) {
@@ -2001,9 +2016,19 @@ int32_t prune_select(abo_gp* g, const double* Zd, int64_t M, const AcqTerms& t, 
     HIPCHK(launch_prune_compact(ub, M, tau, kind == ABO_ACQ_LOGEI ? PRUNE_ABS_LOGEI : PRUNE_ABS, g->pr_blk.as<int>(), g->pr_sel.as<int64_t>(),
                                 count_d, s));
     HIPCHK(hipEventRecord(g->evs()[PE + 2], s));
-    int64_t S = 0;
-    HIPCHK(hipMemcpyAsync(&S, count_d, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    // (step 4's lookup, ahead of the count's way to the host: the kernel reads the count itself and does nothing for more than K0
+    // survivors, and its "not found" flag comes back with the count — no synchronisation of its own)
+    const bool try_reuse = pp.reuse && 2 * K0 <= PRUNE_REUSE_SLOTS;
+    if (try_reuse) {
+        HIPCHK(hipMemsetAsync(count_d + 2, 0, sizeof(int64_t), s));
+        HIPCHK(launch_prune_reuse_scores(g->pr_sel.as<int64_t>(), count_d, g->pr_ti0.as<int64_t>(), g->pr_sc.as<double>(), K0,
+                                         g->pr_sc.as<double>() + K0, count_d + 2, s));
+    }
+    int64_t back[3] = {0, 0, 0};          // survivor count, (the hook's threshold), not found
+    HIPCHK(hipMemcpyAsync(back, count_d, sizeof(int64_t) * (try_reuse ? 3 : 1), hipMemcpyDeviceToHost, s));
     HIPCHK(wait_stream(s));
+    int64_t S = back[0];
+    const bool not_found = back[2] != 0;
     // 3b. second level: the bound pass at rblocks on the first level's survivors, against the SAME τ (the k-th best exact score of any
     // subset is a valid threshold).  ub keeps min(level 1, level 2) — still an upper bound for every one of the M candidates — and is
     // compacted again over all M (8 bytes a candidate: cheaper than a second index map), so the list stays in index order.
@@ -2033,14 +2058,35 @@ int32_t prune_select(abo_gp* g, const double* Zd, int64_t M, const AcqTerms& t, 
     }
     g->pst.survivors = S;
     if (S < k || S > pp.max_survivors) { g->pst.fallback = 1; return ABO_OK; }
-    HIPCHK(g->pr_z.ensure(sizeof(double) * S * d));
-    HIPCHK(g->pr_sc.ensure(sizeof(double) * S));
-    HIPCHK(launch_gather_points(Zd, g->pr_sel.as<int64_t>(), 0, (int)S, d, g->pr_z.as<double>(), s));
-    rc = posterior(g, g->pr_z.as<double>(), S, kind, p0, best_y, nullptr, nullptr, g->pr_sc.as<double>(), further);
-    if (rc) return rc;
-    PHASE_EVENT(g->evs()[6], s);
-    // 4. the selection among the exactly evaluated: list positions are in index order, so ties fall as they do over all M
-    HIPCHK(launch_topk(g->pr_sc.as<double>(), S, k, 0, w, tv, ti, s));
+    // 4. exact scores of the survivors, in list order.  With no second level and S ≤ K0 the threshold pass has scored nearly always all
+    // of them: a survivor kept because its bound reaches τ ranks, by bound, ahead of every candidate that does not, so were it outside
+    // the K0 best by bound, all K0 of them would survive too, S ≥ K0 + 1; NaN bounds are kept and rank first.  The exception is a stored
+    // bound of −Inf (LogEI where the bound's variance is ≤ 1e-12 and Δ ≤ 0): its guard is −Inf + Inf = NaN, so it is kept, yet it ranks
+    // LAST by bound and need not be among the K0.  So the argument is not relied on: the lookup above reports every survivor it did not
+    // find, and such a call runs the survivor pass as before.  An exact score does not depend on the batch a candidate is evaluated in
+    // (DESIGN §3b-1), so a score that was found is the bits a pass over the survivors would give.  (After a second level the list is
+    // a subset of the first level's, whose lookup is void: the survivor pass runs.)
+    const bool reuse = try_reuse && g->plv.rows2 == 0 && S <= K0 && !not_found;
+    if (reuse) {
+        double* sc0 = g->pr_sc.as<double>();           // K0 scores in the order of pr_ti0; the survivors' behind them
+        PHASE_EVENT(g->evs()[6], s);
+        HIPCHK(launch_topk(sc0 + K0, S, k, 0, w, tv, ti, s));
+        g->pr_reused = true;
+        // The call's work figures (var_gemm_flop, oz_gemm_ops) stay those of the selection as an algorithm — bound pass, K0 threshold
+        // candidates, S survivors — as tests/test_gpu_kgen_head32.py holds them: a pass of no chunks stands for the survivors.  No time
+        // is booked against it, so a rate taken from these figures (the benchmark's residue-GEMM rate among them) credits a reusing
+        // call with S/(K0 + S) of exact evaluations it did not launch (DESIGN §3b-1 says so where it gives the figures).
+        g->passes.push_back({g->passes.back().chunk0 + g->passes.back().nchunk, 0, S, g->N, g->oz_plan.n, false});
+    } else {
+        HIPCHK(g->pr_z.ensure(sizeof(double) * S * d));
+        HIPCHK(g->pr_sc.ensure(sizeof(double) * S));
+        HIPCHK(launch_gather_points(Zd, g->pr_sel.as<int64_t>(), 0, (int)S, d, g->pr_z.as<double>(), s));
+        rc = posterior(g, g->pr_z.as<double>(), S, kind, p0, best_y, nullptr, nullptr, g->pr_sc.as<double>(), further);
+        if (rc) return rc;
+        PHASE_EVENT(g->evs()[6], s);
+        // the selection among the exactly evaluated: list positions are in index order, so ties fall as they do over all M
+        HIPCHK(launch_topk(g->pr_sc.as<double>(), S, k, 0, w, tv, ti, s));
+    }
     HIPCHK(launch_prune_map(ti, k, g->pr_sel.as<int64_t>(), idx_base, s));
     HIPCHK(hipEventRecord(g->evs()[PE + 3], s));
     g->pst.pruned = 1;
@@ -2062,6 +2108,7 @@ int32_t acq_terms_impl(abo_gp* g, const double* Z, int64_t M, int32_t d, int32_t
     const bool fused_timings = !terms_have_gradnorm(t);           // the slab path does not keep per-chunk events
     g->pst = abo_prune_stats{};
     g->plv = abo_gp::PruneLevels{};
+    g->pr_reused = false;
     PrunePlan pp{false, 0, 0, 0, 0, 0};
     if (M > 0 && terms_plain(t)) {
         int nm = 0;

@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include "../../include/abo_hip.h"
 #include "abo_acq_dev.h"
+#include "abo_state.h"          // launch_prune_reuse_scores
 
 namespace abo {
 
@@ -895,6 +896,51 @@ __global__ void prune_map_kernel(int64_t* top_idx, int k, const int64_t* sel, in
 hipError_t launch_prune_map(int64_t* top_idx, int k, const int64_t* sel, int64_t idx_base, hipStream_t s) {
     if (k <= 0) return hipSuccess;
     hipLaunchKernelGGL(prune_map_kernel, dim3((k + 255) / 256), dim3(256), 0, s, top_idx, k, sel, idx_base);
+    return hipGetLastError();
+}
+
+// The survivors' exact scores out of the threshold pass's (api.hip: prune_select).  idx0[q], q < K0, are the K0 best candidates by
+// bound — distinct, in no particular order — and sc0[q] their exact scores; sel[p], p < S = *count, the survivors in index order; more
+// than K0 survivors: nothing is done.  A survivor whose bound reaches τ is among the K0 whenever S ≤ K0 — by bound it ranks ahead of
+// every candidate that is not kept, so outside the K0 best it would make all K0 of them survivors, S ≥ K0 + 1 — and so is one with a
+// NaN bound (kept, first in the selection's order); one with a stored bound of −Inf is kept as well (its guard is NaN: prune_keep)
+// but ranks last and need not be.  A survivor that is not found gets NaN and raises *missing: the caller then evaluates the survivors.
+// One workgroup: the K0 indices go into an open-addressing table in LDS (2·K0 slots rounded up to a power of two, so never full),
+// each thread then looks its survivors up.
+__device__ __forceinline__ unsigned prune_reuse_hash(int64_t j, unsigned mask) {
+    return (unsigned)(((uint64_t)j * 0x9E3779B97F4A7C15ull) >> 40) & mask;
+}
+
+__global__ void __launch_bounds__(1024) prune_reuse_kernel(const int64_t* __restrict__ sel, const int64_t* __restrict__ count,
+                                                           const int64_t* __restrict__ idx0, const double* __restrict__ sc0, int K0,
+                                                           unsigned mask, double* __restrict__ sc, int64_t* __restrict__ missing) {
+    __shared__ int slot[PRUNE_REUSE_SLOTS];          // position q in idx0 / sc0, −1 = empty
+    const int64_t S64 = count[0];
+    if (S64 <= 0 || S64 > K0) return;                // (uniform)
+    const int S = (int)S64;
+    for (unsigned e = threadIdx.x; e <= mask; e += blockDim.x) slot[e] = -1;
+    __syncthreads();
+    for (int q = threadIdx.x; q < K0; q += blockDim.x) {
+        unsigned h = prune_reuse_hash(idx0[q], mask);
+        while (atomicCAS(&slot[h], -1, q) != -1) h = (h + 1) & mask;
+    }
+    __syncthreads();
+    for (int p = threadIdx.x; p < S; p += blockDim.x) {
+        const int64_t j = sel[p];
+        unsigned h = prune_reuse_hash(j, mask);
+        int q = slot[h];
+        while (q >= 0 && idx0[q] != j) { h = (h + 1) & mask; q = slot[h]; }
+        if (q >= 0) sc[p] = sc0[q];
+        else { sc[p] = __builtin_nan(""); missing[0] = 1; }
+    }
+}
+
+hipError_t launch_prune_reuse_scores(const int64_t* sel, const int64_t* count, const int64_t* idx0, const double* sc0, int64_t K0, double* sc,
+                                     int64_t* missing, hipStream_t s) {
+    if (K0 <= 0 || 2 * K0 > PRUNE_REUSE_SLOTS) return hipErrorInvalidValue;
+    unsigned slots = 64;
+    while ((int64_t)slots < 2 * K0) slots <<= 1;
+    hipLaunchKernelGGL(prune_reuse_kernel, dim3(1), dim3(1024), 0, s, sel, count, idx0, sc0, (int)K0, slots - 1, sc, missing);
     return hipGetLastError();
 }
 

@@ -117,6 +117,18 @@ int32_t abo_test_prune_tail32(int32_t mode) {
     return ABO_OK;
 }
 
+int32_t abo_test_prune_reuse(int32_t mode) {
+    if (mode < -1 || mode > 1) return fail(ABO_EINVAL, "abo_test_prune_reuse: mode = %d (-1 = the environment's, 0 = survivors evaluated again, 1 = taken from the threshold pass)", mode);
+    g_prune_reuse.store(mode);
+    return ABO_OK;
+}
+
+int32_t abo_test_prune_reused(abo_gp* g, int32_t* out) {
+    if (!g || !out) return fail(ABO_EINVAL, "abo_test_prune_reused: null argument");
+    *out = g->pr_reused ? 1 : 0;
+    return ABO_OK;
+}
+
 int32_t abo_test_prune_head32(int32_t mode) {
     if (mode < -1 || mode > 1) return fail(ABO_EINVAL, "abo_test_prune_head32: mode = %d (-1 = the environment's, 0 = int8 head, 1 = fused fp32 head)", mode);
     g_prune_head32.store(mode);

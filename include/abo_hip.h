@@ -861,6 +861,11 @@ int32_t abo_test_prune_levels(int32_t pre_rblocks, int64_t level2_min);
 /* The tail of the mean in the FIRST bound level (csrc/kgen_tail32.hip), process-wide: 1 = in fp32, 0 = in fp64 as every other bound
  * pass has it (ABO_PRUNE_TAIL32=0), −1 restores the environment's choice.  Nothing in a call without a first level. */
 int32_t abo_test_prune_tail32(int32_t mode);
+/* Survivors that the threshold pass has already scored (no second level ran, k ≤ S ≤ K₀), process-wide: 1 = their scores are taken from
+ * that pass, 0 = the survivor pass evaluates them again (ABO_PRUNE_REUSE=0), −1 restores the environment's choice. */
+int32_t abo_test_prune_reuse(int32_t mode);
+/* *out = 1 when the last abo_acq on this handle took its survivors' scores from its threshold pass, else 0. */
+int32_t abo_test_prune_reused(abo_gp* g, int32_t* out);
 /* The HEAD of that first level (csrc/kgen_head32.hip), process-wide: 1 = head of the mean and guarded sum of squares by the fused
  * fp32-MFMA kernel, 0 = on the int8 engine (ABO_PRUNE_HEAD32=0), −1 restores the environment's choice.  The fused head runs only where
  * the fp32 tail does, and never under an explicit moduli request (ABO_PRUNE_BOUND_MODULI, abo_test_prune_bound_moduli != 0). */
