@@ -606,7 +606,7 @@ constexpr int MAX_TERMS = 8;
 constexpr int ACQ_GRADNORM_UCB = 4;            // == ABO_ACQ_GRADNORM_UCB (include/abo_hip.h)
 constexpr int ACQ_LOGEI = 5;                   // == ABO_ACQ_LOGEI
 // max-value entropy search (== ABO_ACQ_MES): the one epilogue whose parameter is a VECTOR, the samples y*₀ … y*_{S−1} of the minimum
-// value, so it is no kind of the scalar entry points (plain_kind) and no member of an ensemble (api.hip: make_terms): an objective is
+// value, so it is no kind of the scalar entry points (plain_kind) and no member of an ensemble (acq.hip: make_terms): an objective is
 // MES exactly when it is the single term built by the abo_*_mes entry points (terms_mes)
 constexpr int ACQ_MES = 6;
 constexpr int MES_MAX_SAMPLES = 1024;          // 8 KiB of LDS in the scoring kernel
@@ -665,7 +665,7 @@ size_t refine_lockstep_bytes(int S, int Np, int d, int history);
 hipError_t launch_refine_lockstep(const RefineArgs& a, int S, void* work, hipStream_t s);
 // Gradient-enhanced models (and any objective with a GRADNORM_UCB term): the same lockstep state machine, a round's evaluations
 // delivered by the caller.  eval(points [npts][d] (device), npts, mu [npts][p], cov [npts][p][p]) queues the all-output posterior of
-// the round's points on the stream (api.hip: the kernels behind abo_predict_grad_cov); the driver derives value and gradient of the
+// the round's points on the stream (posterior.hip: the kernels behind abo_predict_grad_cov); the driver derives value and gradient of the
 // objective from it — function-value terms analytically (∇μ = E[∇f] − m_∇, ∇σ² = 2·Cov(f, ∇f)), GRADNORM_UCB terms by central
 // differences over a 2d-point stencil evaluated in the same batch (the reference differentiates every objective that way,
 // acq_utils.jl:55-71).  p = d + 1 outputs; mean_g[d]: prior means of the gradient outputs.

@@ -1,11 +1,13 @@
-// Private state of the single-device host driver: what api.hip shares with test_hooks.hip — the handle struct with the types it is made
-// of, and the internal functions the abo_test_* hooks call.  Nothing else includes this header: mgpu.hip, update.hip, paths.hip and
+// Private state of the single-device host driver: what its units — api.hip, posterior.hip, acq.hip, and test_hooks.hip in the test
+// library — share: the handle struct with the types it is made of, the event slots of a handle, and the internal functions that are
+// called across a unit boundary or by the abo_test_* hooks.  Nothing else includes this header: mgpu.hip, update.hip, paths.hip and
 // qei_mc.hip see the handles through the accessors of abo_internal.h.  Declarations only: every variable and every function declared
-// here is defined once, in api.hip.
+// here is defined once, in the unit its comment names.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cstring>
 #include <mutex>
 #include <set>
 #include <vector>
@@ -21,6 +23,8 @@
             return fail(e_ == hipErrorOutOfMemory ? ABO_ENOMEM : ABO_EHIP, "%s failed: %s (%s:%d)", #expr, \
                         hipGetErrorString(e_), __FILE__, __LINE__);                                    \
     } while (0)
+// an event INSIDE a call (api.hip: phase_events says when these are recorded at all)
+#define PHASE_EVENT(ev, s) do { if (phase_events()) HIPCHK(hipEventRecord((ev), (s))); } while (0)
 
 struct abo_gp;
 struct abo_cand;
@@ -33,7 +37,37 @@ hipError_t wait_stream(hipStream_t s);                     // the polled wait ev
 extern std::atomic<uint64_t> g_storage_gen;                // next Storage::gen
 hipError_t pool_alloc(int dev, size_t bytes, void** p, size_t* cap);
 void pool_free(int dev, void* p, size_t cap);
-int32_t check_fitted(abo_gp* g, int32_t d);
+// api.hip — what every entry point of the three units starts and ends with
+int32_t check_fitted(abo_gp* g, int32_t d);                // also tells phase_events() the size of the model the calling thread works on
+int32_t stage_candidates(abo_gp* g, const double* Z, int64_t M, int32_t z_space, const double** Zd);
+int32_t copy_in(void* dst, const void* src, size_t bytes, int32_t space, hipStream_t s);
+int32_t copy_out(void* dst, const void* src, size_t bytes, int32_t space, hipStream_t s);
+bool phase_events();                                       // one definition, one thread-local behind it: a second copy would time N ≤ 128
+float ev_ms(hipEvent_t a, hipEvent_t b);                   // 0 for an event that was never recorded
+void oz_defaults(int* engine, int* nmod);                  // the process default of the contraction engine (ABO_CONTRACTION, abo_set_contraction)
+
+// Event slots of a handle (abo_gp::evs()).  The numbers are fixed: abo_timings, abo_prune_stats and abo_get_prune_levels are differences
+// of these.  EV_REFINE_* ALIASES the W-planes pair: the grid-and-refine call (api.hip: optimize_terms_impl) brackets its refinement
+// stage with them, and on a gradient-enhanced handle whose planes of W are stale that stage reaches refine_device → grad_eval_device →
+// oz_planes_of_w, which records both again in between — refine_ms then starts at the rebuild.  Kept as it is; not to be copied.
+enum EvSlot : size_t {
+    EV_FIT_BEGIN = 0, EV_FIT_KMAT = 1, EV_FIT_CHOL = 2, EV_FIT_INV = 3, EV_FIT_END = 4,       // the fit's phases end at 1 … 4
+    EV_ACQ_BEGIN = 5, EV_ACQ_SCORED = 6, EV_ACQ_END = 7,                                       // a posterior / acquisition call; a call without selection ends at SCORED
+    EV_WPLANES_BEGIN = 8, EV_WPLANES_END = 9,                                                  // residue planes of W rebuilt (posterior.hip: oz_planes_of_w)
+    EV_REFINE_BEGIN = EV_WPLANES_BEGIN, EV_REFINE_END = EV_WPLANES_END,                        // alias, see above
+    EV_BOUND_BEGIN = 10, EV_BOUND_END = 11, EV_THRESHOLD_END = 12, EV_SURVIVORS_END = 13,      // the pruned selection (acq.hip: prune_select)
+    EV_BOUND2_BEGIN = 14, EV_BOUND2_END = 15,                                                  // its second bound level
+    // from here on: the per-chunk events of a call's posterior passes (ev_chunk) — or, in calls that run none, scratch: append_impl
+    // EV_BASE + 0 … 1, nlml_grad_impl + 0 … 2, qei_block + 0 … 3 (the factorisation's look-ahead kept its strip events here)
+    EV_BASE = 16
+};
+enum EvChunk : size_t {
+    EVC_KGEN_BEGIN = 0, EVC_KGEN_END = 1, EVC_CONTRACT_BEGIN = 2, EVC_CONTRACT_END = 3, EVC_EPILOGUE_BEGIN = 4, EVC_EPILOGUE_END = 5,
+    EVC_OZ_QUANT_END = 6, EVC_OZ_GEMM_END = 7,          // int8 pipeline, between CONTRACT_BEGIN and CONTRACT_END
+    EV_PER_CHUNK = 8
+};
+// slot of chunk `chunk` of the call (PostPass::chunk0 + c: the passes of one call count on)
+inline size_t ev_chunk(int64_t chunk, EvChunk slot) { return (size_t)EV_BASE + (size_t)EV_PER_CHUNK * (size_t)chunk + slot; }
 
 struct DevBuf {
     void* p = nullptr;
@@ -63,6 +97,31 @@ struct ExecCtx {
     hipStream_t stream = nullptr;
     std::vector<hipEvent_t> ev;
     char* pin = nullptr;
+};
+
+// the small read-backs of ONE call: each goes into the context's pinned block (asynchronously) while it fits, straight to its
+// destination otherwise; flush() — behind the call's stream synchronisation — copies the staged ones on
+struct PinStage {
+    ExecCtx* c;
+    size_t off = PIN_OUT;
+    struct Item { void* dst; size_t off, n; } it[8];
+    int n = 0;
+    explicit PinStage(ExecCtx* ctx) : c(ctx) {}
+    hipError_t d2h(void* dst, const void* src, size_t bytes, hipStream_t s) {
+        if (bytes == 0) return hipSuccess;
+        const size_t a = (bytes + 15) & ~(size_t)15;
+        if (c && c->pin && n < 8 && off + a <= PIN_BYTES) {
+            it[n++] = Item{dst, off, bytes};
+            const hipError_t e = hipMemcpyAsync(c->pin + off, src, bytes, hipMemcpyDeviceToHost, s);
+            off += a;
+            return e;
+        }
+        return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s);
+    }
+    void flush() {
+        for (int i = 0; i < n; ++i) memcpy(it[i].dst, c->pin + it[i].off, it[i].n);
+        n = 0;
+    }
 };
 
 constexpr int OZ_DEFAULT_NMOD = 14;   // moduli of the contraction's residue plan unless asked otherwise; P ≈ 2^110: the fixed-point images keep 50+ bits of W per row and 52–53 bits of K_XZ
@@ -186,7 +245,7 @@ struct abo_gp {
     int oz_engine = ABO_CONTRACT_AUTO, oz_nmod = 0;
     int* oz_ctr_clean = nullptr;       // the tile-counter block of oz_badc known to hold zeros (OzVarArgs::ctr_clean)
     abo::OzPlan oz_plan{};
-    bool oz_prepare_pending = false;  // events 8/9 of the current call bracket a rebuild of the residue planes of W (read with its timings)
+    bool oz_prepare_pending = false;  // EV_WPLANES_BEGIN / _END of the current call bracket a rebuild of the residue planes of W (read with its timings)
     uint64_t oz_gen = 0;
     int64_t oz_N = -1;
     // the posterior passes of the current call, in launch order (their per-chunk events are read back with them): the pruned top-k
@@ -226,7 +285,46 @@ struct abo_gp {
 #pragma GCC visibility push(hidden)
 namespace abo {
 
+// api.hip: the fields of KgenArgs that describe the MODEL of a fitted handle — Xs, N, Np, d, dp, family, s, sigma_f2, pt, and with_mean:
+// mean_c, mean_vec (else both zero: the launch forms no mean) —, everything else as KgenArgs{} leaves it.  A call site adds its launch
+// (Z, outputs, chunk, layout) and states whatever it wants different of the model.
+KgenArgs kgen_model_args(const abo_gp* g, bool with_mean);
+
+// ---- the chunked posterior pass (posterior.hip) ------------------------------------------------------------------------------------------
+// what the pass does beyond mu / var / score of M candidates
+struct PostOpts {
+    int pc = 1;                  // outputs per candidate: 1 = function value; p_out = all outputs of a gradient-enhanced GP (mu / var / score arrays then have pc·M entries)
+    bool point_major = false;    // with pc > 1: the rows go point by point (i·pc + q) instead of output by output (q·M + i)
+    double* kstore = nullptr;    // write K_XZ into a caller-owned candidate-major matrix (pad_up(M,128) rows of ldstore ≥ Np doubles)
+    int64_t ldstore = 0;         // instead of the per-chunk scratch — the resident K_ZX of a candidate set
+    // rblocks > 0 (the bound pass of the pruned selection; int8 engine with generator-written planes only, else PRUNE_UNAVAILABLE):
+    // the contraction covers the first rblocks 256-row blocks of W — var / score then come from σ²_R ≥ σ² and from μ̃ − ε ≤ μ: the mean's
+    // columns past those blocks are summed by the cheaper launch_kgen_tail, which also proves ε ≥ |μ̃ − μ| (kgen_tail.hip).
+    int rblocks = 0;
+    bool more = false;           // a further pass of the same call — its events and counts are kept next to those of the passes before it
+    bool level2 = false;         // a bound pass over the survivors of a first one — μ̃ and ε go to buffers of their own
+    bool tail32 = false;         // the tail of a bound pass by launch_kgen_tail32 (fp32 pairs, a wider proven ε: kgen_tail32.hip) — the M-wide first level
+    // head32 (with tail32 only): the head of that pass — head of the mean and guarded sum of squares — by ONE launch of kgen_head32.hip over
+    // all candidates in place of head generator, residue GEMM and reconstruction per chunk; the chunk loop then runs tail and epilogue alone.
+    bool head32 = false;
+};
+constexpr int32_t PRUNE_UNAVAILABLE = -100;
+// mu / var / score for M candidates into device arrays (any may be null); launches only, on the handle's stream
+int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0, double best_y, double* mu_out, double* var_out,
+                  double* score_out, const PostOpts& o = {});
+// gradient-enhanced model: mean of all P outputs, P×P covariance block and GradientNormUCB score per point; launches only
+int32_t grad_eval_device(abo_gp* g, const double* Zd, int64_t M, double beta, double* mu_d, double* cov_d, double* sc_d);
+void collect_posterior_timings(abo_gp* g, bool with_var);  // behind the call's synchronisation: phase times and work of its passes
+bool wants_int8(const abo_gp* g, bool want_var, int pc, int* nmod);   // the engine of a posterior call's contraction, and its moduli
+double grad_prior_var(const abo_gp* g);                    // prior variance of a gradient output
+bool prune_bound_moduli_asked();                           // ABO_PRUNE_BOUND_MODULI is set, or its hook: an explicit request for the int8 head
+
+// ---- scoring and selection (acq.hip) -----------------------------------------------------------------------------------------------------
+// scores + selection for host or device candidates, behind check_fitted; separate memory spaces for the M scores and the k selected pairs
+int32_t acq_terms_impl(abo_gp* g, const double* Z, int64_t M, int32_t d, int32_t z_space, const AcqTerms& t, int64_t idx_base,
+                       double* scores, int32_t out_space, int32_t k, double* top_val, int64_t* top_idx, int32_t top_space);
 int32_t make_terms(const abo_gp* g, const abo_acq_term* terms, int32_t n, AcqTerms* out, const char* fn);
+// api.hip: the MES entry points' checks and objective
 int32_t mes_check_samples(const double* ystar, int32_t S, int32_t ys_space, const char* fn);
 int32_t mes_check_handle(abo_gp* g, const char* fn);
 int32_t mes_terms(abo_gp* g, const double* ystar, int32_t S, int32_t ys_space, AcqTerms* t);

@@ -1,6 +1,7 @@
-// C-ABI of libabo_hip.so (declared in include/abo_hip.h): handle lifetime, the blocked fp64
-// factorisation driver, the chunked posterior/acquisition driver.  Host-side orchestration only —
-// all arithmetic is in the HIP kernels of gemm.hip / kgen.hip / chol.hip / misc.hip.
+// C-ABI of libabo_hip.so (declared in include/abo_hip.h): handle lifetime and the device-memory pool, the blocked fp64
+// factorisation driver (fit / append / remove), NLML / LOO / joint covariance, resident candidate sets and q-EI, refinement, the
+// MES entry points.  The chunked posterior pass is posterior.hip, scoring and selection acq.hip; what the three share is declared
+// in abo_state.h.  Host-side orchestration only — all arithmetic is in the HIP kernels of gemm.hip / kgen.hip / chol.hip / misc.hip.
 //
 // Device-resident state of a fitted handle (Np = N rounded up to 128, identity-padded):
 //   Xs  [Np][dp]   training points × 1/ell, zero padded (dp = d rounded up to 1,2,4,8,16,32)
@@ -109,11 +110,6 @@ size_t pool_limit() {
     return lim;
 }
 
-size_t oz_scratch_limit() {
-    const char* e = getenv("ABO_OZ_SCRATCH_LIMIT_MB");
-    return e ? (size_t)atoll(e) << 20 : ~(size_t)0;
-}
-
 size_t round_size(size_t bytes) {
     const size_t g = bytes < ((size_t)1 << 20) ? 4096 : ((size_t)2 << 20);
     return (bytes + g - 1) / g * g;
@@ -195,31 +191,6 @@ void pool_trim(int dev) {
 std::mutex g_ctx_mu;
 std::vector<ExecCtx*> g_ctx_free[16];
 
-// the small read-backs of ONE call: each goes into the context's pinned block (asynchronously) while it fits, straight to its
-// destination otherwise; flush() — behind the call's stream synchronisation — copies the staged ones on
-struct PinStage {
-    ExecCtx* c;
-    size_t off = PIN_OUT;
-    struct Item { void* dst; size_t off, n; } it[8];
-    int n = 0;
-    explicit PinStage(ExecCtx* ctx) : c(ctx) {}
-    hipError_t d2h(void* dst, const void* src, size_t bytes, hipStream_t s) {
-        if (bytes == 0) return hipSuccess;
-        const size_t a = (bytes + 15) & ~(size_t)15;
-        if (c && c->pin && n < 8 && off + a <= PIN_BYTES) {
-            it[n++] = Item{dst, off, bytes};
-            const hipError_t e = hipMemcpyAsync(c->pin + off, src, bytes, hipMemcpyDeviceToHost, s);
-            off += a;
-            return e;
-        }
-        return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s);
-    }
-    void flush() {
-        for (int i = 0; i < n; ++i) memcpy(it[i].dst, c->pin + it[i].off, it[i].n);
-        n = 0;
-    }
-};
-
 // padded coordinate count: 1, 2, 4, 8, 16, 32 (register-resident kernels), beyond that a multiple of 32 (slab kernels)
 int dp_for(int d) {
     if (d > 32) return (d + 31) / 32 * 32;
@@ -239,10 +210,10 @@ std::atomic<uint64_t> g_append_serial{1};
 
 // contraction engine of the posterior variance: process default (ABO_CONTRACTION = auto | fp64 | int8 | int8:<moduli>),
 // overridable per handle (abo_set_contraction)
-constexpr int OZ_AUTO_MIN_NP = 1280;  // below this the fp64 kernels win (tools/engine_crossover.py, profiles/r06_engine_crossover.txt: fp64/int8 = 0.97 at
-                                      // 1024, 1.09 at 1280, 1.21 at 1536, 1.90 at 4096; round 2's engine crossed at 1536)
 std::atomic<int> g_oz_engine{-1}, g_oz_nmod{OZ_DEFAULT_NMOD};
-void oz_defaults(int* engine, int* nmod) {
+}  // namespace
+
+void abo::oz_defaults(int* engine, int* nmod) {
     int e = g_oz_engine.load();
     if (e < 0) {
         e = ABO_CONTRACT_AUTO;
@@ -261,8 +232,6 @@ void oz_defaults(int* engine, int* nmod) {
     *nmod = g_oz_nmod.load();
 }
 
-}  // namespace
-
 void abo_gp::free_all() {
 #define X(name) name.release();
     ABO_GP_BUFS(X)
@@ -277,6 +246,17 @@ void abo_gp::free_all() {
         g_ctx_free[prm.device & 15].push_back(ctx);
         ctx = nullptr; stream = nullptr;
     }
+}
+
+KgenArgs abo::kgen_model_args(const abo_gp* g, bool with_mean) {
+    KgenArgs ka{};
+    ka.Xs = g->st->Xs.as<double>(); ka.N = (int)g->npts; ka.Np = (int)g->Np; ka.d = g->d; ka.dp = g->dp;
+    ka.family = g->prm.family; ka.s = 1.0 / g->prm.ell; ka.sigma_f2 = g->prm.sigma_f2; ka.pt = g->p_out;
+    if (with_mean) {
+        ka.mean_c = g->prm.mean_c;
+        for (int q = 0; q < MAX_P; ++q) ka.mean_vec[q] = g->mean_vec[q];
+    }
+    return ka;
 }
 
 // candidate set resident in HBM with its posterior (C5: O(N·M) down-dates instead of re-evaluation)
@@ -339,7 +319,7 @@ struct abo_cand {
     }
 };
 
-namespace {
+namespace abo {    // shared with the other host units (abo_state.h)
 
 int32_t copy_in(void* dst, const void* src, size_t bytes, int32_t space, hipStream_t s) {
     if (bytes == 0) return ABO_OK;
@@ -353,10 +333,6 @@ int32_t copy_out(void* dst, const void* src, size_t bytes, int32_t space, hipStr
     return ABO_OK;
 }
 
-int32_t factorise(abo_gp* g, double noise, int64_t* info_host);
-int32_t fit_small(abo_gp* g, double noise, int64_t* info_host);
-void fit_collect(abo_gp* g);
-
 float ev_ms(hipEvent_t a, hipEvent_t b) {
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, a, b) != hipSuccess) { (void)hipGetLastError(); ms = 0.f; }   // (an event that was never recorded)
@@ -369,39 +345,43 @@ float ev_ms(hipEvent_t a, hipEvent_t b) {
 // leaves them out (the phase fields of abo_timings then read 0, the totals stay); default on.
 // ABO_PHASE_EVENTS: 1 = always, 0 = never, unset = automatic — on, except while the calling thread works on a model of one row block
 // (N ≤ 128: the reference's own loops, where the step is 0.2 ms and the instrumentation a fifth of it).
-thread_local int64_t tl_phase_np = (int64_t)1 << 40;     // padded factor rows of the handle the current call works on
+// The thread-local is written in this unit alone (check_fitted, fit_impl, append_impl) and read through phase_events(), which the
+// other units call: ONE definition of both.
+namespace { thread_local int64_t tl_phase_np = (int64_t)1 << 40; }    // padded factor rows of the handle the current call works on
 bool phase_events() {
     static const int mode = [] { const char* e = getenv("ABO_PHASE_EVENTS"); return !e ? -1 : (e[0] == '0' ? 0 : 1); }();
     return mode < 0 ? tl_phase_np > TB : mode == 1;
 }
-#define PHASE_EVENT(ev, s) do { if (phase_events()) HIPCHK(hipEventRecord((ev), (s))); } while (0)
+
+}  // namespace abo
+
+namespace {
+
+int32_t factorise(abo_gp* g, double noise, int64_t* info_host);
+int32_t fit_small(abo_gp* g, double noise, int64_t* info_host);
 
 // the scalars and phase timings of a finished fit (h_sc / h_info have landed: the stream has been synchronised since)
 void fit_collect(abo_gp* g) {
     g->logdet = g->h_sc()[0];
     g->quad = g->h_sc()[1];
-    g->tm.fit_total_ms = ev_ms(g->evs()[0], g->evs()[4]);
+    g->tm.fit_total_ms = ev_ms(g->evs()[EV_FIT_BEGIN], g->evs()[EV_FIT_END]);
     if (!phase_events()) {
         g->tm.fit_kernel_matrix_ms = g->tm.fit_cholesky_ms = g->tm.fit_inverse_ms = g->tm.fit_alpha_ms = 0.0;
         return;
     }
     if (g->fit_small_path) {
         g->tm.fit_kernel_matrix_ms = 0.0;
-        g->tm.fit_cholesky_ms = ev_ms(g->evs()[1], g->evs()[2]);      // the one launch
+        g->tm.fit_cholesky_ms = ev_ms(g->evs()[EV_FIT_KMAT], g->evs()[EV_FIT_CHOL]);      // the one launch
         g->tm.fit_inverse_ms = 0.0;
         g->tm.fit_alpha_ms = 0.0;
     } else {
-        g->tm.fit_kernel_matrix_ms = ev_ms(g->evs()[0], g->evs()[1]);
-        g->tm.fit_cholesky_ms = ev_ms(g->evs()[1], g->evs()[2]);
-        g->tm.fit_inverse_ms = ev_ms(g->evs()[2], g->evs()[3]);
-        g->tm.fit_alpha_ms = ev_ms(g->evs()[3], g->evs()[4]);
+        g->tm.fit_kernel_matrix_ms = ev_ms(g->evs()[EV_FIT_BEGIN], g->evs()[EV_FIT_KMAT]);
+        g->tm.fit_cholesky_ms = ev_ms(g->evs()[EV_FIT_KMAT], g->evs()[EV_FIT_CHOL]);
+        g->tm.fit_inverse_ms = ev_ms(g->evs()[EV_FIT_CHOL], g->evs()[EV_FIT_INV]);
+        g->tm.fit_alpha_ms = ev_ms(g->evs()[EV_FIT_INV], g->evs()[EV_FIT_END]);
     }
-    g->tm.fit_total_ms = ev_ms(g->evs()[0], g->evs()[4]);
+    g->tm.fit_total_ms = ev_ms(g->evs()[EV_FIT_BEGIN], g->evs()[EV_FIT_END]);
 }
-
-constexpr size_t EV_BASE = 16;        // 0-4 fit phases, 5-7 acquisition call, 8-9 residue planes of W, 10-13 passes of the pruned selection, 14-15 its second bound level; from EV_BASE: per-chunk events of a
-                                      // posterior call, or (inside a fit) the strip events of the factorisation's look-ahead
-constexpr size_t EV_PER_CHUNK = 8;   // kgen 0-1, contraction 2-3, epilogue 4-5, int8 pipeline: end of quantisation 6, end of GEMM 7
 
 }  // namespace
 
@@ -538,7 +518,7 @@ int32_t factorise(abo_gp* g, double noise, int64_t* info_host) {
     HIPCHK(g->info.ensure(sizeof(int64_t)));
     int64_t* info = g->info.as<int64_t>();              // the LAPACK-style status
 
-    HIPCHK(hipEventRecord(g->evs()[0], s));
+    HIPCHK(hipEventRecord(g->evs()[EV_FIT_BEGIN], s));
     // whole capacity region: zeros, identity on the padded diagonal (rows ≥ N), K on the active part.  With a panel chain (more than
     // one block) rows < Np of W / WT are zeroed by the chain's own launches — the idle workgroups of each diagonal-block launch take
     // that panel's rows (chol.hip: potf2_pipe_kernel) — instead of two whole-matrix memsets in front of the fit (148 µs at N = 8192).
@@ -551,33 +531,31 @@ int32_t factorise(abo_gp* g, double noise, int64_t* info_host) {
         HIPCHK(hipMemsetAsync(W + (int64_t)Np * ld, 0, sizeof(double) * (ld - Np) * ld, s));
         HIPCHK(hipMemsetAsync(WT + (int64_t)Np * ld, 0, sizeof(double) * (ld - Np) * ld, s));
     }
-    KgenArgs ka{};
-    ka.Xs = st->Xs.as<double>(); ka.Z = st->Xraw.as<double>(); ka.alpha = nullptr; ka.Kout = K; ka.mu = nullptr;
-    ka.ldk = ld; ka.M = g->npts; ka.j0 = 0; ka.Mc = Np; ka.N = (int)g->npts; ka.Np = Np; ka.d = g->d; ka.dp = g->dp;
-    ka.family = g->prm.family; ka.s = 1.0 / g->prm.ell; ka.sigma_f2 = g->prm.sigma_f2; ka.mean_c = 0.0;
-    ka.pt = g->p_out; ka.pc = g->p_out; ka.point_major = 1;      // K_XX: rows and columns point-major → symmetric
+    KgenArgs ka = kgen_model_args(g, false);
+    ka.Z = st->Xraw.as<double>(); ka.Kout = K; ka.ldk = ld; ka.M = g->npts; ka.Mc = Np;
+    ka.pc = g->p_out; ka.point_major = 1;                        // K_XX: rows and columns point-major → symmetric
     HIPCHK(launch_kgen(ka, s));
     HIPCHK(launch_diag_fix(K, ld, N, (int)ld, noise, s, info));      // also resets the status word
     if (ld > Np) {
         HIPCHK(launch_set_diag(W, ld, Np, (int)ld, 1.0, s));
         HIPCHK(launch_set_diag(WT, ld, Np, (int)ld, 1.0, s));
     }
-    PHASE_EVENT(g->evs()[1], s);
+    PHASE_EVENT(g->evs()[EV_FIT_KMAT], s);
 
     // (the operand stream of the panel solve lives in T, which the factorisation does not use — the blocked inverse behind it does)
     if (split) HIPCHK(g->T.ensure(TRSM_STREAM_BYTES));
     { const int32_t rc = chol_blocked(K, W, WT, g->T.as<double>(), ld, Np, info, CholBlocking{}, s); if (rc) return rc; }
-    PHASE_EVENT(g->evs()[2], s);
+    PHASE_EVENT(g->evs()[EV_FIT_CHOL], s);
     // no host round trip here: after a failed pivot every later kernel of the fit either exits on `info` (the GEMMs) or
     // works on finite leftovers whose results are discarded; `info` is read once, with the scalars, at the end
 
     { const int32_t rc = trinv_blocked(K, W, WT, g->T.as<double>(), ld, Np, info, s); if (rc) return rc; }
-    PHASE_EVENT(g->evs()[3], s);
+    PHASE_EVENT(g->evs()[EV_FIT_INV], s);
     // alpha = Wᵀ(W·delta)
     HIPCHK(launch_trmv(W, ld, st->delta.as<double>(), g->tvec.as<double>(), Np, 1, s));
     HIPCHK(launch_trmv(WT, ld, g->tvec.as<double>(), g->alpha.as<double>(), Np, 0, s));
     HIPCHK(launch_nlml_terms(K, ld, st->delta.as<double>(), g->alpha.as<double>(), N, g->scal.as<double>(), s));
-    HIPCHK(hipEventRecord(g->evs()[4], s));
+    HIPCHK(hipEventRecord(g->evs()[EV_FIT_END], s));
     g->fit_small_path = false;
     HIPCHK(hipMemcpyAsync(g->h_sc(), g->scal.as<double>(), 2 * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(&g->h_info(), info, sizeof(int64_t), hipMemcpyDeviceToHost, s));
@@ -593,8 +571,8 @@ int32_t fit_small(abo_gp* g, double noise, int64_t* info_host) {
     hipStream_t s = g->stream;
     Storage* st = g->st;
     int64_t* info = g->info.as<int64_t>();
-    HIPCHK(hipEventRecord(g->evs()[0], s));
-    PHASE_EVENT(g->evs()[1], s);                            // (the launch resets the status word itself)
+    HIPCHK(hipEventRecord(g->evs()[EV_FIT_BEGIN], s));
+    PHASE_EVENT(g->evs()[EV_FIT_KMAT], s);                            // (the launch resets the status word itself)
     FitSmallArgs fs{};
     fs.Xraw = st->Xraw.as<double>(); fs.y = st->ybuf.as<double>(); fs.Xs = st->Xs.as<double>(); fs.delta = st->delta.as<double>();
     if (g->in_x) { fs.Xraw = g->in_x; fs.y = g->in_y; fs.Xkeep = st->Xraw.as<double>(); fs.ykeep = st->ybuf.as<double>(); }
@@ -602,8 +580,8 @@ int32_t fit_small(abo_gp* g, double noise, int64_t* info_host) {
     fs.N = (int)g->N; fs.d = g->d; fs.dp = g->dp; fs.family = g->prm.family;
     fs.s = 1.0 / g->prm.ell; fs.sigma_f2 = g->prm.sigma_f2; fs.noise = noise; fs.mean_c = g->prm.mean_c;
     HIPCHK(launch_fit_small(st->K.as<double>(), st->W.as<double>(), st->WT.as<double>(), info, fs, s));
-    PHASE_EVENT(g->evs()[2], s);
-    HIPCHK(hipEventRecord(g->evs()[4], s));
+    PHASE_EVENT(g->evs()[EV_FIT_CHOL], s);
+    HIPCHK(hipEventRecord(g->evs()[EV_FIT_END], s));
     g->fit_small_path = true;
     HIPCHK(hipMemcpyAsync(g->h_sc(), g->scal.as<double>(), 2 * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(&g->h_info(), info, sizeof(int64_t), hipMemcpyDeviceToHost, s));
@@ -612,437 +590,6 @@ int32_t fit_small(abo_gp* g, double noise, int64_t* info_host) {
     *info_host = g->h_info();
     if (g->h_info() == 0) fit_collect(g);
     return ABO_OK;
-}
-
-// k((z,q),(z,q)) of a gradient output: −2σ_f²φ'(0)/ℓ²  (φ'(0) = −1/2 SE, −5/6 Matérn-5/2, −7/10 Matérn-7/2)
-double grad_prior_var(const abo_gp* g) {
-    const double c = g->prm.family == ABO_KERNEL_SE ? 1.0 : (g->prm.family == ABO_KERNEL_MATERN52 ? 5.0 / 3.0 : 7.0 / 5.0);
-    return c * g->prm.sigma_f2 / (g->prm.ell * g->prm.ell);
-}
-
-
-// exponent of the row scaling of a gradient-enhanced model's derivative outputs: 2^t ≈ √(prior variance of a derivative output / σ_f²)
-int oz_grad_exp(const abo_gp* g) {
-    if (g->p_out <= 1) return 0;
-    return (int)std::lrint(0.5 * std::log2(grad_prior_var(g) / g->prm.sigma_f2));
-}
-
-// which engine runs the contraction of a posterior call on this handle (int8 = true), and with how many moduli
-bool wants_int8(const abo_gp* g, bool want_var, int pc, int* nmod) {
-    if (!want_var || (pc != 1 && pc != g->p_out)) return false;
-    int eng = g->oz_engine, nm = g->oz_nmod, de, dn;
-    oz_defaults(&de, &dn);
-    if (eng == ABO_CONTRACT_AUTO) eng = de;
-    if (!nm) nm = dn;
-    *nmod = nm;
-    // int32 accumulation of the residue GEMMs is exact for k·2^14 < 2^31: beyond 65536 padded training points the engine is not
-    // offered (the fp64 kernels take over, whatever was asked for)
-    if (g->Np > 65536) return false;
-    return eng == ABO_CONTRACT_INT8 || (eng == ABO_CONTRACT_AUTO && g->Np >= OZ_AUTO_MIN_NP);
-}
-
-int64_t pick_chunk(const abo_gp* g, int64_t M, bool int8) {
-    int64_t mc = g->prm.chunk;
-    if (mc <= 0 && int8) {
-        // int8 engine: 28 bytes of residue planes and residue products per (candidate, training point); measured at N = 8192:
-        // 8192 candidates per chunk 597 ms, 16384 572, 32768 565, 65536 560 per C3 step — 65536 at N = 8192 (15 GB of scratch of the
-        // 288), 32768 at N = 16384
-        mc = ((int64_t)1 << 32) / (g->Np * (int64_t)sizeof(double));
-        if (mc < 2048) mc = 2048;
-        if (mc > 65536) mc = 65536;
-    } else if (mc <= 0) {
-        // ~1 GiB of K_XZ per chunk (measured at N = 8192, tools/chunk_sweep.sh: 2048 candidates per chunk 1072 ms,
-        // 4096 1011, 8192 997, 16384 992-995, 32768 998, 65536 996 — small chunks pay launch tails in every kernel,
-        // larger ones lose a little L2/MALL reuse of the candidate panels), at least 2048 and at most 65536 candidates
-        mc = ((int64_t)1 << 30) / (g->Np * (int64_t)sizeof(double));
-        if (mc < 2048) mc = 2048;
-        if (mc > 65536) mc = 65536;
-    }
-    mc = pad_up(mc, TB);
-    if (int8) {        // byte offsets inside one residue plane of a chunk stay below 2^31 (32-bit lane offsets in the generator and the DMA)
-        const int64_t cap = (((int64_t)1 << 31) / pad_up(g->Np, 256)) / 256 * 256 - 256;
-        if (mc > cap) mc = cap;
-    }
-    const int64_t mp = pad_up(M, TB);
-    return mc < mp ? mc : mp;
-}
-
-// The int8 engine's scratch — 2 × n bytes per (candidate, factor row) of a chunk, and the n residue planes of W: when the device
-// cannot give it (a shared or nearly full GPU), the chunk *Mc is halved down to 4096 candidates, and below that *oz comes back false:
-// the call then runs on the fp64 kernels (8 bytes per pair of a chunk four times smaller) instead of failing.
-int32_t oz_acquire(abo_gp* g, int nm, int64_t M, int64_t* Mc_io, bool* oz_io) {
-    const int64_t Np = g->Np;
-    int64_t Mc = *Mc_io;
-    bool oz = *oz_io;
-    if (oz) {
-        if (g->oz_plan.n != nm) {                               // another moduli count: the cached planes of W belong to the old plan
-            if (!oz_make_plan(nm, &g->oz_plan)) return fail(ABO_EINVAL, "contraction: %d moduli not supported", nm);
-            g->oz_N = -1;
-        }
-        const int64_t q = pad_up(Np, 256);
-        hipError_t e = g->oz_WR.ensure(oz_w_bytes(nm, (int)Np));
-        if (e == hipSuccess) e = g->oz_sexp.ensure(sizeof(int) * q);
-        if (e == hipSuccess) e = g->oz_badr.ensure(sizeof(int) * q);
-        while (e == hipSuccess) {
-            // ABO_OZ_SCRATCH_LIMIT_MB caps what the two chunk buffers may take together (a knob for shared devices; the tests use it
-            // to walk this very path)
-            const size_t kb = oz_k_bytes(nm, (int)Np, (int)Mc);
-            e = 2 * kb > oz_scratch_limit() ? hipErrorOutOfMemory : g->oz_KR.ensure(kb);
-            if (e == hipSuccess) e = g->oz_U.ensure(kb);
-            if (e == hipSuccess) e = g->oz_badc.ensure(sizeof(int) * (pad_up(Mc, 256) + OZ_CTR_INTS));   // + the GEMM's tile counters
-            if (e != hipErrorOutOfMemory || Mc <= 4096) break;
-            (void)hipGetLastError();
-            g->oz_KR.release(); g->oz_U.release();
-            Mc = pad_up(Mc / 2, 256);
-            e = hipSuccess;
-        }
-        if (e == hipErrorOutOfMemory) {
-            (void)hipGetLastError();
-            g->oz_KR.release(); g->oz_U.release(); g->oz_WR.release();
-            g->oz_N = -1;
-            oz = false;
-            Mc = pick_chunk(g, M, false);
-        } else HIPCHK(e);
-    }
-    *Mc_io = Mc;
-    *oz_io = oz;
-    return ABO_OK;
-}
-
-// residue planes of this view's W, once per model (cached on the handle until the storage generation or the view changes)
-int32_t oz_planes_of_w(abo_gp* g) {
-    hipStream_t s = g->stream;
-    if (g->oz_gen != g->st->gen || g->oz_N != g->N) {
-        PHASE_EVENT(g->evs()[8], s);
-        HIPCHK(oz_prepare_w(g->oz_plan, g->st->W.as<double>(), g->st->cap, (int)g->Np, (int)g->N, g->oz_WR.as<int8_t>(),
-                            g->oz_sexp.as<int>(), g->oz_badr.as<int>(), s, g->p_out, oz_grad_exp(g)));
-        PHASE_EVENT(g->evs()[9], s);
-        g->oz_gen = g->st->gen; g->oz_N = g->N;
-        g->oz_prepare_pending = true;                               // both events recorded in THIS call: read with the posterior timings
-    }
-    return ABO_OK;
-}
-
-// what the chunked posterior pass does beyond mu / var / score of M candidates
-struct PostOpts {
-    int pc = 1;                  // outputs per candidate: 1 = function value; p_out = all outputs of a gradient-enhanced GP (mu / var / score arrays then have pc·M entries)
-    bool point_major = false;    // with pc > 1: the rows go point by point (i·pc + q) instead of output by output (q·M + i)
-    double* kstore = nullptr;    // write K_XZ into a caller-owned candidate-major matrix (pad_up(M,128) rows of ldstore ≥ Np doubles)
-    int64_t ldstore = 0;         // instead of the per-chunk scratch — the resident K_ZX of a candidate set
-    // rblocks > 0 (the bound pass of the pruned selection; int8 engine with generator-written planes only, else PRUNE_UNAVAILABLE):
-    // the contraction covers the first rblocks 256-row blocks of W — var / score then come from σ²_R ≥ σ² and from μ̃ − ε ≤ μ: the mean's
-    // columns past those blocks are summed by the cheaper launch_kgen_tail, which also proves ε ≥ |μ̃ − μ| (kgen_tail.hip).
-    int rblocks = 0;
-    bool more = false;           // a further pass of the same call — its events and counts are kept next to those of the passes before it
-    bool level2 = false;         // a bound pass over the survivors of a first one — μ̃ and ε go to buffers of their own
-    bool tail32 = false;         // the tail of a bound pass by launch_kgen_tail32 (fp32 pairs, a wider proven ε: kgen_tail32.hip) — the M-wide first level
-    // head32 (with tail32 only): the head of that pass — head of the mean and guarded sum of squares — by ONE launch of kgen_head32.hip over
-    // all candidates in place of head generator, residue GEMM and reconstruction per chunk; the chunk loop then runs tail and epilogue alone.
-    bool head32 = false;
-};
-constexpr int32_t PRUNE_UNAVAILABLE = -100;
-
-// moduli of the bound pass's residue plan: 8 (default), 9, 10 — a short plan with the guard of ozaki.hip — or 14: the handle's plan,
-// exact contraction, as before the short plan existed.  ABO_PRUNE_BOUND_MODULI; any other value (11 – 13, below 8, text) is IGNORED and
-// the default 8 used — the head generator is instantiated for these counts alone; the test hook refuses such a value with an error.
-int prune_bound_moduli() {
-    static const int env = [] {
-        const char* e = getenv("ABO_PRUNE_BOUND_MODULI");
-        const int v = e ? atoi(e) : 0;
-        return (kgen_short_moduli(v) || v == 14) ? v : 8;
-    }();
-    if (g_prune_bound_moduli.load(std::memory_order_relaxed) > 0) return g_prune_bound_moduli.load(std::memory_order_relaxed);
-    return env;
-}
-
-// mu / var / score for M candidates into device arrays (any may be null)
-int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0, double best_y, double* mu_out,
-                  double* var_out, double* score_out, const PostOpts& o = {}) {
-    const int pc = o.pc, point_major = o.point_major ? 1 : 0, rblocks = o.rblocks;
-    double* const kstore = o.kstore;
-    const int64_t ldstore = o.ldstore;
-    const bool more = o.more, level2 = o.level2, tail32 = o.tail32;
-    const int64_t M = Mpts * pc;                         // candidate rows
-    hipStream_t s = g->stream;
-    const int64_t Np = g->Np;
-    const int T = (int)(Np / TB);
-    const bool want_var = var_out || score_out;
-    int nm = 0;
-    bool oz = wants_int8(g, want_var, pc, &nm);
-    int64_t Mc = pick_chunk(g, M, oz);
-    { int32_t rc = oz_acquire(g, nm, M, &Mc, &oz); if (rc) return rc; }
-    {
-        KgenArgs probe{};
-        probe.pt = g->p_out; probe.dp = g->dp;
-        if (rblocks > 0 && !(oz && kgen_writes_residues(probe, nm) && !kstore && pc == 1)) return PRUNE_UNAVAILABLE;
-        // the fp64 chunk of K_XZ is not materialised when the generator writes the residue planes itself
-        if (!kstore && !(oz && kgen_writes_residues(probe, nm))) HIPCHK(g->Kxz.ensure(sizeof(double) * Mc * Np));
-    }
-    HIPCHK(g->partial.ensure(sizeof(double) * T * Mc));
-    HIPCHK(g->mu_c.ensure(sizeof(double) * Mc));
-    DevBuf& mut = level2 ? g->pr_mut2 : g->pr_mut;       // (the first level's μ̃ and ε of all candidates stay what abo_test_prune_mean reads)
-    DevBuf& eps = level2 ? g->pr_eps2 : g->pr_eps;
-    if (rblocks > 0) {
-        HIPCHK(mut.ensure(sizeof(double) * M));
-        HIPCHK(eps.ensure(sizeof(double) * M));
-        HIPCHK(g->pr_nrm.ensure(sizeof(double) * 4));
-    }
-    const int64_t nchunk = (M + Mc - 1) / Mc;
-    if (!more) {
-        g->passes.clear();
-        g->tm.var_gemm_launches = 0;
-        g->oz_prepare_pending = false;
-        g->tm.oz_prepare_ms = 0.0;                                  // planes cached from an earlier call: nothing spent in this one
-    }
-    const int64_t chunk0 = g->passes.empty() ? 0 : g->passes.back().chunk0 + g->passes.back().nchunk;
-    HIPCHK(g->events(EV_BASE + EV_PER_CHUNK * (size_t)(chunk0 + nchunk)));
-    if (oz) { int32_t rc = oz_planes_of_w(g); if (rc) return rc; }
-    // the bound pass on a short plan: its own planes of the first 256·rblocks rows of W, row scales and guards — rebuilt every call (one
-    // row-scale and one quantiser launch over R × R; appends, abo_update, a changed R and shared factor storage would all have to
-    // invalidate a cache)
-    const bool head32 = o.head32 && tail32 && rblocks > 0 && oz && (int64_t)256 * rblocks <= g->npts && 256 * rblocks <= 2048;
-    const int nb = rblocks > 0 && !head32 ? prune_bound_moduli() : 0;
-    const bool shortp = nb > 0 && nb != g->oz_plan.n;
-    const double sf2k = g->p_out > 1 ? (pc > 1 ? 2.0 : 1.5) * g->prm.sigma_f2 : g->prm.sigma_f2;
-    if (shortp) {
-        if (g->oz_plan_b.n != nb && !oz_make_plan(nb, &g->oz_plan_b)) return fail(ABO_EINVAL, "bound pass: %d moduli not supported", nb);
-        const int rows = 256 * rblocks;
-        const int64_t q = pad_up(Np, 256);
-        HIPCHK(g->oz_WRb.ensure((size_t)nb * rows * q));
-        HIPCHK(g->oz_sexpb.ensure(sizeof(int) * rows));
-        HIPCHK(g->oz_badrb.ensure(sizeof(int) * rows));
-        HIPCHK(g->oz_delta.ensure(sizeof(double) * rows));
-        const int bK = oz_bound_kbits(g->oz_plan_b.eP, rows);
-        g->pb_sK = oz_k_scale(sf2k, bK);
-        g->pb_rows = rows;
-        HIPCHK(oz_prepare_w_bound(g->oz_plan_b, g->oz_plan, g->st->W.as<double>(), g->st->cap, (int)Np, (int)g->N, rows, bK, g->pb_sK,
-                                  oz_k_scale(sf2k), sf2k * (1.0 + 0x1p-40), g->oz_WRb.as<int8_t>(), g->oz_sexpb.as<int>(), g->oz_badrb.as<int>(),
-                                  g->oz_delta.as<double>(), s));
-    } else if (rblocks > 0) g->pb_rows = 0;
-    if (rblocks > 0) g->ph_rows = head32 ? 256 * rblocks : 0;
-    const OzPlan& plan = shortp ? g->oz_plan_b : g->oz_plan;
-    g->passes.push_back({chunk0, nchunk, M, rblocks > 0 && (int64_t)256 * rblocks < g->N ? (int64_t)256 * rblocks : g->N, oz && !head32 ? plan.n : 0, head32});
-    g->tm.contraction_engine = want_var ? (oz ? ABO_CONTRACT_INT8 : ABO_CONTRACT_FP64) : 0;
-    g->tm.oz_nmod = oz ? g->oz_plan.n : 0;
-    // (prune_plan: fewer row blocks than the model has, so the tail is never empty)
-    if (rblocks > 0) HIPCHK(launch_tail_norms(g->st->Xs.as<double>(), g->alpha.as<double>(), (int)g->npts, g->dp, 256 * rblocks, g->pr_nrm.as<double>(), s));
-    if (head32) {
-        const int rows = 256 * rblocks;
-        HIPCHK(g->pr_head.ensure(sizeof(double) * M));
-        HIPCHK(g->pr_ssq.ensure(sizeof(double) * M));
-        HIPCHK(g->pr_wf.ensure(sizeof(float) * rows * rows));
-        HIPCHK(g->pr_hdl.ensure(sizeof(double) * 2 * rows));
-        KgenHead32Args ha{};
-        ha.Xs = g->st->Xs.as<double>(); ha.Z = Zd; ha.alpha = g->alpha.as<double>(); ha.W = g->st->W.as<double>(); ha.ldw = g->st->cap;
-        ha.Wf = g->pr_wf.as<float>(); ha.delta = g->pr_hdl.as<double>(); ha.l1 = g->pr_hdl.as<double>() + rows;
-        ha.head = g->pr_head.as<double>(); ha.ssq = g->pr_ssq.as<double>();
-        ha.M = M; ha.N = (int)g->npts; ha.Np = (int)Np; ha.R = rows; ha.d = g->d; ha.dp = g->dp; ha.family = g->prm.family;
-        ha.s = 1.0 / g->prm.ell; ha.sigma_f2 = g->prm.sigma_f2; ha.mean_c = g->prm.mean_c;
-        // what δ covers of the FULL pass: its plan's exponent budget, the scale of its image of K, its reconstruction error
-        ha.eP_full = g->oz_plan.eP; ha.sK_full = oz_k_scale(sf2k);
-        ha.rec_full = (128.0 * g->oz_plan.n * g->oz_plan.n + 256.0 * g->oz_plan.n) * std::ldexp(1.0, g->oz_plan.eP - 91);
-        hipEvent_t* e0 = &g->evs()[EV_BASE + EV_PER_CHUNK * chunk0];
-        PHASE_EVENT(e0[2], s);
-        HIPCHK(launch_kgen_head32(ha, s));
-        PHASE_EVENT(e0[3], s);
-        g->tm.var_gemm_launches += 1;
-    }
-    for (int64_t c = 0; c < nchunk; ++c) {
-        const int64_t j0 = c * Mc;
-        const int64_t m = (M - j0) < Mc ? (M - j0) : Mc;
-        const int mcp = (int)pad_up(m, TB);
-        hipEvent_t* e = &g->evs()[EV_BASE + EV_PER_CHUNK * (chunk0 + c)];
-        KgenArgs ka{};
-        double* kchunk = kstore ? kstore + j0 * ldstore : g->Kxz.as<double>();
-        const int64_t ldk = kstore ? ldstore : Np;
-        ka.Xs = g->st->Xs.as<double>(); ka.Z = Zd; ka.alpha = g->alpha.as<double>(); ka.Kout = kchunk;
-        ka.mu = g->mu_c.as<double>(); ka.ldk = ldk; ka.M = Mpts; ka.j0 = j0; ka.Mc = mcp; ka.N = (int)g->npts;
-        ka.pt = g->p_out; ka.pc = pc; ka.point_major = point_major;
-        for (int q = 0; q < MAX_P; ++q) ka.mean_vec[q] = g->mean_vec[q];
-        ka.Np = (int)Np; ka.d = g->d; ka.dp = g->dp; ka.family = g->prm.family; ka.s = 1.0 / g->prm.ell;
-        ka.sigma_f2 = g->prm.sigma_f2; ka.mean_c = g->prm.mean_c;
-        // int8 engine: the generator writes the residue planes of the chunk itself (the fp64 K_XZ is then only materialised for a
-        // caller that keeps it — the resident K_ZX of a candidate set)
-        ka.res_kmax = 256 * rblocks;
-        const bool fused = oz && kgen_writes_residues(ka, plan.n);
-        if (fused) {
-            const int64_t q = pad_up(Np, 256);
-            ka.res = g->oz_KR.as<int8_t>(); ka.res_ld = q; ka.res_plane = pad_up(mcp, 256) * q;
-            // (a gradient-enhanced model's scaled chunk is bounded by σ_f²·√2, its all-output chunk by 2σ_f²: the exponent the
-            // contraction below is told, oa.sK)
-            ka.res_bad = g->oz_badc.as<int>(); ka.res_n = plan.n;
-            ka.res_sK = shortp ? g->pb_sK : oz_k_scale(sf2k);
-            ka.res_ktg = oz_grad_exp(g);
-            if (!kstore) ka.Kout = nullptr;
-        } else ka.res_kmax = 0;
-        PHASE_EVENT(e[0], s);
-        if (!head32) HIPCHK(launch_kgen(ka, s));
-        if (rblocks > 0) {
-            KgenTailArgs kt{};
-            kt.Xs = ka.Xs; kt.Z = Zd; kt.alpha = ka.alpha; kt.norms = g->pr_nrm.as<double>();
-            kt.mu_tail = mut.as<double>(); kt.eps = eps.as<double>();
-            kt.M = Mpts; kt.j0 = j0; kt.Mc = mcp; kt.N = (int)g->npts; kt.Np = (int)Np; kt.k0 = ka.res_kmax; kt.d = g->d; kt.dp = g->dp; kt.family = ka.family;
-            kt.s = ka.s; kt.sigma_f2 = ka.sigma_f2; kt.mean_c = ka.mean_c;
-            HIPCHK(tail32 ? launch_kgen_tail32(kt, s) : launch_kgen_tail(kt, s));
-        }
-        PHASE_EVENT(e[1], s);
-        if (head32) {
-            // (head and sum of squares of every candidate are there already)
-        } else if (oz) {
-            OzVarArgs oa{};
-            oa.plan = &plan; oa.Kxz = kchunk; oa.ldk = ldk; oa.WR = g->oz_WR.as<int8_t>(); oa.sexp = g->oz_sexp.as<int>();
-            oa.bad_row = g->oz_badr.as<int>(); oa.KR = g->oz_KR.as<int8_t>(); oa.U = g->oz_U.as<int8_t>();
-            oa.bad_col = g->oz_badc.as<int>(); oa.ctr_clean = &g->oz_ctr_clean; oa.partial = g->partial.as<double>(); oa.ldp = Mc; oa.Np = (int)Np; oa.Mc = mcp;
-            if (shortp) {           // the short plan's planes of W (row stride of the full planes), scales, flags and guards
-                oa.WR = g->oz_WRb.as<int8_t>(); oa.sexp = g->oz_sexpb.as<int>(); oa.bad_row = g->oz_badrb.as<int>();
-                oa.delta = g->oz_delta.as<double>(); oa.w_plane = (int64_t)256 * rblocks * pad_up(Np, 256);
-            }
-            // a gradient-enhanced model's scaled chunk is bounded by σ_f²·√2 (oz_prepare_w), a StandardGP's by σ_f²
-            // (derivative candidates against derivative training rows, both scaled: 2σ_f²)
-            oa.nvalid = (int)g->N; oa.sK = shortp ? g->pb_sK : oz_k_scale(sf2k);
-            oa.kper = g->p_out; oa.ktg = oz_grad_exp(g);
-            if (pc > 1) { oa.rmode = point_major ? 1 : 2; oa.rper = pc; oa.r0 = j0; oa.rpts = Mpts; }
-            oa.ev_quant = phase_events() ? e[6] : nullptr; oa.ev_gemm = phase_events() ? e[7] : nullptr; oa.planes_ready = fused ? 1 : 0;
-            oa.rblocks = rblocks;
-            PHASE_EVENT(e[2], s);
-            HIPCHK(launch_var_ozaki(oa, s));
-            PHASE_EVENT(e[3], s);
-            g->tm.var_gemm_launches += 1;
-        } else if (want_var) {
-            VarGemmArgs va{};
-            va.W = g->st->W.as<double>(); va.Kxz = kchunk; va.partial = g->partial.as<double>();
-            va.ldw = g->st->cap; va.ldk = ldk; va.ldp = Mc; va.Np = (int)Np; va.Mc = mcp; va.nvalid = (int)g->N;
-            PHASE_EVENT(e[2], s);
-            HIPCHK(launch_var_gemm(va, s));
-            PHASE_EVENT(e[3], s);
-            g->tm.var_gemm_launches += 1;
-        }
-        FinalizeArgs fa{};
-        fa.partial = g->partial.as<double>(); fa.mu_in = g->mu_c.as<double>(); fa.mu_out = mu_out;
-        fa.var_out = var_out; fa.score_out = score_out; fa.ldp = Mc; fa.j0 = j0; fa.M = M;
-        fa.T = (var_out || score_out) && !head32 ? (rblocks > 0 && 2 * rblocks < T ? 2 * rblocks : T) : 0; fa.Mc = mcp; fa.kind = kind; fa.sigma_f2 = g->prm.sigma_f2;
-        fa.p0 = p0; fa.best_y = best_y;
-        fa.prior_grad = grad_prior_var(g); fa.pc = pc; fa.point_major = point_major; fa.Mpts = Mpts;
-        if (rblocks > 0) { fa.mu_tail = mut.as<double>(); fa.mu_eps = eps.as<double>(); }
-        if (head32) { fa.head_g = g->pr_head.as<double>(); fa.ssq_g = g->pr_ssq.as<double>(); }
-        PHASE_EVENT(e[4], s);
-        HIPCHK(launch_finalize(fa, s));
-        PHASE_EVENT(e[5], s);
-    }
-    return ABO_OK;
-}
-
-// Gradient-enhanced model: per-point posterior mean of all P outputs (mu_d [M][P]), P×P covariance block (cov_d [M][P][P]) and
-// GradientNormUCB score (sc_d [M]) of M points in DEVICE memory (any output may be null) — queued on the handle's stream, no
-// synchronisation.  The arithmetic behind abo_predict_grad_cov (GradientGP.jl:936-971, gradNormUCB.jl:43-51) and behind the
-// refinement rounds of a gradient-enhanced handle (refine.hip: launch_refine_lockstep_grad).
-int32_t grad_eval_device(abo_gp* g, const double* Zd, int64_t M, double beta, double* mu_d, double* cov_d, double* sc_d) {
-    hipStream_t s = g->stream;
-    const int P = g->p_out;
-    const int64_t Np = g->Np;
-    // points per chunk: V chunk (rows·Np doubles) ≤ 256 MiB, rows padded to 128
-    int64_t pts = (((int64_t)1 << 28) / (Np * (int64_t)sizeof(double))) / P;
-    if (pts < 1) pts = 1;
-    if (pts > M) pts = M;
-    const int64_t rows_pad = pad_up(pts * P, TB);
-    // V = L⁻¹K_XZ on the int8-residue engine when the handle's contraction says so (same rule as the variance calls): the residue
-    // GEMMs and a reconstruction that writes V itself; a chunk whose scratch the device cannot give runs on the fp64 GEMM
-    int nm = 0;
-    bool oz = wants_int8(g, true, P, &nm);
-    if (oz) {
-        int64_t mc = rows_pad;
-        int32_t rc = oz_acquire(g, nm, rows_pad, &mc, &oz);
-        if (rc) return rc;
-        if (oz && mc != rows_pad) oz = false;
-    }
-    HIPCHK(g->events(EV_BASE));
-    g->oz_prepare_pending = false;
-    if (oz) { int32_t rc = oz_planes_of_w(g); if (rc) return rc; }
-    g->tm.contraction_engine = oz ? ABO_CONTRACT_INT8 : ABO_CONTRACT_FP64;
-    g->tm.oz_nmod = oz ? g->oz_plan.n : 0;
-    // int8 engine: the generator writes the residue planes of the chunk itself; the fp64 chunk is then not materialised
-    bool fused = false;
-    if (oz) {
-        KgenArgs probe{};
-        probe.pt = P; probe.dp = g->dp;
-        fused = kgen_writes_residues(probe, g->oz_plan.n);
-    }
-    if (!fused) HIPCHK(g->Kxz.ensure(sizeof(double) * rows_pad * Np));
-    HIPCHK(g->partial.ensure(sizeof(double) * rows_pad * Np));       // V
-    HIPCHK(g->mu_c.ensure(sizeof(double) * rows_pad));
-    for (int64_t p0 = 0; p0 < M; p0 += pts) {
-        const int64_t np = (M - p0) < pts ? (M - p0) : pts;
-        const int rows = (int)pad_up(np * P, TB);
-        KgenArgs ka{};
-        ka.Xs = g->st->Xs.as<double>(); ka.Z = Zd; ka.alpha = g->alpha.as<double>(); ka.Kout = g->Kxz.as<double>();
-        ka.mu = g->mu_c.as<double>(); ka.ldk = Np; ka.M = M; ka.j0 = p0 * P; ka.Mc = rows; ka.N = (int)g->npts;
-        ka.Np = (int)Np; ka.d = g->d; ka.dp = g->dp; ka.family = g->prm.family; ka.s = 1.0 / g->prm.ell;
-        ka.sigma_f2 = g->prm.sigma_f2; ka.pt = P; ka.pc = P; ka.point_major = 1;
-        for (int q = 0; q < MAX_P; ++q) ka.mean_vec[q] = g->mean_vec[q];
-        if (fused) {
-            const int64_t q256 = pad_up(Np, 256);
-            ka.Kout = nullptr;
-            ka.res = g->oz_KR.as<int8_t>(); ka.res_ld = q256; ka.res_plane = pad_up(rows, 256) * q256;
-            ka.res_bad = g->oz_badc.as<int>(); ka.res_n = g->oz_plan.n; ka.res_sK = oz_k_scale(2.0 * g->prm.sigma_f2);
-            ka.res_ktg = oz_grad_exp(g);
-        }
-        HIPCHK(launch_kgen(ka, s));
-        if (oz) {
-            OzVarArgs oa{};
-            oa.plan = &g->oz_plan; oa.Kxz = g->Kxz.as<double>(); oa.ldk = Np; oa.WR = g->oz_WR.as<int8_t>(); oa.sexp = g->oz_sexp.as<int>();
-            oa.bad_row = g->oz_badr.as<int>(); oa.KR = g->oz_KR.as<int8_t>(); oa.U = g->oz_U.as<int8_t>();
-            oa.bad_col = g->oz_badc.as<int>(); oa.ctr_clean = &g->oz_ctr_clean; oa.partial = nullptr; oa.ldp = 0; oa.Np = (int)Np; oa.Mc = rows;
-            oa.nvalid = (int)g->N; oa.sK = oz_k_scale(2.0 * g->prm.sigma_f2);
-            oa.kper = P; oa.ktg = oz_grad_exp(g); oa.planes_ready = fused ? 1 : 0;
-            oa.rmode = 1; oa.rper = P; oa.r0 = p0 * P; oa.rpts = M;
-            oa.Vout = g->partial.as<double>(); oa.ldv = Np;
-            HIPCHK(launch_var_ozaki(oa, s));
-        } else {
-            GemmArgs a{};           // V[row][i] = Σ_k Kxz[row][k]·W[i][k]
-            a.A = g->Kxz.as<double>(); a.lda = Np; a.B = g->st->W.as<double>(); a.ldb = g->st->cap;
-            a.C = g->partial.as<double>(); a.ldc = Np; a.M = rows; a.N = (int)Np; a.K = (int)Np;
-            a.kmode = K_B_LOWER; a.batch = 1; a.alpha = 1.0; a.beta = 0.0;       // W[i][k] = 0 for k > i: half the product
-            HIPCHK(launch_gemm_nt(a, s));
-        }
-        GradCovArgs ca{};
-        ca.V = g->partial.as<double>(); ca.mu_rows = g->mu_c.as<double>(); ca.ldv = Np; ca.R = (int)g->N; ca.p = P;
-        ca.pt0 = p0; ca.prior0 = g->prm.sigma_f2; ca.prior_g = grad_prior_var(g); ca.beta = beta;
-        ca.cov_out = cov_d; ca.mu_out = mu_d; ca.score_out = sc_d;
-        HIPCHK(launch_grad_cov(ca, (int)np, s));
-    }
-    return ABO_OK;
-}
-
-// phase times and algorithmic work of the call's posterior passes (what was launched: a bound pass counts its R rows, a survivor pass
-// its survivors — with ONE exception: survivors whose scores were taken from the threshold pass, prune_select step 4, are counted as if
-// their pass had been launched; the pass of no chunks that stands for them adds work and no time)
-void collect_posterior_timings(abo_gp* g, bool with_var) {
-    double kx = 0, vg = 0, fi = 0, oq = 0, og = 0, oc = 0, work = 0, ozops = 0;
-    const bool oz = with_var && g->tm.contraction_engine == ABO_CONTRACT_INT8;
-    for (const abo_gp::PostPass& ps : g->passes) {
-        for (int64_t c = 0; phase_events() && c < ps.nchunk; ++c) {
-            hipEvent_t* e = &g->evs()[EV_BASE + EV_PER_CHUNK * (ps.chunk0 + c)];
-            kx += ev_ms(e[0], e[1]);
-            // (a fused first-level head: one launch, timed in the first chunk's slot — the other chunks' slots hold older calls' events)
-            if (with_var && (!ps.head32 || c == 0)) vg += ev_ms(e[2], e[3]);
-            if (oz && !ps.head32) { oq += ev_ms(e[2], e[6]); og += ev_ms(e[6], e[7]); oc += ev_ms(e[7], e[3]); }
-            fi += ev_ms(e[4], e[5]);
-        }
-        work += (double)ps.rows * (double)ps.rows * (double)ps.M;
-        ozops += (double)ps.nmod * (double)ps.rows * (double)ps.rows * (double)ps.M;
-    }
-    g->tm.acq_kxz_ms = kx;
-    g->tm.acq_var_gemm_ms = vg;
-    g->tm.acq_finalize_ms = fi;
-    g->tm.oz_quant_ms = oq; g->tm.oz_gemm_ms = og; g->tm.oz_crt_ms = oc;
-    if (g->oz_prepare_pending) { g->tm.oz_prepare_ms = phase_events() ? ev_ms(g->evs()[8], g->evs()[9]) : 0.0; g->oz_prepare_pending = false; }
-    // ALGORITHMIC int8 operations of the residue GEMMs: n moduli × the triangular product R²·M per pass (R(R+1)/2 multiply-adds per
-    // candidate over the R rows of W the pass contracts — R = N but for a bound pass —, 2 operations each ≈ R²).  What the kernel issues
-    // beyond that — the upper halves of its 256-wide diagonal blocks (of which it skips 6 of 16 units), padding of N and M to 256 — is
-    // not credited.  The moduli are those each pass launched: a bound pass on its short plan counts that plan's.
-    g->tm.oz_gemm_ops = oz ? ozops : 0.0;
-    // algorithmic (triangular) flop of the contraction: R²·M per pass
-    g->tm.var_gemm_flop = with_var ? work : 0.0;
 }
 
 }  // namespace
@@ -1055,9 +602,6 @@ int32_t check_fitted(abo_gp* g, int32_t d) {
     if (d != g->d) return fail(ABO_EDIM, "DimensionMismatch: candidate dimension %d, model dimension %d", d, g->d);
     return ABO_OK;
 }
-}  // namespace abo
-
-namespace {
 
 int32_t stage_candidates(abo_gp* g, const double* Z, int64_t M, int32_t z_space, const double** Zd) {
     if (z_space == ABO_DEVICE) { *Zd = Z; return ABO_OK; }
@@ -1066,6 +610,9 @@ int32_t stage_candidates(abo_gp* g, const double* Z, int64_t M, int32_t z_space,
     *Zd = g->Zdev.as<double>();
     return ABO_OK;
 }
+}  // namespace abo
+
+namespace {
 
 // Full refit into a fresh Storage of capacity max(N, n_max) points.  X/y: caller buffers (host or device).
 // Gradient-enhanced models (p_out > 1): y holds p_out values per point, by outputs at the ABI (y[q·N + i]) or — internal
@@ -1251,6 +798,7 @@ int32_t append_impl(abo_gp* g, abo_gp* n, const double* x, double y, int64_t* in
     // only rows/columns < N: anything beyond may be the stale remains of a discarded branch
     tl_phase_np = Np1;
     const bool timed = phase_events();
+    // (scratch slots EV_BASE + 0 … 1: begin and end of the two mat-vecs — an append runs no posterior pass)
     if (timed) { HIPCHK(n->events(EV_BASE + 2)); HIPCHK(hipEventRecord(n->evs()[EV_BASE], s)); }
     HIPCHK(launch_trmv(st->W.as<double>(), ld, krow, lvec, (int)N, 1, s));
     HIPCHK(launch_trmv(st->WT.as<double>(), ld, lvec, vvec, (int)N, 0, s));
@@ -1336,11 +884,10 @@ int32_t append_grad_impl(abo_gp* g, abo_gp* n, const double* x, const double* yv
     const double* alpha_cur = g->alpha.as<double>();
     for (int q = 0; q < P; ++q) {
         const int64_t Rq = R + q;                          // rows in front of the one being appended
-        KgenArgs ka{};
-        ka.Xs = st->Xs.as<double>(); ka.Z = Xraw + npts * d; ka.alpha = nullptr; ka.Kout = krow; ka.mu = nullptr;
-        ka.ldk = ld; ka.M = 1; ka.j0 = q; ka.Mc = 16; ka.N = (int)(npts + 1); ka.Np = (int)pad_up(Rq, TB); ka.d = d; ka.dp = st->dp;
-        ka.family = g->prm.family; ka.s = 1.0 / g->prm.ell; ka.sigma_f2 = g->prm.sigma_f2; ka.mean_c = 0.0;
-        ka.pt = P; ka.pc = P; ka.point_major = 1; ka.rvalid = (int)Rq;
+        KgenArgs ka = kgen_model_args(g, false);           // the old view's model (same storage, same kernel) …
+        ka.N = (int)(npts + 1); ka.Np = (int)pad_up(Rq, TB); ka.rvalid = (int)Rq;      // … with the partly appended point
+        ka.Z = Xraw + npts * d; ka.Kout = krow; ka.ldk = ld; ka.M = 1; ka.j0 = q; ka.Mc = 16;
+        ka.pc = P; ka.point_major = 1;
         HIPCHK(launch_kgen(ka, s));
         HIPCHK(launch_trmv(st->W.as<double>(), ld, krow, lvec, (int)Rq, 1, s));
         HIPCHK(launch_trmv(st->WT.as<double>(), ld, lvec, vvec, (int)Rq, 0, s));
@@ -1508,7 +1055,7 @@ int32_t abo_create(const abo_params* params, abo_gp** out) {
         else (void)hipGetLastError();
     }
     g->stream = g->ctx->stream;
-    e = g->events(8);
+    e = g->events(EV_ACQ_END + 1);
     if (e != hipSuccess) { g->free_all(); delete g; return fail(ABO_EHIP, "hipEventCreate: %s", hipGetErrorString(e)); }
     *out = g;
     return ABO_OK;
@@ -1686,536 +1233,7 @@ int32_t abo_remove(abo_gp* g, const int64_t* idx, int32_t k, int32_t* path, abo_
     return ABO_OK;
 }
 
-int32_t abo_predict(abo_gp* g, const double* Z, int64_t M, int32_t d, int32_t z_space, double* mu, double* var,
-                    int32_t out_space) {
-    int32_t rc = check_fitted(g, d);
-    if (rc) return rc;
-    if (M < 0 || (M > 0 && !Z)) return fail(ABO_EINVAL, "abo_predict: bad candidate buffer");
-    if (M == 0) return ABO_OK;
-    HIPCHK(hipSetDevice(g->prm.device));
-    hipStream_t s = g->stream;
-    const double* Zd = nullptr;
-    rc = stage_candidates(g, Z, M, z_space, &Zd);
-    if (rc) return rc;
-    double* mu_d = nullptr;
-    double* var_d = nullptr;
-    if (mu) {
-        if (out_space == ABO_DEVICE) mu_d = mu;
-        else { HIPCHK(g->mu_all.ensure(sizeof(double) * M)); mu_d = g->mu_all.as<double>(); }
-    }
-    if (var) {
-        if (out_space == ABO_DEVICE) var_d = var;
-        else { HIPCHK(g->var_all.ensure(sizeof(double) * M)); var_d = g->var_all.as<double>(); }
-    }
-    HIPCHK(hipEventRecord(g->evs()[5], s));
-    rc = posterior(g, Zd, M, -1, 0.0, 0.0, mu_d, var_d, nullptr);
-    if (rc) return rc;
-    HIPCHK(hipEventRecord(g->evs()[6], s));
-    if (mu && out_space == ABO_HOST) { rc = copy_out(mu, mu_d, sizeof(double) * M, ABO_HOST, s); if (rc) return rc; }
-    if (var && out_space == ABO_HOST) { rc = copy_out(var, var_d, sizeof(double) * M, ABO_HOST, s); if (rc) return rc; }
-    HIPCHK(wait_stream(s));
-    collect_posterior_timings(g, var != nullptr);
-    g->tm.acq_topk_ms = 0.0;
-    g->tm.acq_total_ms = ev_ms(g->evs()[5], g->evs()[6]);
-    return ABO_OK;
-}
-
-int32_t abo_predict_grad(abo_gp* g, const double* Z, int64_t M, int32_t d, int32_t z_space, double* mu, double* var,
-                         int32_t out_space) {
-    int32_t rc = check_fitted(g, d);
-    if (rc) return rc;
-    if (g->p_out < 2) return fail(ABO_EINVAL, "abo_predict_grad: the model has no gradient outputs");
-    if (M < 0 || (M > 0 && !Z)) return fail(ABO_EINVAL, "abo_predict_grad: bad candidate buffer");
-    if (M == 0) return ABO_OK;
-    HIPCHK(hipSetDevice(g->prm.device));
-    hipStream_t s = g->stream;
-    const int P = g->p_out;
-    const double* Zd = nullptr;
-    rc = stage_candidates(g, Z, M, z_space, &Zd);
-    if (rc) return rc;
-    double* mu_d = nullptr;
-    double* var_d = nullptr;
-    if (mu) { if (out_space == ABO_DEVICE) mu_d = mu; else { HIPCHK(g->mu_all.ensure(sizeof(double) * M * P)); mu_d = g->mu_all.as<double>(); } }
-    if (var) { if (out_space == ABO_DEVICE) var_d = var; else { HIPCHK(g->var_all.ensure(sizeof(double) * M * P)); var_d = g->var_all.as<double>(); } }
-    PostOpts all_outputs;
-    all_outputs.pc = P;
-    rc = posterior(g, Zd, M, -1, 0.0, 0.0, mu_d, var_d, nullptr, all_outputs);
-    if (rc) return rc;
-    if (mu && out_space == ABO_HOST) { rc = copy_out(mu, mu_d, sizeof(double) * M * P, ABO_HOST, s); if (rc) return rc; }
-    if (var && out_space == ABO_HOST) { rc = copy_out(var, var_d, sizeof(double) * M * P, ABO_HOST, s); if (rc) return rc; }
-    HIPCHK(wait_stream(s));
-    return ABO_OK;
-}
-
-int32_t abo_predict_grad_cov(abo_gp* g, const double* Z, int64_t M, int32_t d, int32_t z_space, double beta, double* mu,
-                             double* cov, double* score, int32_t out_space) {
-    int32_t rc = check_fitted(g, d);
-    if (rc) return rc;
-    if (g->p_out < 2) return fail(ABO_EINVAL, "abo_predict_grad_cov: the model has no gradient outputs");
-    if (M < 0 || (M > 0 && !Z)) return fail(ABO_EINVAL, "abo_predict_grad_cov: bad candidate buffer");
-    if (M == 0) return ABO_OK;
-    HIPCHK(hipSetDevice(g->prm.device));
-    hipStream_t s = g->stream;
-    const int P = g->p_out;
-    const double* Zd = nullptr;
-    rc = stage_candidates(g, Z, M, z_space, &Zd);
-    if (rc) return rc;
-    double* mu_d = nullptr; double* cov_d = nullptr; double* sc_d = nullptr;
-    if (mu) { if (out_space == ABO_DEVICE) mu_d = mu; else { HIPCHK(g->mu_all.ensure(sizeof(double) * M * P)); mu_d = g->mu_all.as<double>(); } }
-    if (cov) { if (out_space == ABO_DEVICE) cov_d = cov; else { HIPCHK(g->var_all.ensure(sizeof(double) * M * P * P)); cov_d = g->var_all.as<double>(); } }
-    if (score) { if (out_space == ABO_DEVICE) sc_d = score; else { HIPCHK(g->score_all.ensure(sizeof(double) * M)); sc_d = g->score_all.as<double>(); } }
-    rc = grad_eval_device(g, Zd, M, beta, mu_d, cov_d, sc_d);
-    if (rc) return rc;
-    if (mu && out_space == ABO_HOST) { rc = copy_out(mu, mu_d, sizeof(double) * M * P, ABO_HOST, s); if (rc) return rc; }
-    if (cov && out_space == ABO_HOST) { rc = copy_out(cov, cov_d, sizeof(double) * M * P * P, ABO_HOST, s); if (rc) return rc; }
-    if (score && out_space == ABO_HOST) { rc = copy_out(score, sc_d, sizeof(double) * M, ABO_HOST, s); if (rc) return rc; }
-    HIPCHK(wait_stream(s));
-    return ABO_OK;
-}
-
-int32_t abo_acq(abo_gp* g, const double* Z, int64_t M, int32_t d, int32_t z_space, int32_t kind, double p0,
-                double best_y, int64_t idx_base, double* scores, int32_t k, double* top_val, int64_t* top_idx,
-                int32_t out_space) {
-    return abo::acq_ex(g, Z, M, d, z_space, kind, p0, best_y, idx_base, scores, out_space, k, top_val, top_idx, out_space);
-}
-
 }  // extern "C"
-
-namespace abo {    // shared with test_hooks.hip (abo_state.h)
-// C-ABI terms → the kernels' form; validates kinds against the handle (GRADNORM_UCB needs gradient outputs)
-int32_t make_terms(const abo_gp* g, const abo_acq_term* terms, int32_t n, AcqTerms* out, const char* fn) {
-    if (!terms || n < 1) return fail(ABO_EINVAL, "%s: an objective needs at least one term", fn);
-    if (n > MAX_TERMS) return fail(ABO_EINVAL, "%s: %d terms, the library takes at most %d", fn, n, MAX_TERMS);
-    out->n = n;
-    for (int i = 0; i < n; ++i) {
-        const int k = terms[i].kind;
-        if (k == ABO_ACQ_MES) return fail(ABO_EINVAL, "%s: ABO_ACQ_MES (term %d) takes a vector of samples and is no member of a weighted sum: "
-                                                      "use the abo_*_mes entry points (abo_acq_mes, abo_refine_mes, …)", fn, i);
-        if (k < ABO_ACQ_EI || k > ABO_ACQ_LOGEI) return fail(ABO_EINVAL, "%s: unknown acquisition kind %d (term %d)", fn, k, i);
-        if (k == ABO_ACQ_GRADNORM_UCB && (!g || g->p_out < 2))
-            return fail(ABO_EINVAL, "%s: GradientNormUCB (term %d) needs a gradient-enhanced model", fn, i);
-        if (!(terms[i].weight == terms[i].weight)) return fail(ABO_EINVAL, "%s: weight of term %d is not a number", fn, i);
-        out->kind[i] = k; out->p0[i] = terms[i].p0; out->best_y[i] = terms[i].best_y; out->w[i] = terms[i].weight;
-    }
-    return ABO_OK;
-}
-}  // namespace abo
-
-namespace {
-
-AcqTerms one_term(int32_t kind, double p0, double best_y) {
-    AcqTerms t{};
-    t.n = 1; t.kind[0] = kind; t.p0[0] = p0; t.best_y[0] = best_y; t.w[0] = 1.0;
-    return t;
-}
-
-// scores of M device-resident candidates under the objective `t` into sc_d (device), queued on the handle's stream:
-//   one plain term            the fused posterior + epilogue pass (what abo_acq has always run: same bits)
-//   function-value terms      ONE posterior pass, then every member's epilogue on that μ, σ² (EnsembleAcq.jl:53-55)
-//   MES                       the same posterior pass, then the sum over the samples per candidate (misc.hip: score_mes_kernel)
-//   a GRADNORM_UCB term       the all-output posterior per point (mean[p], covariance block) in slabs, epilogue on those
-//   more: the call already ran posterior passes (a pruned selection that fell back): this one is counted next to them
-int32_t score_terms_device(abo_gp* g, const double* Zd, int64_t M, const AcqTerms& t, double* sc_d, bool more = false) {
-    hipStream_t s = g->stream;
-    if (terms_plain(t)) {
-        if (t.kind[0] != ABO_ACQ_MEAN) {
-            PostOpts o;
-            o.more = more;
-            return posterior(g, Zd, M, t.kind[0], t.p0[0], t.best_y[0], nullptr, nullptr, sc_d, o);
-        }
-        // −mu only: skip the contraction (scores come from the mean pass)
-        HIPCHK(g->mu_all.ensure(sizeof(double) * M));
-        int32_t rc = posterior(g, Zd, M, -1, 0.0, 0.0, g->mu_all.as<double>(), nullptr, nullptr);
-        if (rc) return rc;
-        FinalizeArgs fa{};
-        fa.partial = nullptr; fa.mu_in = g->mu_all.as<double>(); fa.score_out = sc_d; fa.ldp = 0; fa.j0 = 0; fa.M = M;
-        fa.T = 0; fa.Mc = (int)M; fa.kind = ABO_ACQ_MEAN; fa.sigma_f2 = g->prm.sigma_f2;
-        HIPCHK(launch_finalize(fa, s));
-        return ABO_OK;
-    }
-    if (!terms_have_gradnorm(t)) {
-        HIPCHK(g->mu_all.ensure(sizeof(double) * M));
-        HIPCHK(g->var_all.ensure(sizeof(double) * M));
-        int32_t rc = posterior(g, Zd, M, -1, 0.0, 0.0, g->mu_all.as<double>(), g->var_all.as<double>(), nullptr);
-        if (rc) return rc;
-        if (terms_mes(t))
-            HIPCHK(launch_score_mes(g->mu_all.as<double>(), g->var_all.as<double>(), M, t.ystar, t.n_ystar, sc_d, nullptr, nullptr, s));
-        else
-            HIPCHK(launch_score_terms(g->mu_all.as<double>(), g->var_all.as<double>(), sc_d, M, t, s));
-        return ABO_OK;
-    }
-    const int P = g->p_out;
-    int64_t slab = ((int64_t)64 << 20) / ((int64_t)sizeof(double) * P * P);       // ≤ 64 MiB of covariance blocks at a time
-    if (slab < 1) slab = 1;
-    if (slab > M) slab = M;
-    HIPCHK(g->mu_all.ensure(sizeof(double) * slab * P));
-    HIPCHK(g->var_all.ensure(sizeof(double) * slab * P * P));
-    for (int64_t j0 = 0; j0 < M; j0 += slab) {
-        const int64_t np = (M - j0) < slab ? (M - j0) : slab;
-        int32_t rc = grad_eval_device(g, Zd + j0 * g->d, np, 0.0, g->mu_all.as<double>(), g->var_all.as<double>(), nullptr);
-        if (rc) return rc;
-        HIPCHK(launch_score_terms_grad(g->mu_all.as<double>(), g->var_all.as<double>(), sc_d + j0, np, P, t, s));
-    }
-    return ABO_OK;
-}
-
-}  // namespace
-
-namespace abo {    // shared with test_hooks.hip (abo_state.h)
-// the overrides of abo_state.h: defined here, read below, written by test_hooks.hip alone
-std::atomic<int> g_prune_bound_moduli{0};
-std::atomic<int> g_prune_force_rblocks{0};
-std::atomic<int> g_prune_force_mode{0};
-std::atomic<int> g_prune_pre_rblocks{0};
-std::atomic<int64_t> g_prune_level2_min{-1};
-std::atomic<int> g_prune_tail32{-1};
-std::atomic<int> g_prune_head32{-1};
-std::atomic<int> g_prune_reuse{-1};
-}  // namespace abo
-
-namespace {
-
-// The mean's tail of the M-wide FIRST bound level in fp32 (kgen_tail32.hip).  ABO_PRUNE_TAIL32=0 (read once) keeps the fp64 tail
-// there, for A/B runs.  Every other bound pass — the second level, a single level — has the fp64 tail either way.
-bool prune_tail32() {
-    static const bool on = [] { const char* e = getenv("ABO_PRUNE_TAIL32"); return !(e && e[0] == '0'); }();
-    if (g_prune_tail32.load(std::memory_order_relaxed) >= 0) return g_prune_tail32.load(std::memory_order_relaxed) != 0;
-    return on;
-}
-
-// Survivors that the threshold pass has scored are not evaluated again (prune_select, step 4).  ABO_PRUNE_REUSE=0 (read once) runs the
-// survivor pass on them as before, for A/B runs.
-bool prune_reuse() {
-    static const bool on = [] { const char* e = getenv("ABO_PRUNE_REUSE"); return !(e && e[0] == '0'); }();
-    if (g_prune_reuse.load(std::memory_order_relaxed) >= 0) return g_prune_reuse.load(std::memory_order_relaxed) != 0;
-    return on;
-}
-
-// The head of that first level by the fused kernel of kgen_head32.hip — only where the fp32 tail runs, and not under an explicit moduli
-// request (ABO_PRUNE_BOUND_MODULI set, or its hook): that asks for the int8 engine.  ABO_PRUNE_HEAD32=0 (read once) keeps the fp32 tail
-// and runs the int8 head (generator planes, residue GEMM, reconstruction), for A/B runs.
-bool prune_head32() {
-    static const bool on = [] { const char* e = getenv("ABO_PRUNE_HEAD32"); return !(e && e[0] == '0'); }();
-    static const bool moduli_env = getenv("ABO_PRUNE_BOUND_MODULI") != nullptr;
-    if (moduli_env) return false;
-    if (g_prune_bound_moduli.load(std::memory_order_relaxed) != 0) return false;
-    if (g_prune_head32.load(std::memory_order_relaxed) >= 0) return g_prune_head32.load(std::memory_order_relaxed) != 0;
-    return on;
-}
-
-bool prune_enabled() {
-    static const bool on = [] { const char* e = getenv("ABO_ACQ_PRUNE"); return !(e && e[0] == '0'); }();
-    if (g_prune_force_mode.load(std::memory_order_relaxed) == 2) return false;
-    return on;
-}
-
-}  // namespace
-
-namespace abo {    // shared with test_hooks.hip (abo_state.h)
-// rows: factor rows N of the model; int8_fused: the int8-residue engine would run this call's contraction with generator-written planes
-PrunePlan prune_plan(int64_t rows, int64_t M, int k, bool want_scores, int kind, double p0, int p_out, bool int8_fused, int d) {
-    PrunePlan pp{false, 0, 0, 0, 0, 0};
-    const int64_t tblocks = (rows + 255) / 256;
-    // R = N/8, rounded to whole 256-row blocks: the bound pass then costs 1/64 of the contraction.  On the synthetic problem of the
-    // benchmark R = N/8, N/4, N/2 left 4 %, 2 %, 1 % of the candidates: R = N/4 would halve a survivor pass that costs 0.04 of the
-    // full one at four times a bound pass that costs 0.016 of it.
-    int rb = (int)((rows / 8 + 128) / 256);
-    if (rb < 1) rb = 1;
-    // Two levels: how many candidates a bound removes hardly depends on R — μ decides nearly all of it — while the
-    // pass's residue work grows with R (generator, reconstruction) and R² (GEMM).  So a first level of R₀ = N/32, rounded the same
-    // way, runs over all M and sets the threshold, and the N/8 pass above runs only on the S₁ candidates it leaves, at S₁/M of its
-    // cost: the survivor pass sees what it saw with one level.  (A narrow SINGLE level would not do: where N/8 leaves 4 % of the
-    // candidates, a narrower bound leaves more, and a 4 % survivor pass already costs twice what the narrower bound saves.)  Only where
-    // R₀ is fewer blocks than R — from N = 3072 on — and, under a forced R, only when the test hook asks for one.  Measured at C3:
-    // 312 survivors at N/32 against 172 at N/8, the call 24.1 → 17.8 ms (N/16: 207 survivors, 18.7 ms); N = 4096: 12.6 → 11.5 ms.
-    int rb0 = (int)((rows / 32 + 128) / 256);
-    if (rb0 < 1) rb0 = 1;
-    bool forced = false;
-    int pre = 0;
-    forced = g_prune_force_rblocks.load(std::memory_order_relaxed) > 0;
-    if (forced) rb = g_prune_force_rblocks.load(std::memory_order_relaxed);
-    pre = g_prune_pre_rblocks.load(std::memory_order_relaxed);
-    if (pre > 0) rb0 = pre;              // (a forced first level that is not below rblocks: an error the callers report)
-    else if (pre < 0 || forced || rb0 >= rb) rb0 = 0;
-    pp.rblocks = rb;
-    pp.rblocks0 = rb0;
-    pp.tail32 = rb0 > 0 && prune_tail32();
-    pp.head32 = pp.tail32 && prune_head32();
-    pp.reuse = prune_reuse();
-    pp.k0 = k > 0 ? ((int64_t)4 * k > 1024 ? (int64_t)4 * k : 1024) : 0;
-    // below 4·K0 survivors the full pass on them costs less than the ≈ 16 launches of another bound pass
-    pp.level2_min = 4 * pp.k0;
-    if (g_prune_level2_min.load(std::memory_order_relaxed) >= 0) pp.level2_min = g_prune_level2_min.load(std::memory_order_relaxed);
-    // the survivor pass costs S/M of the full pass it replaces (plus a gather of S points): it is the cheaper of the two for any
-    // S < M, and is taken while it saves at least an eighth of the pass — far more than the extra launches cost
-    pp.max_survivors = M - M / 8;
-    const bool monotone = kind == ABO_ACQ_EI || kind == ABO_ACQ_LOGEI || (kind == ABO_ACQ_UCB && p0 >= 0.0);
-    // two passes pay from a few times the K0 exactly evaluated candidates on (M ≥ 4·K0: the threshold pass is at most a quarter of
-    // what the selection can save); the compaction counts in ints and gathers with 32-bit element indices
-    pp.eligible = prune_enabled() && k > 0 && !want_scores && monotone && p_out == 1 && int8_fused && rb < tblocks &&
-                  M >= 4 * pp.k0 && M * (int64_t)d < ((int64_t)1 << 31);
-    return pp;
-}
-}  // namespace abo
-
-namespace {
-
-// The pruned selection on device candidates Zd.  *done = false: nothing selected (the engine was not available after all, or too many
-// candidates survived) — the caller runs the ordinary pass, with more = true when passes were launched here.
-int32_t prune_select(abo_gp* g, const double* Zd, int64_t M, const AcqTerms& t, const PrunePlan& pp, int64_t idx_base, int32_t k,
-                     TopkWork w, double* tv, int64_t* ti, bool* done) {
-    hipStream_t s = g->stream;
-    const int d = g->d;
-    const int kind = t.kind[0];
-    const double p0 = t.p0[0], best_y = t.best_y[0];
-    const int64_t K0 = pp.k0;
-    *done = false;
-    const int64_t nb = (M + PRUNE_SCAN_E - 1) / PRUNE_SCAN_E;
-    HIPCHK(g->pr_ub.ensure(sizeof(double) * M));
-    HIPCHK(g->pr_z.ensure(sizeof(double) * K0 * d));
-    HIPCHK(g->pr_sc.ensure(sizeof(double) * 2 * K0));            // the threshold pass's scores, then those of ≤ K0 survivors taken from them
-    HIPCHK(g->pr_sel.ensure(sizeof(int64_t) * M));
-    HIPCHK(g->pr_blk.ensure(sizeof(int) * nb + 16));
-    HIPCHK(g->pr_tv.ensure(sizeof(double) * (K0 + 3)));          // K0 values, then {survivor count, −Inf (test hook), the reuse's "not found" flag}
-    HIPCHK(g->pr_ti.ensure(sizeof(int64_t) * K0));
-    HIPCHK(g->pr_ti0.ensure(sizeof(int64_t) * K0));              // the threshold pass's K0 candidates
-    g->pr_reused = false;
-    double* ub = g->pr_ub.as<double>();
-    int64_t* count_d = reinterpret_cast<int64_t*>(g->pr_tv.as<double>() + K0);
-    HIPCHK(g->events(EV_BASE));
-    constexpr size_t PE = 10;          // events 10-13, by index: the passes below may grow (and move) the context's event list
-    // 1. bound pass: the chunk pipeline on the first row blocks of W — those of the first level where the plan has one
-    const bool two_levels = pp.rblocks0 > 0;
-    HIPCHK(hipEventRecord(g->evs()[PE], s));
-    // (a first level's looser mean costs survivors alone, and the second level is there when they are many; a single level has no such net)
-    PostOpts bound;
-    bound.rblocks = two_levels ? pp.rblocks0 : pp.rblocks; bound.tail32 = pp.tail32; bound.head32 = pp.head32;
-    int32_t rc = posterior(g, Zd, M, kind, p0, best_y, nullptr, nullptr, ub, bound);
-    if (rc == PRUNE_UNAVAILABLE) return ABO_OK;
-    if (rc) return rc;
-    g->pst.bound_rows = g->passes.back().rows;
-    g->pst.k0 = K0;
-    HIPCHK(hipEventRecord(g->evs()[PE + 1], s));
-    // 2. threshold: exact scores of the K0 best by bound (NaN bounds first, as everywhere), τ = the k-th best of them
-    HIPCHK(launch_topk(ub, M, (int)K0, 0, w, g->pr_tv.as<double>(), g->pr_ti.as<int64_t>(), s));
-    HIPCHK(launch_gather_points(Zd, g->pr_ti.as<int64_t>(), 0, (int)K0, d, g->pr_z.as<double>(), s));
-    PostOpts further;
-    further.more = true;
-    rc = posterior(g, g->pr_z.as<double>(), K0, kind, p0, best_y, nullptr, nullptr, g->pr_sc.as<double>(), further);
-    if (rc) return rc;
-    // (the selection below overwrites pr_ti: the candidates that pr_sc's scores belong to are kept for step 4)
-    if (pp.reuse) HIPCHK(hipMemcpyAsync(g->pr_ti0.p, g->pr_ti.p, sizeof(int64_t) * K0, hipMemcpyDeviceToDevice, s));
-    HIPCHK(launch_topk(g->pr_sc.as<double>(), K0, k, 0, w, g->pr_tv.as<double>(), g->pr_ti.as<int64_t>(), s));
-    const double* tau = g->pr_tv.as<double>() + (k - 1);
-    if (g_prune_force_mode.load(std::memory_order_relaxed) == 1) {
-        static const double ninf = -HUGE_VAL;
-        HIPCHK(hipMemcpyAsync(count_d + 1, &ninf, sizeof(double), hipMemcpyHostToDevice, s));
-        tau = reinterpret_cast<const double*>(count_d + 1);
-    }
-    // 3. survivors: every candidate whose guarded bound reaches τ (the k that set τ among them), in index order
-    HIPCHK(launch_prune_compact(ub, M, tau, kind == ABO_ACQ_LOGEI ? PRUNE_ABS_LOGEI : PRUNE_ABS, g->pr_blk.as<int>(), g->pr_sel.as<int64_t>(),
-                                count_d, s));
-    HIPCHK(hipEventRecord(g->evs()[PE + 2], s));
-    // (step 4's lookup, ahead of the count's way to the host: the kernel reads the count itself and does nothing for more than K0
-    // survivors, and its "not found" flag comes back with the count — no synchronisation of its own)
-    const bool try_reuse = pp.reuse && 2 * K0 <= PRUNE_REUSE_SLOTS;
-    if (try_reuse) {
-        HIPCHK(hipMemsetAsync(count_d + 2, 0, sizeof(int64_t), s));
-        HIPCHK(launch_prune_reuse_scores(g->pr_sel.as<int64_t>(), count_d, g->pr_ti0.as<int64_t>(), g->pr_sc.as<double>(), K0,
-                                         g->pr_sc.as<double>() + K0, count_d + 2, s));
-    }
-    int64_t back[3] = {0, 0, 0};          // survivor count, (the hook's threshold), not found
-    HIPCHK(hipMemcpyAsync(back, count_d, sizeof(int64_t) * (try_reuse ? 3 : 1), hipMemcpyDeviceToHost, s));
-    HIPCHK(wait_stream(s));
-    int64_t S = back[0];
-    const bool not_found = back[2] != 0;
-    // 3b. second level: the bound pass at rblocks on the first level's survivors, against the SAME τ (the k-th best exact score of any
-    // subset is a valid threshold).  ub keeps min(level 1, level 2) — still an upper bound for every one of the M candidates — and is
-    // compacted again over all M (8 bytes a candidate: cheaper than a second index map), so the list stays in index order.
-    if (two_levels) {
-        g->plv.rows1 = g->pst.bound_rows;
-        g->plv.s1 = S;
-    }
-    if (two_levels && S > pp.level2_min) {
-        HIPCHK(hipEventRecord(g->evs()[14], s));
-        HIPCHK(g->pr_z.ensure(sizeof(double) * S * d));
-        HIPCHK(g->pr_ub2.ensure(sizeof(double) * S));
-        HIPCHK(launch_gather_points(Zd, g->pr_sel.as<int64_t>(), 0, (int)S, d, g->pr_z.as<double>(), s));
-        PostOpts bound2;
-        bound2.rblocks = pp.rblocks; bound2.more = true; bound2.level2 = true;
-        rc = posterior(g, g->pr_z.as<double>(), S, kind, p0, best_y, nullptr, nullptr, g->pr_ub2.as<double>(), bound2);
-        if (rc && rc != PRUNE_UNAVAILABLE) return rc;
-        if (!rc) {          // (no scratch for the engine at this size: the first level's list goes on as it is)
-            g->plv.rows2 = g->passes.back().rows;
-            HIPCHK(launch_prune_min_scatter(ub, g->pr_sel.as<int64_t>(), g->pr_ub2.as<double>(), S, s));
-            HIPCHK(launch_prune_compact(ub, M, tau, kind == ABO_ACQ_LOGEI ? PRUNE_ABS_LOGEI : PRUNE_ABS, g->pr_blk.as<int>(),
-                                        g->pr_sel.as<int64_t>(), count_d, s));
-            HIPCHK(hipEventRecord(g->evs()[15], s));
-            HIPCHK(hipMemcpyAsync(&S, count_d, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-            HIPCHK(wait_stream(s));
-            g->plv.s2 = S;
-        }
-    }
-    g->pst.survivors = S;
-    if (S < k || S > pp.max_survivors) { g->pst.fallback = 1; return ABO_OK; }
-    // 4. exact scores of the survivors, in list order.  With no second level and S ≤ K0 the threshold pass has scored nearly always all
-    // of them: a survivor kept because its bound reaches τ ranks, by bound, ahead of every candidate that does not, so were it outside
-    // the K0 best by bound, all K0 of them would survive too, S ≥ K0 + 1; NaN bounds are kept and rank first.  The exception is a stored
-    // bound of −Inf (LogEI where the bound's variance is ≤ 1e-12 and Δ ≤ 0): its guard is −Inf + Inf = NaN, so it is kept, yet it ranks
-    // LAST by bound and need not be among the K0.  So the argument is not relied on: the lookup above reports every survivor it did not
-    // find, and such a call runs the survivor pass as before.  An exact score does not depend on the batch a candidate is evaluated in
-    // (DESIGN §3b-1), so a score that was found is the bits a pass over the survivors would give.  (After a second level the list is
-    // a subset of the first level's, whose lookup is void: the survivor pass runs.)
-    const bool reuse = try_reuse && g->plv.rows2 == 0 && S <= K0 && !not_found;
-    if (reuse) {
-        double* sc0 = g->pr_sc.as<double>();           // K0 scores in the order of pr_ti0; the survivors' behind them
-        PHASE_EVENT(g->evs()[6], s);
-        HIPCHK(launch_topk(sc0 + K0, S, k, 0, w, tv, ti, s));
-        g->pr_reused = true;
-        // The call's work figures (var_gemm_flop, oz_gemm_ops) stay those of the selection as an algorithm — bound pass, K0 threshold
-        // candidates, S survivors — as tests/test_gpu_kgen_head32.py holds them: a pass of no chunks stands for the survivors.  No time
-        // is booked against it, so a rate taken from these figures (the benchmark's residue-GEMM rate among them) credits a reusing
-        // call with S/(K0 + S) of exact evaluations it did not launch (DESIGN §3b-1 says so where it gives the figures).
-        g->passes.push_back({g->passes.back().chunk0 + g->passes.back().nchunk, 0, S, g->N, g->oz_plan.n, false});
-    } else {
-        HIPCHK(g->pr_z.ensure(sizeof(double) * S * d));
-        HIPCHK(g->pr_sc.ensure(sizeof(double) * S));
-        HIPCHK(launch_gather_points(Zd, g->pr_sel.as<int64_t>(), 0, (int)S, d, g->pr_z.as<double>(), s));
-        rc = posterior(g, g->pr_z.as<double>(), S, kind, p0, best_y, nullptr, nullptr, g->pr_sc.as<double>(), further);
-        if (rc) return rc;
-        PHASE_EVENT(g->evs()[6], s);
-        // the selection among the exactly evaluated: list positions are in index order, so ties fall as they do over all M
-        HIPCHK(launch_topk(g->pr_sc.as<double>(), S, k, 0, w, tv, ti, s));
-    }
-    HIPCHK(launch_prune_map(ti, k, g->pr_sel.as<int64_t>(), idx_base, s));
-    HIPCHK(hipEventRecord(g->evs()[PE + 3], s));
-    g->pst.pruned = 1;
-    *done = true;
-    return ABO_OK;
-}
-
-// scores + selection for host or device candidates; separate memory spaces for the M scores and for the k selected pairs
-int32_t acq_terms_impl(abo_gp* g, const double* Z, int64_t M, int32_t d, int32_t z_space, const AcqTerms& t, int64_t idx_base,
-                       double* scores, int32_t out_space, int32_t k, double* top_val, int64_t* top_idx, int32_t top_space) {
-    if (M < 0 || (M > 0 && !Z)) return fail(ABO_EINVAL, "abo_acq: bad candidate buffer");
-    if (k < 0) return fail(ABO_EINVAL, "abo_acq: k = %d is negative", k);
-    if (k > 0 && (!top_val || !top_idx)) return fail(ABO_EINVAL, "abo_acq: k > 0 needs top_val and top_idx");
-    HIPCHK(hipSetDevice(g->prm.device));
-    hipStream_t s = g->stream;
-    double* sc_d = nullptr;
-    PinStage pin(g->ctx);
-    const bool with_var = !(terms_plain(t) && t.kind[0] == ABO_ACQ_MEAN);
-    const bool fused_timings = !terms_have_gradnorm(t);           // the slab path does not keep per-chunk events
-    g->pst = abo_prune_stats{};
-    g->plv = abo_gp::PruneLevels{};
-    g->pr_reused = false;
-    PrunePlan pp{false, 0, 0, 0, 0, 0};
-    if (M > 0 && terms_plain(t)) {
-        int nm = 0;
-        KgenArgs probe{};
-        probe.pt = g->p_out; probe.dp = g->dp;
-        const bool int8_fused = wants_int8(g, true, 1, &nm) && kgen_writes_residues(probe, nm);
-        pp = prune_plan(g->N, M, k, scores != nullptr, t.kind[0], t.p0[0], g->p_out, int8_fused, g->d);
-        if (pp.eligible && pp.rblocks0 >= pp.rblocks)          // (abo_test_prune_levels alone can ask for this)
-            return fail(ABO_EINVAL, "abo_acq: a first bound level of %d row blocks is not below the bound pass's %d", pp.rblocks0, pp.rblocks);
-    }
-    TopkWork w{};
-    double* tv = top_val;
-    int64_t* ti = top_idx;
-    if (k > 0) {
-        const int64_t we = topk_workspace_entries(M, pp.eligible && pp.k0 > k ? (int)pp.k0 : k);
-        HIPCHK(g->tk_keys0.ensure(sizeof(uint64_t) * we));
-        HIPCHK(g->tk_keys1.ensure(sizeof(uint64_t) * we));
-        HIPCHK(g->tk_idx0.ensure(sizeof(int64_t) * we));
-        HIPCHK(g->tk_idx1.ensure(sizeof(int64_t) * we));
-        w = TopkWork{{g->tk_keys0.as<uint64_t>(), g->tk_keys1.as<uint64_t>()}, {g->tk_idx0.as<int64_t>(), g->tk_idx1.as<int64_t>()}};
-        if (top_space == ABO_HOST) {
-            HIPCHK(g->top_val.ensure(sizeof(double) * k));
-            HIPCHK(g->top_idx.ensure(sizeof(int64_t) * k));
-            tv = g->top_val.as<double>();
-            ti = g->top_idx.as<int64_t>();
-        }
-    }
-    bool selected = false;
-    if (M > 0) {
-        const double* Zd = nullptr;
-        int32_t rc = stage_candidates(g, Z, M, z_space, &Zd);
-        if (rc) return rc;
-        HIPCHK(hipEventRecord(g->evs()[5], s));
-        if (pp.eligible) {
-            rc = prune_select(g, Zd, M, t, pp, idx_base, k, w, tv, ti, &selected);
-            if (rc) return rc;
-        }
-        if (!selected) {
-            if (scores && out_space == ABO_DEVICE) sc_d = scores;
-            else { HIPCHK(g->score_all.ensure(sizeof(double) * M)); sc_d = g->score_all.as<double>(); }
-            rc = score_terms_device(g, Zd, M, t, sc_d, /*more=*/g->pst.bound_rows > 0);
-            if (rc) return rc;
-            PHASE_EVENT(g->evs()[6], s);
-        }
-    } else {
-        HIPCHK(hipEventRecord(g->evs()[5], s));
-        PHASE_EVENT(g->evs()[6], s);
-    }
-    if (k > 0) {
-        if (!selected) HIPCHK(launch_topk(sc_d, M, k, idx_base, w, tv, ti, s));
-        if (top_space == ABO_HOST) {
-            HIPCHK(pin.d2h(top_val, tv, sizeof(double) * k, s));             // through the pinned block, copied on after the sync
-            HIPCHK(pin.d2h(top_idx, ti, sizeof(int64_t) * k, s));
-        }
-    }
-    HIPCHK(hipEventRecord(g->evs()[7], s));
-    if (scores && out_space == ABO_HOST && M > 0) {
-        int32_t rc = copy_out(scores, sc_d, sizeof(double) * M, ABO_HOST, s);
-        if (rc) return rc;
-    }
-    HIPCHK(wait_stream(s));
-    pin.flush();
-    if (M > 0 && fused_timings) collect_posterior_timings(g, with_var);
-    g->tm.acq_topk_ms = phase_events() ? ev_ms(g->evs()[6], g->evs()[7]) : 0.0;
-    g->tm.acq_total_ms = ev_ms(g->evs()[5], g->evs()[7]);
-    if (g->pst.bound_rows > 0) {
-        hipEvent_t* pe = &g->evs()[10];          // 10 … 15: start, end of the (first) bound pass, end of the threshold pass and compaction,
-        const bool l2 = g->plv.rows2 > 0;        // end of the survivor pass, start and end of the second bound level
-        if (g->plv.rows1 > 0) g->plv.ms1 = ev_ms(pe[0], pe[1]);
-        if (l2) g->plv.ms2 = ev_ms(pe[4], pe[5]);
-        g->pst.bound_ms = ev_ms(pe[0], pe[1]) + g->plv.ms2;
-        g->pst.threshold_ms = ev_ms(pe[1], pe[2]);
-        g->pst.survivor_ms = g->pst.pruned ? ev_ms(pe[l2 ? 5 : 2], pe[3]) : 0.0;
-    }
-    return ABO_OK;
-}
-
-}  // namespace
-
-// abo_acq with separate memory spaces for the M scores and for the k selected pairs (the multi-device driver keeps the
-// pairs on the device for the RCCL exchange while the scores, when asked for, go to the caller's host array)
-int32_t abo::acq_ex(abo_gp* g, const double* Z, int64_t M, int32_t d, int32_t z_space, int32_t kind, double p0,
-                    double best_y, int64_t idx_base, double* scores, int32_t out_space, int32_t k, double* top_val,
-                    int64_t* top_idx, int32_t top_space) {
-    int32_t rc = check_fitted(g, d);
-    if (rc) return rc;
-    if (kind == ABO_ACQ_MES) return fail(ABO_EINVAL, "abo_acq: ABO_ACQ_MES takes a vector of samples: use abo_acq_mes");
-    if (!plain_kind(kind)) return fail(ABO_EINVAL, "abo_acq: unknown acquisition kind %d", kind);
-    return acq_terms_impl(g, Z, M, d, z_space, one_term(kind, p0, best_y), idx_base, scores, out_space, k, top_val, top_idx, top_space);
-}
-
-int32_t abo::acq_terms_ex(abo_gp* g, const double* Z, int64_t M, int32_t d, int32_t z_space, const abo_acq_term* terms, int32_t nterms,
-                          int64_t idx_base, double* scores, int32_t out_space, int32_t k, double* top_val, int64_t* top_idx,
-                          int32_t top_space) {
-    int32_t rc = check_fitted(g, d);
-    if (rc) return rc;
-    AcqTerms t{};
-    rc = make_terms(g, terms, nterms, &t, "abo_acq_terms");
-    if (rc) return rc;
-    return acq_terms_impl(g, Z, M, d, z_space, t, idx_base, scores, out_space, k, top_val, top_idx, top_space);
-}
-
-extern "C" int32_t abo_acq_terms(abo_gp* g, const double* Z, int64_t M, int32_t d, int32_t z_space, const abo_acq_term* terms,
-                                 int32_t nterms, int64_t idx_base, double* scores, int32_t k, double* top_val, int64_t* top_idx,
-                                 int32_t out_space) {
-    return abo::acq_terms_ex(g, Z, M, d, z_space, terms, nterms, idx_base, scores, out_space, k, top_val, top_idx, out_space);
-}
 
 namespace {
 // after the synchronisation that followed a deferred fit: the verdict on the factorisation
@@ -2282,7 +1300,7 @@ static int32_t nlml_grad_impl(abo_gp* g, bool ard, double* nlml, double* d_log_e
     a.C = g->T.as<double>(); a.ldc = Np; a.M = (int)Np; a.N = (int)Np; a.K = (int)Np;
     a.kmode = K_A_UPPER; a.lower_only = 1; a.batch = 1; a.alpha = 1.0; a.beta = 0.0;
     HIPCHK(g->events(EV_BASE + 3));
-    hipEvent_t* ev = &g->evs()[EV_BASE];
+    hipEvent_t* ev = &g->evs()[EV_BASE];          // scratch slots: ev[0] begin, ev[1] K⁻¹ formed, ev[2] traces done (no posterior pass in this call)
     HIPCHK(hipEventRecord(ev[0], s));
     HIPCHK(launch_gemm_nt(a, s));
     HIPCHK(hipEventRecord(ev[1], s));
@@ -2296,11 +1314,9 @@ static int32_t nlml_grad_impl(abo_gp* g, bool ard, double* nlml, double* d_log_e
         // gradient-enhanced GP: dK/dlog(ell) of the multi-output system as a matrix (same generator as K_XX with the
         // derivative triple), then the weighted sum against K^-1 - alpha alpha^T
         HIPCHK(g->Kxz.ensure(sizeof(double) * Np * Np));
-        KgenArgs ka{};
-        ka.Xs = g->st->Xs.as<double>(); ka.Z = g->st->Xraw.as<double>(); ka.alpha = nullptr; ka.Kout = g->Kxz.as<double>();
-        ka.mu = nullptr; ka.ldk = Np; ka.M = g->npts; ka.j0 = 0; ka.Mc = (int)Np; ka.N = (int)g->npts; ka.Np = (int)Np;
-        ka.d = g->d; ka.dp = g->dp; ka.family = g->prm.family; ka.s = 1.0 / g->prm.ell; ka.sigma_f2 = g->prm.sigma_f2;
-        ka.mean_c = 0.0; ka.pt = g->p_out; ka.pc = g->p_out; ka.point_major = 1; ka.dlogell = 1;
+        KgenArgs ka = kgen_model_args(g, false);
+        ka.Z = g->st->Xraw.as<double>(); ka.Kout = g->Kxz.as<double>(); ka.ldk = Np; ka.M = g->npts; ka.Mc = (int)Np;
+        ka.pc = g->p_out; ka.point_major = 1; ka.dlogell = 1;
         HIPCHK(launch_kgen(ka, s));
         HIPCHK(launch_nlml_grad_matrix(ga, g->Kxz.as<double>(), Np, s));
     } else {
@@ -2488,11 +1504,9 @@ int32_t abo_predict_cov(abo_gp* g, const double* Za, int64_t Ma, const double* Z
             HIPCHK(hipMemcpyAsync(stage, Zin[q], sizeof(double) * (size_t)Ms[q] * d, hipMemcpyHostToDevice, s));
             Zd = stage;
         }
-        KgenArgs ka{};
-        ka.Xs = g->st->Xs.as<double>(); ka.Z = Zd; ka.alpha = g->alpha.as<double>(); ka.Kout = cov ? g->Kxz.as<double>() : nullptr;
-        ka.mu = muset[q]; ka.ldk = Np; ka.M = Ms[q]; ka.j0 = 0; ka.Mc = (int)Mps[q]; ka.N = (int)g->npts;
-        ka.Np = (int)Np; ka.d = g->d; ka.dp = dp; ka.family = g->prm.family; ka.s = 1.0 / g->prm.ell;
-        ka.sigma_f2 = g->prm.sigma_f2; ka.mean_c = g->prm.mean_c; ka.mean_vec[0] = g->mean_vec[0];
+        KgenArgs ka = kgen_model_args(g, true);             // (one output: pt = 1, and mean_vec is its [0] alone)
+        ka.Z = Zd; ka.alpha = g->alpha.as<double>(); ka.Kout = cov ? g->Kxz.as<double>() : nullptr;
+        ka.mu = muset[q]; ka.ldk = Np; ka.M = Ms[q]; ka.Mc = (int)Mps[q];
         HIPCHK(launch_kgen(ka, s));
         if (!cov) continue;
         HIPCHK(launch_scale_points(Zd, Zsset[q], (int)Ms[q], (int)Mps[q], g->d, dp, 1.0 / g->prm.ell, s));
@@ -2672,16 +1686,16 @@ int32_t abo_cand_refresh(abo_gp* g, abo_cand* c) {
         } else {
             c->Kzx.release();
         }
-        HIPCHK(hipEventRecord(g->evs()[5], g->stream));
+        HIPCHK(hipEventRecord(g->evs()[EV_ACQ_BEGIN], g->stream));
         PostOpts keep;
         keep.kstore = c->kzx_ld ? c->Kzx.as<double>() : nullptr; keep.ldstore = c->kzx_ld;
         rc = posterior(g, c->Z.as<double>(), c->M, -1, 0.0, 0.0, c->mu.as<double>(), c->var.as<double>(), nullptr, keep);
         if (rc) return rc;
-        HIPCHK(hipEventRecord(g->evs()[6], g->stream));
+        HIPCHK(hipEventRecord(g->evs()[EV_ACQ_SCORED], g->stream));
         HIPCHK(wait_stream(g->stream));
         collect_posterior_timings(g, true);
         g->tm.acq_topk_ms = 0.0;
-        g->tm.acq_total_ms = ev_ms(g->evs()[5], g->evs()[6]);
+        g->tm.acq_total_ms = ev_ms(g->evs()[EV_ACQ_BEGIN], g->evs()[EV_ACQ_SCORED]);
     }
     c->synced_gen = g->st->gen;
     c->synced_N = g->N;
@@ -2732,7 +1746,7 @@ int32_t abo_cand_downdate(abo_gp* g, abo_cand* c) {
         // c(z) = k(z,x*) − k_zᵀ K⁻¹ k_* = Σ_{k ≤ N} k(z, x_k)·vext[k]: one kernel-evaluation pass, nothing stored
         HIPCHK(c->cdot.ensure(sizeof(double) * pad_up(c->M, 16)));
         const bool resident = c->kzx_ld > 0 && c->kzx_ld == g->st->cap;
-        HIPCHK(g->events(8));
+        HIPCHK(g->events(EV_ACQ_END + 1));
         // The set's block-form q-EI state (blocks + chain) follows the model through real appends.  Entry i = number of rows appended
         // since the state's base.  If the appended point is the next FANTASY of the last batch (the picks appended for real, in
         // order), its column c_i(z) is in the chain already (it does not depend on the observed value): no pass over K_ZX.  Otherwise
@@ -2758,13 +1772,13 @@ int32_t abo_cand_downdate(abo_gp* g, abo_cand* c) {
             else Q = abo_cand::Qei();                                                                                  // no room: start over
         }
         g->tm.downdate_from_chain = chain_i >= 0 ? 1 : 0;
-        HIPCHK(hipEventRecord(g->evs()[5], s));
+        HIPCHK(hipEventRecord(g->evs()[EV_ACQ_BEGIN], s));
         double pass_ms = 0.0;
         if (chain_i >= 0) {
             // the appended row's column keeps the resident K_ZX current for later passes
             HIPCHK(launch_cand_newcol(g->st->Xs.as<double>(), c->Z.as<double>(), c->Kzx.as<double>(), c->kzx_ld, c->M, (int)(g->N - 1),
                                       g->d, g->dp, g->prm.family, 1.0 / g->prm.ell, g->prm.sigma_f2, s));
-            HIPCHK(hipEventRecord(g->evs()[6], s));
+            HIPCHK(hipEventRecord(g->evs()[EV_ACQ_SCORED], s));
             HIPCHK(launch_downdate(c->mu.as<double>(), c->var.as<double>(), c->qchain.as<double>() + (size_t)chain_i * Q.Mp, c->M,
                                    g->ap_beta, g->ap_s2, s));
             Q.chain_s[chain_i] = g->ap_s2;                         // what the stored variance was down-dated with
@@ -2789,16 +1803,14 @@ int32_t abo_cand_downdate(abo_gp* g, abo_cand* c) {
             const int64_t step = 65536;
             for (int64_t j0 = 0; !resident && j0 < c->M; j0 += step) {
                 const int64_t m = (c->M - j0) < step ? (c->M - j0) : step;
-                KgenArgs ka{};
-                ka.Xs = g->st->Xs.as<double>(); ka.Z = c->Z.as<double>(); ka.alpha = vext; ka.Kout = nullptr;
-                ka.mu = c->cdot.as<double>() + j0; ka.ldk = 0; ka.M = c->M; ka.j0 = j0; ka.Mc = (int)pad_up(m, 16);
-                ka.N = (int)g->npts; ka.Np = (int)pad_up(Rq + 1, TB); ka.d = g->d; ka.dp = g->dp; ka.family = g->prm.family;
-                ka.s = 1.0 / g->prm.ell; ka.sigma_f2 = g->prm.sigma_f2; ka.mean_c = 0.0;
-                if (P > 1) { ka.pt = P; ka.pc = 1; ka.point_major = 0; ka.rvalid = (int)(Rq + 1); }
-                else { ka.N = (int)(Rq + 1); }
+                KgenArgs ka = kgen_model_args(g, false);
+                ka.Z = c->Z.as<double>(); ka.alpha = vext; ka.mu = c->cdot.as<double>() + j0; ka.M = c->M; ka.j0 = j0; ka.Mc = (int)pad_up(m, 16);
+                ka.Np = (int)pad_up(Rq + 1, TB);                   // the rows up to the appended one: a partly appended point …
+                if (P > 1) ka.rvalid = (int)(Rq + 1);
+                else ka.N = (int)(Rq + 1);                         // … or, with one output per point, simply fewer points
                 HIPCHK(launch_kgen(ka, s));
             }
-            if (q == P - 1) HIPCHK(hipEventRecord(g->evs()[6], s));
+            if (q == P - 1) HIPCHK(hipEventRecord(g->evs()[EV_ACQ_SCORED], s));
             HIPCHK(launch_downdate(c->mu.as<double>(), c->var.as<double>(), c->cdot.as<double>(), c->M, beta, s2, s));
             if (chain_put >= 0) {                                  // the pass's column joins the chain as real entry chain_put
                 HIPCHK(hipMemcpyAsync(c->qchain.as<double>() + (size_t)chain_put * Q.Mp, c->cdot.p, sizeof(double) * c->M, hipMemcpyDeviceToDevice, s));
@@ -2810,7 +1822,7 @@ int32_t abo_cand_downdate(abo_gp* g, abo_cand* c) {
             }
         }
         HIPCHK(wait_stream(s));
-        pass_ms = ev_ms(g->evs()[5], g->evs()[6]);
+        pass_ms = ev_ms(g->evs()[EV_ACQ_BEGIN], g->evs()[EV_ACQ_SCORED]);
         g->tm.downdate_ms = pass_ms;
         g->tm.downdate_bytes = (resident && chain_i < 0) ? 8.0 * (double)g->N * (double)c->M * P : 0.0;
         c->dd_serial = P == 1 ? g->ap_serial : 0;
@@ -3047,7 +2059,7 @@ int32_t abo::qei_block(abo_gp* g, abo_cand* c, const double* pts, const int64_t*
     const QeiWork w = qei_carve(c->qwork.p, T16, d, dp, Np);
     double* C = c->qblk.as<double>() + (size_t)blk * T16 * Mp;
     HIPCHK(g->events(EV_BASE + 4));
-    hipEvent_t* ev = &g->evs()[EV_BASE];
+    hipEvent_t* ev = &g->evs()[EV_BASE];          // scratch slots: ev[0] / ev[3] the block build, ev[1] / ev[2] its pass over the set (no posterior pass in this call)
     HIPCHK(hipEventRecord(ev[0], s));
     HIPCHK(hipMemsetAsync(w.P, 0, sizeof(double) * (size_t)T16 * d, s));
     HIPCHK(hipMemcpyAsync(w.P, pts, sizeof(double) * (size_t)T * d, hipMemcpyHostToDevice, s));
@@ -3444,7 +2456,7 @@ hipError_t grad_eval_cb(void* ctx, const double* pts, int npts, double* mu, doub
 
 namespace abo {    // shared with test_hooks.hip (abo_state.h)
 // bounds (2·d doubles: lower, upper), starts (S·d) and the outputs all in DEVICE memory; asynchronous on the handle's stream
-// between events 5 and 6
+// between EV_ACQ_BEGIN and EV_ACQ_SCORED (abo_refine*) or the EV_REFINE_* pair (abo_optimize_acquisition*): the caller records them
 int32_t refine_device(abo_gp* g, const AcqTerms& terms, const double* bounds_d, const double* starts_d, int S,
                       RefineOpts o, double* x_out_d, double* f_out_d, int* iters_d, int grad_only) {
     hipStream_t s = g->stream;
@@ -3542,11 +2554,11 @@ static int32_t refine_terms_impl(abo_gp* g, const AcqTerms& terms, const double*
     HIPCHK(hipMemcpyAsync(bd, lower, sizeof(double) * d, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(bd + d, upper, sizeof(double) * d, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(sd, starts, sizeof(double) * ns, hipMemcpyHostToDevice, s));
-    HIPCHK(g->events(8));
-    HIPCHK(hipEventRecord(g->evs()[5], s));
+    HIPCHK(g->events(EV_ACQ_END + 1));
+    HIPCHK(hipEventRecord(g->evs()[EV_ACQ_BEGIN], s));
     int32_t rc = refine_device(g, terms, bd, sd, S, refine_defaults(opts), xd, fd, id, 0);
     if (rc) return rc;
-    HIPCHK(hipEventRecord(g->evs()[6], s));
+    HIPCHK(hipEventRecord(g->evs()[EV_ACQ_SCORED], s));
     std::vector<int> it(2 * (size_t)S);
     PinStage pin(g->ctx);
     HIPCHK(pin.d2h(x_out, xd, sizeof(double) * ns, s));
@@ -3554,7 +2566,7 @@ static int32_t refine_terms_impl(abo_gp* g, const AcqTerms& terms, const double*
     HIPCHK(pin.d2h(it.data(), id, sizeof(int) * 2 * S, s));
     HIPCHK(wait_stream(s));
     pin.flush();
-    g->tm.refine_ms = ev_ms(g->evs()[5], g->evs()[6]);
+    g->tm.refine_ms = ev_ms(g->evs()[EV_ACQ_BEGIN], g->evs()[EV_ACQ_SCORED]);
     g->tm.refine_starts = S;
     g->tm.refine_evals = 0;
     for (int e = 0; e < S; ++e) g->tm.refine_evals += it[2 * e + 1];
@@ -3626,11 +2638,11 @@ static int32_t optimize_terms_impl(abo_gp* g, const AcqTerms& t, const double* l
     if (rc) return rc;
     const double grid_ms = g->tm.acq_total_ms;
     // refinement stage (:55-71): one launch
-    HIPCHK(g->events(10));
-    HIPCHK(hipEventRecord(g->evs()[8], s));
+    HIPCHK(g->events(EV_REFINE_END + 1));
+    HIPCHK(hipEventRecord(g->evs()[EV_REFINE_BEGIN], s));
     rc = refine_device(g, t, bd, sd, k, refine_defaults(opts), xd, fd, id, 0);
     if (rc) return rc;
-    HIPCHK(hipEventRecord(g->evs()[9], s));
+    HIPCHK(hipEventRecord(g->evs()[EV_REFINE_END], s));
     std::vector<double> hs(ns), hv(k), hx(ns), hf(k);
     std::vector<int> it(2 * (size_t)k);
     PinStage pin(g->ctx);
@@ -3642,7 +2654,7 @@ static int32_t optimize_terms_impl(abo_gp* g, const AcqTerms& t, const double* l
     HIPCHK(wait_stream(s));
     pin.flush();
     g->tm.acq_total_ms = grid_ms;
-    g->tm.refine_ms = ev_ms(g->evs()[8], g->evs()[9]);
+    g->tm.refine_ms = ev_ms(g->evs()[EV_REFINE_BEGIN], g->evs()[EV_REFINE_END]);
     g->tm.refine_starts = k;
     g->tm.refine_evals = 0;
     for (int e = 0; e < k; ++e) g->tm.refine_evals += it[2 * e + 1];
@@ -3801,20 +2813,6 @@ int32_t abo_score_mes(int32_t device, const double* mu, const double* var, int64
     return ABO_OK;
 }
 
-int32_t abo_acq_mes(abo_gp* g, const double* Z, int64_t M, int32_t d, int32_t z_space, const double* ystar, int32_t S, int32_t ys_space,
-                    int64_t idx_base, double* scores, int32_t k, double* top_val, int64_t* top_idx, int32_t out_space) {
-    int32_t rc = mes_check_samples(ystar, S, ys_space, "abo_acq_mes");
-    if (rc) return rc;
-    rc = check_fitted(g, d);
-    if (rc) return rc;
-    rc = mes_check_handle(g, "abo_acq_mes");
-    if (rc) return rc;
-    AcqTerms t;
-    rc = mes_terms(g, ystar, S, ys_space, &t);
-    if (rc) return rc;
-    return acq_terms_impl(g, Z, M, d, z_space, t, idx_base, scores, out_space, k, top_val, top_idx, out_space);
-}
-
 int32_t abo_cand_acq_mes(abo_gp* g, abo_cand* c, const double* ystar, int32_t S, int32_t ys_space, int64_t idx_base, double* scores,
                          int32_t k, double* top_val, int64_t* top_idx, int32_t out_space) {
     int32_t rc = mes_check_samples(ystar, S, ys_space, "abo_cand_acq_mes");
@@ -3926,11 +2924,10 @@ int32_t abo::cand_downdate_column(abo_gp* g, abo_cand* c, double* tmp, const dou
         const int64_t step = 65536;
         for (int64_t j0 = 0; j0 < c->M; j0 += step) {
             const int64_t m = (c->M - j0) < step ? (c->M - j0) : step;
-            KgenArgs ka{};
-            ka.Xs = g->st->Xs.as<double>(); ka.Z = c->Z.as<double>(); ka.alpha = vext; ka.Kout = nullptr;
-            ka.mu = tmp + j0; ka.ldk = 0; ka.M = c->M; ka.j0 = j0; ka.Mc = (int)pad_up(m, 16);
-            ka.N = (int)(Rq + 1); ka.Np = (int)pad_up(Rq + 1, TB); ka.d = g->d; ka.dp = g->dp; ka.family = g->prm.family;
-            ka.s = 1.0 / g->prm.ell; ka.sigma_f2 = g->prm.sigma_f2; ka.mean_c = 0.0;
+            KgenArgs ka = kgen_model_args(g, false);
+            ka.pt = 1;                                             // (the column of a ONE-row append)
+            ka.Z = c->Z.as<double>(); ka.alpha = vext; ka.mu = tmp + j0; ka.M = c->M; ka.j0 = j0; ka.Mc = (int)pad_up(m, 16);
+            ka.N = (int)(Rq + 1); ka.Np = (int)pad_up(Rq + 1, TB);
             HIPCHK(launch_kgen(ka, s));
         }
     }

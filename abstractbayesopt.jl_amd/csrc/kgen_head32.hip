@@ -1,4 +1,4 @@
-// The HEAD of the FIRST bound level of the pruned top-k selection in one fused kernel (api.hip: prune_select).
+// The HEAD of the FIRST bound level of the pruned top-k selection in one fused kernel (acq.hip: prune_select).
 //
 // A first-level bound pass over R = 256·rblocks0 rows needs, per candidate j, the head of the mean (columns k < R) and
 // σ²_R = k_zz − Σ_{i<R} v_ij², V = W·K_XZ with the triangular W = L⁻¹: only the R × R head of W and the kernel values of the first R

@@ -1,4 +1,4 @@
-// The μ-only tail of the bound pass of the pruned top-k selection (api.hip: prune_select).
+// The μ-only tail of the bound pass of the pruned top-k selection (acq.hip: prune_select).
 //
 // The bound pass needs the residue planes of K_XZ for the first R = res_kmax training columns only, but the posterior mean needs every
 // column.  For the columns k ≥ R the kernel values have one consumer: μ, which in that pass is used for one thing, an upper bound of

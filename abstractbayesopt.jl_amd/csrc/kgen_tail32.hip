@@ -1,4 +1,4 @@
-// The μ-only tail of the FIRST bound level of the pruned top-k selection in fp32 (api.hip: prune_select).
+// The μ-only tail of the FIRST bound level of the pruned top-k selection in fp32 (acq.hip: prune_select).
 //
 // kgen_tail.hip's job — μ̃_tail = σ_f²·Σ_{k ≥ R} α_k·κ̃(r̃²_jk) for every candidate, with a PROVEN ε_j ≥ |μ̃_j − μ_j| — and its mapping
 // (16 candidates per workgroup in LDS, two training points per lane in registers, sweep over k from k0, fixed-order reduction, a lane

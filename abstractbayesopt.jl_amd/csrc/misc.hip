@@ -899,7 +899,7 @@ hipError_t launch_prune_map(int64_t* top_idx, int k, const int64_t* sel, int64_t
     return hipGetLastError();
 }
 
-// The survivors' exact scores out of the threshold pass's (api.hip: prune_select).  idx0[q], q < K0, are the K0 best candidates by
+// The survivors' exact scores out of the threshold pass's (acq.hip: prune_select).  idx0[q], q < K0, are the K0 best candidates by
 // bound — distinct, in no particular order — and sc0[q] their exact scores; sel[p], p < S = *count, the survivors in index order; more
 // than K0 survivors: nothing is done.  A survivor whose bound reaches τ is among the K0 whenever S ≤ K0 — by bound it ranks ahead of
 // every candidate that is not kept, so outside the K0 best it would make all K0 of them survivors, S ≥ K0 + 1 — and so is one with a

@@ -950,7 +950,7 @@ static unsigned oz_gemm_shape(int Ti, int Tj, int n, OzGemmArgs& g) {
 }
 
 // what the kernel's packing (ti < 512, tj < 2048 in ti | tj << 9 | l << 20), oz_divmod (tickets and divisors below 2^23) and the int32
-// accumulators (k·2^14 ≤ 2^30) can take — the engine's own limits (api.hip: wants_int8 up to 65536 padded rows, pick_chunk up to
+// accumulators (k·2^14 ≤ 2^30) can take — the engine's own limits (posterior.hip: wants_int8 up to 65536 padded rows, pick_chunk up to
 // 65536 candidates) lie inside: Ti ≤ 256, Tj ≤ 256, at most 1024 tickets a list (tests/test_oz_ref_cpu.py walks that launch)
 static bool oz_gemm_shape_ok(int Ti, int Tj, int n, int Np256) {
     if (Ti < 1 || Tj < 1 || Ti > 256 || Tj > 2047 || n < 1 || n > OZ_MAXMOD || Np256 > 65536) return false;

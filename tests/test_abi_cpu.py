@@ -81,12 +81,17 @@ def test_argument_validation_needs_no_gpu():
 
 
 def test_every_host_unit_reports_through_the_one_error_slot():
-    """The host driver is two translation units (api.hip, and test_hooks.hip in the test library) with ONE last-error slot per thread,
-    defined in api.hip: null-argument calls across its surfaces and into a hook — the argument check is the first thing each of these
-    does, no device is touched — return ABO_EINVAL, and abo_last_error then holds THAT call's message, the function's name in it.  A
-    unit with a private copy of the slot would leave the previous call's text (or none) there."""
+    """The host driver is four translation units (api.hip, posterior.hip, acq.hip, and test_hooks.hip in the test library) with ONE
+    last-error slot per thread, defined in api.hip: null-argument calls across its surfaces and into a hook — the argument check is the
+    first thing each of these does, no device is touched — return ABO_EINVAL, and abo_last_error then holds THAT call's message, the
+    function's name in it.  A unit with a private copy of the slot would leave the previous call's text (or none) there.
+    acq.hip is entered through abo_acq_mes, whose first check names it (abo_acq and abo_acq_terms begin with the handle check, which
+    does not).  posterior.hip has no such entry point: abo_predict, abo_predict_grad and abo_predict_grad_cov all begin with that
+    handle check, so abo_predict is held to its message as it is — "null handle", replacing its predecessor's."""
     lib = abo._lib.lib()
     calls = [
+        ("abo_acq_mes", lambda: lib.abo_acq_mes(None, None, 0, 1, 0, None, 1, 0, 0, None, 0, None, None, 0)),          # acq.hip
+        ("null handle", lambda: lib.abo_predict(None, None, 0, 1, 0, None, None, 0)),                                   # posterior.hip
         ("abo_create", lambda: lib.abo_create(None, None)),
         ("abo_fit", lambda: lib.abo_fit(None, None, 1, 1, None, 0, None)),
         ("abo_nlml", lambda: lib.abo_nlml(None, None)),

@@ -1,4 +1,4 @@
-"""Host-side decisions of the pruned top-k selection (csrc/api.hip: prune_plan; DESIGN.md "Pruned top-k selection"): when the path is
+"""Host-side decisions of the pruned top-k selection (csrc/acq.hip: prune_plan; DESIGN.md "Pruned top-k selection"): when the path is
 taken, how many row blocks of L⁻¹ the bound pass contracts, how many candidates set the threshold and when the survivor pass gives
 way to the ordinary full pass.  No GPU needed: abo_test_prune_plan of the test build is plain host code."""
 import ctypes as C

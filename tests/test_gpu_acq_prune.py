@@ -1,4 +1,4 @@
-"""Exact top-k without the full variance contraction (csrc/api.hip: prune_select; DESIGN.md "Pruned top-k selection").
+"""Exact top-k without the full variance contraction (csrc/acq.hip: prune_select; DESIGN.md "Pruned top-k selection").
 
 A call that asks for the top k only (EI, or UCB with β ≥ 0, int8-residue engine) bounds every score from above with the variance
 reduction of the first rows of L⁻¹ alone, takes a threshold from the exact scores of the best-by-bound candidates and runs the full

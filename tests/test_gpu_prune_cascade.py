@@ -1,4 +1,4 @@
-"""Two bound levels of the pruned top-k selection (csrc/api.hip: prune_plan, prune_select): a first bound pass over
+"""Two bound levels of the pruned top-k selection (csrc/acq.hip: prune_plan, prune_select): a first bound pass over
 N/32 rows of L⁻¹ on all candidates sets the threshold τ, the N/8 pass runs on its survivors only (when more than 4·K₀ are left, or
 when abo_test_prune_levels says so), the stored bounds become min(level 1, level 2) and the list is compacted again against the same τ.
 

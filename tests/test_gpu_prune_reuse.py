@@ -1,5 +1,5 @@
-"""Survivors that the threshold pass of the pruned top-k selection has scored are not evaluated again (csrc/api.hip: prune_select,
-step 4; csrc/misc.hip: prune_reuse_kernel).  int8 engine, k = 100 (K₀ = 1024); every selection is asked to equal, bit
+"""Survivors that the threshold pass of the pruned top-k selection has scored are not evaluated again (csrc/acq.hip: prune_select,
+prune_survivors; csrc/misc.hip: prune_reuse_kernel).  int8 engine, k = 100 (K₀ = 1024); every selection is asked to equal, bit
 for bit, the same call with the path off (abo_test_prune_force(0, 2)) and with the switch off (ABO_PRUNE_REUSE=0 through its hook).
 
   * N = 3072, M = 20 000, EI and UCB(2): both calls reuse (their survivors are fewer than K₀), same survivor count either way;

@@ -111,7 +111,7 @@ def test_ticket_decode_takes_every_tile_exactly_once(n):
 
 
 def test_ticket_decode_at_the_largest_launch_the_engine_offers():
-    """The engine's limits, read from api.hip: wants_int8 offers the engine up to Np = 65536 padded rows (Ti ≤ 256); pick_chunk caps a
+    """The engine's limits, read from posterior.hip: wants_int8 offers the engine up to Np = 65536 padded rows (Ti ≤ 256); pick_chunk caps a
     chunk at 65536 candidates AND at a residue plane below 2^31 bytes, Mc256 ≤ (2^31 / Np256) / 256 · 256 − 256, i.e. Ti·Tj < 2^15.  The
     largest tile lists: the most row blocks (256 × 127) and the most column blocks (31 × 256, Np256 = 7936 being the widest plane that
     leaves 65536 candidates under the cap, and 32 × 255 next to it).

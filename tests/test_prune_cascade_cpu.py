@@ -1,4 +1,4 @@
-"""Host-side plan of the two bound levels of the pruned top-k selection (csrc/api.hip: prune_plan): a first level of
+"""Host-side plan of the two bound levels of the pruned top-k selection (csrc/acq.hip: prune_plan): a first level of
 N/32 rows over all candidates, the N/8 pass on its survivors.  No GPU needed: abo_test_prune_plan_levels of the test build is plain host
 code.  The four values abo_test_prune_plan has always returned are what tests/test_acq_prune_cpu.py pins; they are compared here with
 what the new call returns next to the first level's row blocks."""
