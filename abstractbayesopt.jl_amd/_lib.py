@@ -28,7 +28,7 @@ EXPORTS = ["abo_create", "abo_set_contraction", "abo_create_grad", "abo_predict_
            "abo_score_mes", "abo_acq_mes", "abo_cand_acq_mes", "abo_refine_mes", "abo_optimize_acquisition_mes",
            "abo_loo", "abo_loo_grad", "abo_predict_cov", "abo_remove"]
 TEST_EXPORTS = ["abo_test_gemm_nt", "abo_test_kappa", "abo_test_oz_plan", "abo_test_oz_contract", "abo_test_acq_grad",
-                "abo_test_acq_grad_terms", "abo_test_prune_plan", "abo_test_prune_force", "abo_test_prune_levels", "abo_test_prune_plan_levels", "abo_test_prune_bounds", "abo_test_prune_mean",
+                "abo_test_acq_grad_terms", "abo_test_prune_plan", "abo_test_prune_force", "abo_test_prune_levels", "abo_test_prune_plan_levels", "abo_test_prune_bounds", "abo_test_prune_mean", "abo_test_prune_head",
                 "abo_test_kappa_tail", "abo_test_prune_tail32", "abo_test_prune_reuse", "abo_test_prune_reused", "abo_test_prune_head32", "abo_test_bound_head32", "abo_test_kappa_tail32", "abo_test_prune_bound_moduli", "abo_test_prune_bound_plan", "abo_test_oz_contract_bound", "abo_test_acq_partials", "abo_test_mes_partials", "abo_test_acq_grad_mes",
                 "abo_test_gemm_args", "abo_test_gemm_path", "abo_test_gemm_swz_q", "abo_test_gemm_swz_map", "abo_test_qei_pass", "abo_test_splitk_reduce",
                 "abo_test_var_gemm", "abo_test_kgen", "abo_test_cand_newcol",
@@ -240,6 +240,7 @@ def lib():
         L.abo_test_prune_plan_levels.argtypes = [i64, i64, i32, i32, i32, f64, i32, i32, i32, vp]
         L.abo_test_prune_bounds.argtypes = [vp, vp, i64]
         L.abo_test_prune_mean.argtypes = [vp, vp, vp, i64]
+        L.abo_test_prune_head.argtypes = [vp, vp, vp, i64]
         L.abo_test_prune_bound_moduli.argtypes = [i32]
         L.abo_test_prune_bound_plan.argtypes = [vp, vp, vp, i64]
         L.abo_test_kappa_tail.argtypes = [i32, i32, vp, vp, i64]

@@ -288,6 +288,7 @@ struct KgenTailArgs {
     int Mc;               // padded chunk rows (multiple of 16)
     int N, Np, k0, d, dp, family;
     double s, sigma_f2, mean_c;
+    const float* Xf = nullptr;   // launch_kgen_tail32 alone: the rows k ≥ k0 of Xs in fp32, pair-interleaved (launch_tail32_stage with the same k0); null: rounded in the kernel
 };
 hipError_t launch_kgen_tail(const KgenTailArgs& a, hipStream_t s);
 // test hook: out[i] = kappa_tail(family, d2[i]) (abo_kappa.h)

@@ -173,6 +173,11 @@ hipError_t launch_kgen_res_short10(const KgenArgs& a, hipStream_t s);
 // kgen_tail32.hip: launch_kgen_tail (abo_kernels.h) with the pair arithmetic in packed fp32 and the guard that goes with it — the
 // same arguments, outputs and conditions; the tail of the M-wide first bound level
 hipError_t launch_kgen_tail32(const KgenTailArgs& a, hipStream_t s);
+// its training points rounded to fp32 ONCE per bound pass, in the order its lanes read them: for the pair (k, k + 1), k − k0 even, k < N,
+// Xf[(k − k0)·dp + 2c + h] = fl32(Xs[k + h][c]) — the partner of a last odd point is row 0 (its weight is 0 in the kernel).
+// tail32_stage_floats(N, dp, k0) floats are written.
+inline size_t tail32_stage_floats(int N, int dp, int k0) { return (size_t)((N - k0 + 1) / 2) * 2 * dp; }
+hipError_t launch_tail32_stage(const double* Xs, int N, int dp, int k0, float* Xf, hipStream_t s);
 // test hook: out[i] = kappa_tail32(family, fl32(d2[i])) (abo_kappa.h)
 hipError_t launch_kappa_tail32_test(int family, const double* d2, double* out, int64_t n, hipStream_t s);
 

@@ -5,9 +5,12 @@
 // past the last training point sits the step out), with the pair arithmetic in packed fp32.  The first level runs over all M
 // candidates and its mean has one consumer, an upper bound of the score whose survivors are all evaluated again by the full
 // pipeline: a looser mean costs survivors and nothing else, and the second level is there if they become many.
-//   * operands: the same scaled fp64 inputs x = Xs_k, z = Z_j·s, rounded once to fp32 — x per lane and sweep step, z once per
-//     workgroup into LDS.  The lane's two training points are the halves of a packed register pair, the candidate's coordinate is
-//     broadcast to both halves;
+//   * operands: the same scaled fp64 inputs x = Xs_k, z = Z_j·s, each rounded once to fp32.  z: once per workgroup, into LDS.  x: once
+//     per bound pass, by tail32_stage_kernel below, into the pair-interleaved image Xf that a lane fills its registers from with
+//     16-byte loads.  (The rows of Xs are the same for every workgroup, chunk and candidate; on the benchmark's problem 65 536
+//     workgroups a pass each read them as fp64 and rounded them again.  ABO_TAIL32_STAGE=0, STAGED = false, keeps that: the same
+//     values either way, so μ̃_tail and ε are bit-identical.)  The lane's two training points are the halves of a packed register
+//     pair, the candidate's coordinate is broadcast to both halves;
 //   * distance in the DIFFERENCE form, one v_pk_add_f32 and one v_pk_fma_f32 per coordinate and two pairs (the expanded form's
 //     cancellation would cost 4(dp + 2)·2⁻²⁴·w ≈ 6·10⁻⁵ per pair at w = 16);
 //   * kappa_tail32 (abo_kappa.h): v_sqrt_f32, v_exp_f32, the polynomial in packed fp32;
@@ -43,7 +46,26 @@
 
 namespace abo {
 
-template <int FAM, int DP>
+typedef float f4_t __attribute__((ext_vector_type(4)));
+
+// Xf of kgen_core.h: one thread per pair of training points and coordinate
+__global__ void __launch_bounds__(256) tail32_stage_kernel(const double* __restrict__ Xs, int N, int dp, int k0, float* __restrict__ Xf) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int pr = i / dp, c = i - pr * dp;
+    const int k = k0 + 2 * pr;
+    if (k >= N) return;
+    const int k1 = k + 1 < N ? k + 1 : 0;
+    *reinterpret_cast<f2_t*>(Xf + ((int64_t)pr * dp + c) * 2) = f2_t{(float)Xs[(int64_t)k * dp + c], (float)Xs[(int64_t)k1 * dp + c]};
+}
+
+hipError_t launch_tail32_stage(const double* Xs, int N, int dp, int k0, float* Xf, hipStream_t s) {
+    if (k0 < 0 || k0 % 128 || k0 >= N || dp <= 0) return hipErrorInvalidValue;
+    const int64_t n = (int64_t)((N - k0 + 1) / 2) * dp;
+    hipLaunchKernelGGL(tail32_stage_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, Xs, N, dp, k0, Xf);
+    return hipGetLastError();
+}
+
+template <int FAM, int DP, bool STAGED>
 __global__ void __launch_bounds__(256) kgen_tail32_kernel(KgenTailArgs p) {
     __shared__ __attribute__((aligned(16))) float zs[JT][DP];          // fl32(z)
     __shared__ double zz[JT];                                          // |z|² (fp64: the guard's w)
@@ -72,18 +94,32 @@ __global__ void __launch_bounds__(256) kgen_tail32_kernel(KgenTailArgs p) {
             // a column past the last training point reads row 0 with weight 0 (kgen_tail.hip: no padding row of Xs or alpha is read)
             const bool in1 = k + 1 < p.N;
             f2_t x[DP];
-            const double* xp0 = p.Xs + (int64_t)k * DP;
-            const double* xp1 = p.Xs + (int64_t)(in1 ? k + 1 : 0) * DP;
-            if constexpr (DP >= 2) {
+            if constexpr (STAGED) {
+                const float* xf = p.Xf + (int64_t)(k - p.k0) * DP;          // (k − k0 even: 2·DP floats from a multiple of 2·DP)
+                if constexpr (DP >= 2) {
 #pragma unroll
-                for (int c = 0; c < DP; c += 2) {
-                    const d2_t v0 = *reinterpret_cast<const d2_t*>(xp0 + c);
-                    const d2_t v1 = *reinterpret_cast<const d2_t*>(xp1 + c);
-                    x[c] = f2_t{(float)v0[0], (float)v1[0]};
-                    x[c + 1] = f2_t{(float)v0[1], (float)v1[1]};
+                    for (int c = 0; c < DP; c += 2) {
+                        const f4_t v = *reinterpret_cast<const f4_t*>(xf + 2 * c);
+                        x[c] = f2_t{v[0], v[1]};
+                        x[c + 1] = f2_t{v[2], v[3]};
+                    }
+                } else {
+                    x[0] = *reinterpret_cast<const f2_t*>(xf);
                 }
             } else {
-                x[0] = f2_t{(float)xp0[0], (float)xp1[0]};
+                const double* xp0 = p.Xs + (int64_t)k * DP;
+                const double* xp1 = p.Xs + (int64_t)(in1 ? k + 1 : 0) * DP;
+                if constexpr (DP >= 2) {
+#pragma unroll
+                    for (int c = 0; c < DP; c += 2) {
+                        const d2_t v0 = *reinterpret_cast<const d2_t*>(xp0 + c);
+                        const d2_t v1 = *reinterpret_cast<const d2_t*>(xp1 + c);
+                        x[c] = f2_t{(float)v0[0], (float)v1[0]};
+                        x[c + 1] = f2_t{(float)v0[1], (float)v1[1]};
+                    }
+                } else {
+                    x[0] = f2_t{(float)xp0[0], (float)xp1[0]};
+                }
             }
             const double a0 = p.alpha[k] * p.sigma_f2, a1 = in1 ? p.alpha[k + 1] * p.sigma_f2 : 0.0;
 #pragma unroll
@@ -124,16 +160,16 @@ __global__ void __launch_bounds__(256) kgen_tail32_kernel(KgenTailArgs p) {
     }
 }
 
-template <int FAM>
+template <int FAM, bool STAGED>
 static hipError_t launch_tail32_dp(const KgenTailArgs& a, hipStream_t s) {
     dim3 grid(a.Mc / JT), block(256);
     switch (a.dp) {
-        case 1: hipLaunchKernelGGL((kgen_tail32_kernel<FAM, 1>), grid, block, 0, s, a); break;
-        case 2: hipLaunchKernelGGL((kgen_tail32_kernel<FAM, 2>), grid, block, 0, s, a); break;
-        case 4: hipLaunchKernelGGL((kgen_tail32_kernel<FAM, 4>), grid, block, 0, s, a); break;
-        case 8: hipLaunchKernelGGL((kgen_tail32_kernel<FAM, 8>), grid, block, 0, s, a); break;
-        case 16: hipLaunchKernelGGL((kgen_tail32_kernel<FAM, 16>), grid, block, 0, s, a); break;
-        case 32: hipLaunchKernelGGL((kgen_tail32_kernel<FAM, 32>), grid, block, 0, s, a); break;
+        case 1: hipLaunchKernelGGL((kgen_tail32_kernel<FAM, 1, STAGED>), grid, block, 0, s, a); break;
+        case 2: hipLaunchKernelGGL((kgen_tail32_kernel<FAM, 2, STAGED>), grid, block, 0, s, a); break;
+        case 4: hipLaunchKernelGGL((kgen_tail32_kernel<FAM, 4, STAGED>), grid, block, 0, s, a); break;
+        case 8: hipLaunchKernelGGL((kgen_tail32_kernel<FAM, 8, STAGED>), grid, block, 0, s, a); break;
+        case 16: hipLaunchKernelGGL((kgen_tail32_kernel<FAM, 16, STAGED>), grid, block, 0, s, a); break;
+        case 32: hipLaunchKernelGGL((kgen_tail32_kernel<FAM, 32, STAGED>), grid, block, 0, s, a); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -144,10 +180,10 @@ hipError_t launch_kgen_tail32(const KgenTailArgs& a, hipStream_t s) {
     // the conditions of launch_kgen_tail
     if (a.Mc % JT || a.k0 < 0 || a.k0 % 128 || a.k0 >= a.N || a.N > a.Np) return hipErrorInvalidValue;
     switch (a.family) {
-        case ABO_KERNEL_SE: return launch_tail32_dp<ABO_KERNEL_SE>(a, s);
-        case ABO_KERNEL_MATERN52: return launch_tail32_dp<ABO_KERNEL_MATERN52>(a, s);
-        case ABO_KERNEL_MATERN72: return launch_tail32_dp<ABO_KERNEL_MATERN72>(a, s);
-        case ABO_KERNEL_MATERN32: return launch_tail32_dp<ABO_KERNEL_MATERN32>(a, s);
+        case ABO_KERNEL_SE: return a.Xf ? launch_tail32_dp<ABO_KERNEL_SE, true>(a, s) : launch_tail32_dp<ABO_KERNEL_SE, false>(a, s);
+        case ABO_KERNEL_MATERN52: return a.Xf ? launch_tail32_dp<ABO_KERNEL_MATERN52, true>(a, s) : launch_tail32_dp<ABO_KERNEL_MATERN52, false>(a, s);
+        case ABO_KERNEL_MATERN72: return a.Xf ? launch_tail32_dp<ABO_KERNEL_MATERN72, true>(a, s) : launch_tail32_dp<ABO_KERNEL_MATERN72, false>(a, s);
+        case ABO_KERNEL_MATERN32: return a.Xf ? launch_tail32_dp<ABO_KERNEL_MATERN32, true>(a, s) : launch_tail32_dp<ABO_KERNEL_MATERN32, false>(a, s);
         default: return hipErrorInvalidValue;
     }
 }

@@ -135,6 +135,11 @@ int prune_bound_moduli() {
     return env;
 }
 
+// A/B switch, read once: on, unless the variable begins with '0'.  The fp32 tail of a first bound level with the fused head reads its
+// training points from the fp32 image one launch per pass writes (kgen_tail32.hip) instead of rounding the fp64 rows again in every
+// workgroup.
+bool tail32_stage() { static const bool on = [] { const char* e = getenv("ABO_TAIL32_STAGE"); return !(e && e[0] == '0'); }(); return on; }
+
 }  // namespace
 
 namespace abo {    // declared in abo_state.h
@@ -251,6 +256,13 @@ int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0
         PHASE_EVENT(g->evs()[ev_chunk(chunk0, EVC_CONTRACT_END)], s);
         g->tm.var_gemm_launches += 1;
     }
+    // the tail's training points in fp32, once per pass (nothing cached across calls: the rule of the head's preparation launch); a
+    // first level without the fused head keeps the in-kernel conversion, as every other pass keeps what it had
+    const bool staged = head32 && tail32_stage();
+    if (staged) {
+        HIPCHK(g->pr_xf.ensure(sizeof(float) * tail32_stage_floats((int)g->npts, g->dp, 256 * o.rblocks)));
+        HIPCHK(launch_tail32_stage(g->st->Xs.as<double>(), (int)g->npts, g->dp, 256 * o.rblocks, g->pr_xf.as<float>(), s));
+    }
     for (int64_t c = 0; c < nchunk; ++c) {
         const int64_t j0 = c * Mc;
         const int64_t m = (M - j0) < Mc ? (M - j0) : Mc;
@@ -284,6 +296,7 @@ int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0
             kt.mu_tail = mut.as<double>(); kt.eps = eps.as<double>();
             kt.M = Mpts; kt.j0 = j0; kt.Mc = mcp; kt.N = (int)g->npts; kt.Np = (int)Np; kt.k0 = ka.res_kmax; kt.d = g->d; kt.dp = g->dp; kt.family = ka.family;
             kt.s = ka.s; kt.sigma_f2 = ka.sigma_f2; kt.mean_c = ka.mean_c;
+            if (staged) kt.Xf = g->pr_xf.as<float>();
             HIPCHK(o.tail32 ? launch_kgen_tail32(kt, s) : launch_kgen_tail(kt, s));
         }
         PHASE_EVENT(ev(EVC_KGEN_END), s);

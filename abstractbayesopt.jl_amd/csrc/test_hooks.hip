@@ -221,6 +221,17 @@ int32_t abo_test_prune_mean(abo_gp* g, double* mu, double* eps, int64_t M) {
     return ABO_OK;
 }
 
+int32_t abo_test_prune_head(abo_gp* g, double* head, double* ssq, int64_t M) {
+    if (!g || !head || !ssq || M < 0) return fail(ABO_EINVAL, "abo_test_prune_head: bad argument");
+    if (!g->pst.bound_rows || g->ph_rows <= 0 || g->pr_head.cap < sizeof(double) * (size_t)M || g->pr_ssq.cap < sizeof(double) * (size_t)M)
+        return fail(ABO_EINVAL, "abo_test_prune_head: the last abo_acq on this handle ran no fused head over %lld candidates", (long long)M);
+    HIPCHK(hipSetDevice(g->prm.device));
+    HIPCHK(hipMemcpyAsync(head, g->pr_head.p, sizeof(double) * M, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(ssq, g->pr_ssq.p, sizeof(double) * M, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(wait_stream(g->stream));
+    return ABO_OK;
+}
+
 int32_t abo_test_kappa_tail(int32_t device, int32_t family, const double* d2, double* out, int64_t n) {
     if (!d2 || !out || n < 0) return fail(ABO_EINVAL, "abo_test_kappa_tail: bad argument");
     if (family < ABO_KERNEL_SE || family > ABO_KERNEL_MATERN32) return fail(ABO_EINVAL, "abo_test_kappa_tail: unknown family");

@@ -893,6 +893,9 @@ int32_t abo_test_prune_bounds(abo_gp* gp, double* out, int64_t M);
  * full generator, the others by the shortened sequences of csrc/kgen_tail.hip) and the distance ε it proved to the full pass's mean:
  * the bounds above are scores at μ̃ − ε */
 int32_t abo_test_prune_mean(abo_gp* gp, double* mu, double* eps, int64_t M);
+/* head[0..M), ssq[0..M) (host) = what the fused head of the first bound level (csrc/kgen_head32.hip) wrote for every candidate in the
+ * last abo_acq on this handle: the head of the mean and the guarded sum of squares; an error when that call ran no fused head */
+int32_t abo_test_prune_head(abo_gp* gp, double* head, double* ssq, int64_t M);
 /* out[i] = kappa_tail(family, d2[i]): the shortened kernel evaluation of that pass (csrc/abo_kappa.h), without sigma_f2 */
 int32_t abo_test_kappa_tail(int32_t device, int32_t family, const double* d2, double* out, int64_t n);
 /* out[i] = kappa_tail32(family, d2[i] rounded to fp32): the fp32 evaluation of the first level's tail (csrc/abo_kappa.h), without
