@@ -3,7 +3,7 @@ AbstractSurrogate / AbstractAcquisition interface (hot path only: update → pos
 top-k).  Import as ``import abstractbayesopt.jl_amd as abo``."""
 from . import _lib, acquisition, distributed, incremental, multigpu, synth, thompson
 from ._lib import AboError, DimensionMismatch, PosDefException
-from .acquisition import (AbstractAcquisition, EnsembleAcquisition, ExpectedImprovement, LogExpectedImprovement,
+from .acquisition import (AbstractAcquisition, EnsembleAcquisition, ExpectedImprovement, KnowledgeGradient, LogExpectedImprovement,
                           MaxValueEntropySearch, ProbabilityImprovement, UpperConfidenceBound, device_latin_hypercube, evaluate, latin_hypercube,
                           optimize_acquisition, optimize_acquisition_device, acquisition_value_and_grad, refine_starts,
                           update_and_evaluate)
@@ -21,7 +21,7 @@ from . import surrogate as _s
 from .thompson import SamplePaths, max_value_samples, sample_paths, spectral_frequencies, thompson_batch, thompson_step
 from .surrogate import (AbstractSurrogate, ArdUnsupported, HipStandardGP, _get_minimum, _update_model_parameters,
                         ard_lengthscales, from_model_space, to_model_space,
-                        get_factor, get_kernel_constructor, get_lengthscale, get_mean_std, get_scale, leave_one_out, mean_and_var,
+                        get_factor, get_kernel_constructor, get_lengthscale, get_mean_std, get_scale, knowledge_gradient, leave_one_out, mean_and_var,
                         mean_and_cov, nlml, nlml_fitted, nlml_ls, posterior_cov, posterior_mean, posterior_var, prep_input, prep_output,
                         rescale_model, sample_joint, set_default_contraction, std_y, training_data, unstandardized_mean_and_var)
 

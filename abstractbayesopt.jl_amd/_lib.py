@@ -26,7 +26,7 @@ EXPORTS = ["abo_create", "abo_set_contraction", "abo_create_grad", "abo_predict_
            "abo_paths_create", "abo_paths_destroy", "abo_paths_eval", "abo_paths_eval_cand", "abo_paths_stats_get",
            "abo_paths_append", "abo_paths_attach", "abo_paths_detach", "abo_paths_top", "abo_paths_values", "abo_paths_append_stats_get",
            "abo_score_mes", "abo_acq_mes", "abo_cand_acq_mes", "abo_refine_mes", "abo_optimize_acquisition_mes",
-           "abo_loo", "abo_loo_grad", "abo_predict_cov", "abo_remove"]
+           "abo_loo", "abo_loo_grad", "abo_predict_cov", "abo_remove", "abo_acq_kg"]
 TEST_EXPORTS = ["abo_test_gemm_nt", "abo_test_kappa", "abo_test_oz_plan", "abo_test_oz_contract", "abo_test_acq_grad",
                 "abo_test_acq_grad_terms", "abo_test_prune_plan", "abo_test_prune_force", "abo_test_prune_levels", "abo_test_prune_plan_levels", "abo_test_prune_bounds", "abo_test_prune_mean", "abo_test_prune_head",
                 "abo_test_kappa_tail", "abo_test_prune_tail32", "abo_test_prune_reuse", "abo_test_prune_reused", "abo_test_prune_head32", "abo_test_bound_head32", "abo_test_kappa_tail32", "abo_test_prune_bound_moduli", "abo_test_prune_bound_plan", "abo_test_oz_contract_bound", "abo_test_acq_partials", "abo_test_mes_partials", "abo_test_acq_grad_mes",
@@ -37,7 +37,8 @@ TEST_EXPORTS = ["abo_test_gemm_nt", "abo_test_kappa", "abo_test_oz_plan", "abo_t
                 "abo_test_topk_plan", "abo_test_topk", "abo_test_prune_compact", "abo_test_prune_min_scatter", "abo_test_prune_map",
                 "abo_test_finalize", "abo_test_cand_gemv", "abo_test_downdate", "abo_test_grad_cov", "abo_test_gather_points",
                 "abo_test_pick_record", "abo_test_score",
-                "abo_test_oz_rowscale", "abo_test_oz_quant", "abo_test_oz_gemm", "abo_test_oz_crt", "abo_test_oz_modpack", "abo_test_oz_tickets"]
+                "abo_test_oz_rowscale", "abo_test_oz_quant", "abo_test_oz_gemm", "abo_test_oz_crt", "abo_test_oz_modpack", "abo_test_oz_tickets",
+                "abo_test_kg_lines"]
 # what launch_topk runs, as abo_test_topk_plan reports it (include/abo_hip.h: ABO_TOPK_PATH_*)
 TOPK_PATH_NONE, TOPK_PATH_SMALL, TOPK_PATH_SLICES, TOPK_PATH_ARGMAX, TOPK_PATH_BLOCKSORT = -1, 0, 1, 2, 3
 # margins of the pruned selection's guard (csrc/abo_kernels.h)
@@ -53,6 +54,8 @@ UPDATE_PATHS = {UPDATE_SHARED: "shared", UPDATE_APPENDED: "appended", UPDATE_REF
 # what abo_remove ran
 REMOVE_REMOVED, REMOVE_REFIT = 0, 1
 REMOVE_PATHS = {REMOVE_REMOVED: "removed", REMOVE_REFIT: "refit"}
+# abo_acq_kg: add the candidate's own line to its row (include/abo_hip.h)
+KG_SELF = 1
 
 
 class AboParams(C.Structure):
@@ -224,6 +227,7 @@ def lib():
     L.abo_loo.argtypes = [vp, vp, vp, vp, C.POINTER(f64), i32]
     L.abo_loo_grad.argtypes = [vp, C.POINTER(f64), C.POINTER(f64), C.POINTER(f64), C.POINTER(f64)]
     L.abo_predict_cov.argtypes = [vp, vp, i64, vp, i64, i32, i32, vp, vp, vp, i32]
+    L.abo_acq_kg.argtypes = [vp, vp, i64, vp, i64, i32, i32, f64, i32, i64, vp, i32, vp, vp, i32]
     L.abo_lhs.argtypes =[i32, i64, i32, vp, vp, C.c_uint64, i64, i64, vp]
     L.abo_score.argtypes = [i32, vp, vp, i64, i32, f64, f64, vp]
     L.abo_fill_distance.argtypes = [i32, vp, i64, i32, i32, vp, i64, i32, C.POINTER(f64)]
@@ -297,6 +301,7 @@ def lib():
         L.abo_test_oz_crt.argtypes = [i32, vp, i32, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i64, i64, vp, vp, i64, vp, i64, i32, vp]
         L.abo_test_oz_modpack.argtypes = [i32, vp, i64, i32, vp]
         L.abo_test_oz_tickets.argtypes = [i32, i32, i32, vp, C.POINTER(i64)]
+        L.abo_test_kg_lines.argtypes = [i32, vp, vp, i64, i32, i32, vp, vp, vp, vp]
     L.abo_mgpu_create.argtypes = [C.POINTER(AboParams), i32, C.POINTER(i32), C.POINTER(vp)]
     L.abo_mgpu_create_grad.argtypes = [C.POINTER(AboParams), i32, vp, i32, C.POINTER(i32), C.POINTER(vp)]
     L.abo_mgpu_append_grad.argtypes = [vp, vp, i32, vp, C.POINTER(i64), vp]

@@ -143,6 +143,9 @@ class EnsembleAcquisition(AbstractAcquisition):
         assert np.all(weights >= 0), "weights must be non-negative"
         total = float(weights.sum())
         assert total > 0, "sum of weights must be positive"
+        if any(isinstance(a, KnowledgeGradient) for a in acqs):
+            raise TypeError("KnowledgeGradient cannot be a member of an EnsembleAcquisition: it is no function of one point's (mu, var); "
+                            "evaluate it on its own")
         if any(isinstance(a, MaxValueEntropySearch) for a in acqs):
             raise TypeError("MaxValueEntropySearch cannot be a member of an EnsembleAcquisition: its samples do not fit a weighted-sum "
                             "term (include/abo_hip.h: abo_acq_term); evaluate it on its own")
@@ -178,6 +181,50 @@ class EnsembleAcquisition(AbstractAcquisition):
                 and self.acquisitions == other.acquisitions)
 
 
+@dataclass(frozen=True, eq=False)
+class KnowledgeGradient(AbstractAcquisition):
+    """KnowledgeGradient(decision=None, noise=None, include_self=True): the knowledge gradient over a discrete decision set (no
+    reference counterpart; Frazier, Powell and Dayanik 2009, Scott et al. 2011; include/abo_hip.h: abo_acq_kg) — the expected decrease
+    of the minimum of the posterior mean over `decision` from one observation at the candidate.  It needs no best_y, ξ or β.
+    decision None: the evaluated points themselves; an array of up to 8192 points; or "train": the model's training points, refreshed
+    by `update`.  It values a candidate by the JOINT posterior with the decision set, so it travels through abo_acq_kg, not as a
+    (kind, p0, best_y) triple: it cannot be a member of an EnsembleAcquisition or be refined by the library's gradient stage."""
+    decision: object = None
+    noise: object = None
+    include_self: bool = True
+    points: object = None              # with decision="train": the training points `update` read from the model
+
+    def _p0(self):
+        raise TypeError("KnowledgeGradient has no scalar parameters: it is served by abo_acq_kg")
+
+    def _decision(self, surrogate):
+        if isinstance(self.decision, str):
+            if self.decision != "train":
+                raise ValueError(f'KnowledgeGradient: decision must be None, an array of points or "train", got {self.decision!r}')
+            if self.points is not None:
+                return self.points
+            from .surrogate import training_data
+            return training_data(surrogate)[0]
+        return self.decision
+
+    def evaluate(self, surrogate, x, k: int = 0):
+        from .surrogate import knowledge_gradient
+        return knowledge_gradient(surrogate, x, decision=self._decision(surrogate), noise=self.noise, include_self=self.include_self, k=k)
+
+    def __call__(self, surrogate: AbstractSurrogate, x):
+        return self.evaluate(surrogate, x)
+
+    def __eq__(self, other):
+        def same(p, q):
+            if p is None or q is None or isinstance(p, str) or isinstance(q, str):
+                return type(p) is type(q) and p == q
+            return np.array_equal(np.asarray(p), np.asarray(q))
+        return (isinstance(other, KnowledgeGradient) and same(self.decision, other.decision) and self.noise == other.noise
+                and self.include_self == other.include_self)
+
+    __hash__ = None
+
+
 _TAKES_BEST_Y = (ExpectedImprovement, LogExpectedImprovement, ProbabilityImprovement)
 
 
@@ -189,6 +236,9 @@ def update(acq: AbstractAcquisition, ys, surrogate: AbstractSurrogate):
         return EnsembleAcquisition(acq.weights, [update(a, ys, surrogate) for a in acq.acquisitions])
     if isinstance(acq, _TAKES_BEST_Y):
         return replace(acq, best_y=_get_minimum(surrogate, ys))
+    if isinstance(acq, KnowledgeGradient) and isinstance(acq.decision, str) and acq.decision == "train":
+        from .surrogate import training_data
+        return replace(acq, points=training_data(surrogate)[0])         # decision="train": the model's points as they are now
     return acq
 
 
@@ -205,6 +255,11 @@ def evaluate(acq: AbstractAcquisition, surrogate: HipStandardGP, x, k: int = 0, 
     Host inputs give NumPy outputs; a CUDA tensor gives CUDA tensors (nothing crosses PCIe)."""
     if not isinstance(surrogate, HipStandardGP):
         raise TypeError("the fused acquisition path needs a HipStandardGP surrogate")
+    if isinstance(acq, KnowledgeGradient):
+        if idx_base != 0:
+            raise ValueError("evaluate: KnowledgeGradient takes no idx_base")
+        r = acq.evaluate(surrogate, x, k=k)
+        return (r[0] if return_scores else None, r[1], r[2]) if k > 0 else (r if return_scores else None, None, None)
     if isinstance(acq, EnsembleAcquisition) or getattr(acq, "kind", None) == ACQ_GRADNORM_UCB:
         terms = flatten_terms(acq, surrogate)
         if terms is None or hasattr(surrogate, "devices"):

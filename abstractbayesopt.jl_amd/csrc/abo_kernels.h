@@ -383,6 +383,28 @@ hipError_t launch_cov_prior(const double* As, const double* Bs, int Ma, int Mb, 
                             int64_t ldc, hipStream_t s);
 // out[i·Mb + j] = C[i][j] for i < Ma, j < Mb; sym = 1: + 1e-18 on the diagonal (abo_predict's latent-variance jitter)
 hipError_t launch_cov_pack(const double* C, int64_t ldc, int Ma, int Mb, int sym, double* out, hipStream_t s);
+
+// ---- knowledge gradient over a discrete decision set (kg.hip; abo_acq_kg) ----------------------
+// Row i's lines: intercept asign·a[j], slope B[i·ldb + j]/den[i] for j < Mb (den null: the slopes as they are), and — self_b given — the
+// row's own line (asign·self_a[i], self_b[i]).  val[i] = E[max_j (a_j + b_ij·Z)] − max_j a_j exactly (sort by (b, a), upper-envelope scan,
+// Σ Δb·h(−|c|) in envelope order); nenv[i] (may be null) = lines on the envelope.  den[i] == 0: val 0.0, nenv 1; a non-finite intercept or
+// slope in the row: val NaN, nenv 0.  One workgroup per row, the lines in LDS: kg_lds_bytes(Mb) of it, Mb ≤ KG_MAX_LINES.
+constexpr int KG_MAX_LINES = 8192;
+struct KgArgs {
+    const double* a; const double* B; int64_t ldb;
+    const double* den; const double* self_a; const double* self_b;
+    double asign;
+    int Ma, Mb;
+    int P;                 // set by the launcher: the power of two ≥ Mb
+    double* val; int* nenv;
+};
+inline int kg_pow2(int n) { int p = 1; while (p < n) p <<= 1; return p; }
+size_t kg_lds_bytes(int Mb);
+hipError_t launch_kg_rows(KgArgs a, hipStream_t s);
+// per candidate i < Ma: v_i = C[i][i] (C given: the symmetric form's diagonal) or sigma_f2 − Σ_{k<R} V[i][k]² (one wave per row, a fixed
+// order), + 1e-18; den[i] = sqrt(v_i + noise), 0 where v_i + noise ≤ 1e-12; self_b[i] = v_i/den[i] (0 with den)
+hipError_t launch_kg_prep(const double* V, int64_t ldv, int R, const double* C, int64_t ldc, int Ma, double sigma_f2, double noise,
+                          double* den, double* self_b, hipStream_t s);
 // test hook: out[i] = kappa(family, d2[i]) with the device math the generator uses
 hipError_t launch_kappa_test(int family, const double* d2, double* out, int64_t n, hipStream_t s);
 // K[i][i] += noise for i < N; K[i][i] = 1 for N ≤ i < Np (identity padding keeps the factor PD)

@@ -204,6 +204,7 @@ inline void storage_unref(Storage* st) {
 //                                overwritten by the threshold's own selection)
 //   pr_xf                        the fp32 tail's training points in fp32, pair-interleaved (kgen_tail32.hip) — written by every bound pass
 //                                that reads it
+//   kg_w                         abo_acq_kg: sqrt(v_i + noise) and the slope of the own line, per candidate
 #define ABO_GP_BUFS(X)                                                                                                              \
     X(alpha) X(vext) X(tvec) X(T) X(info) X(scal)                                                                                   \
     X(Zdev) X(Kxz) X(partial) X(mu_c) X(mu_all) X(var_all) X(score_all) X(tk_keys0) X(tk_keys1) X(tk_idx0) X(tk_idx1) X(top_val) X(top_idx) \
@@ -211,7 +212,7 @@ inline void storage_unref(Storage* st) {
     X(pr_ub) X(pr_z) X(pr_sc) X(pr_sel) X(pr_blk) X(pr_tv) X(pr_ti)                                                                 \
     X(pr_mut) X(pr_eps) X(pr_nrm) X(pr_ub2) X(pr_mut2) X(pr_eps2)                                                                   \
     X(ystar) X(oz_WRb) X(oz_sexpb) X(oz_badrb) X(oz_delta) X(loo_T) X(cov_Zs) X(cov_V) X(cov_C)                                     \
-    X(pr_head) X(pr_ssq) X(pr_wf) X(pr_hdl) X(pr_ti0) X(pr_xf)
+    X(pr_head) X(pr_ssq) X(pr_wf) X(pr_hdl) X(pr_ti0) X(pr_xf) X(kg_w)
 
 struct abo_gp {
     std::atomic<int> refs{1};

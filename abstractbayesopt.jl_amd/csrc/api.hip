@@ -1446,58 +1446,71 @@ int32_t abo_loo_grad(abo_gp* g, double* nlpl, double* d_log_ell, double* d_log_s
     return ABO_OK;
 }
 
-// Joint posterior covariance between two point sets (include/abo_hip.h).  Per set: K_ZX from the generator (the mean falls out of the
-// same pass: abo_predict's bits), V = K_ZX·L⁻ᵀ on the fp64 GEMM against the lower-triangular W (k ≤ i: half the product), its columns
-// ≥ N zeroed — rows ≥ N of shared factor storage may hold a discarded appended branch, and a 128-tile of W reaches past the view's N.
-// Then the prior block (cov.hip), the product subtracted in place (C = −V_a·V_bᵀ + C), and the compact copy-out.  Zb == NULL: the lower
-// 128-tiles only, mirrored.  Always the fp64 engine: the int8-residue contraction squares one operand, a signed cross product is outside
-// its error analysis.
-constexpr int64_t COV_MAX_POINTS = 8192;
-int32_t abo_predict_cov(abo_gp* g, const double* Za, int64_t Ma, const double* Zb, int64_t Mb, int32_t d, int32_t z_space, double* mu_a,
-                        double* mu_b, double* cov, int32_t out_space) {
-    if (!g) return fail(ABO_EINVAL, "abo_predict_cov: null handle");
+}  // extern "C"
+
+constexpr int64_t COV_MAX_POINTS = 8192;          // points per set of abo_predict_cov and abo_acq_kg
+
+namespace {
+
+// what abo_predict_cov and abo_acq_kg check alike, before any device work; *Mb becomes Ma in the symmetric form
+int32_t cov_check(abo_gp* g, const char* fn, const double* Za, int64_t Ma, const double* Zb, int64_t* Mb, int32_t d, int32_t z_space,
+                  int32_t out_space) {
+    if (!g) return fail(ABO_EINVAL, "%s: null handle", fn);
     if (!g->fitted) return fail(ABO_EINVAL, "surrogate is not conditioned on data yet (call abo_fit first)");
     if (g->p_out > 1)
-        return fail(ABO_EINVAL, "abo_predict_cov: a gradient-enhanced model has p outputs per point (abo_predict_grad_cov gives the block of one point)");
-    if (d != g->d) return fail(ABO_EDIM, "DimensionMismatch: abo_predict_cov with d = %d, model dimension %d", d, g->d);
+        return fail(ABO_EINVAL, "%s: a gradient-enhanced model has p outputs per point (abo_predict_grad_cov gives the block of one point)", fn);
+    if (d != g->d) return fail(ABO_EDIM, "DimensionMismatch: %s with d = %d, model dimension %d", fn, d, g->d);
     if ((z_space != ABO_HOST && z_space != ABO_DEVICE) || (out_space != ABO_HOST && out_space != ABO_DEVICE))
-        return fail(ABO_EINVAL, "abo_predict_cov: z_space %d / out_space %d is neither ABO_HOST nor ABO_DEVICE", z_space, out_space);
-    if (Ma < 1 || Ma > COV_MAX_POINTS) return fail(ABO_EINVAL, "abo_predict_cov: Ma = %lld outside 1..%lld", (long long)Ma, (long long)COV_MAX_POINTS);
-    if (!Za) return fail(ABO_EINVAL, "abo_predict_cov: Za is NULL");
-    const bool sym = Zb == nullptr;
-    if (sym) {
-        if (Mb != 0 && Mb != Ma) return fail(ABO_EINVAL, "abo_predict_cov: Zb is NULL (the symmetric form), Mb = %lld is neither 0 nor Ma = %lld", (long long)Mb, (long long)Ma);
-        if (mu_b) return fail(ABO_EINVAL, "abo_predict_cov: Zb is NULL (the symmetric form) but mu_b is given; the means are mu_a");
-        Mb = Ma;
-    } else if (Mb < 1 || Mb > COV_MAX_POINTS) {
-        return fail(ABO_EINVAL, "abo_predict_cov: Mb = %lld outside 1..%lld", (long long)Mb, (long long)COV_MAX_POINTS);
+        return fail(ABO_EINVAL, "%s: z_space %d / out_space %d is neither ABO_HOST nor ABO_DEVICE", fn, z_space, out_space);
+    if (Ma < 1 || Ma > COV_MAX_POINTS) return fail(ABO_EINVAL, "%s: Ma = %lld outside 1..%lld", fn, (long long)Ma, (long long)COV_MAX_POINTS);
+    if (!Za) return fail(ABO_EINVAL, "%s: Za is NULL", fn);
+    if (!Zb) {
+        if (*Mb != 0 && *Mb != Ma)
+            return fail(ABO_EINVAL, "%s: Zb is NULL (the symmetric form), Mb = %lld is neither 0 nor Ma = %lld", fn, (long long)*Mb, (long long)Ma);
+        *Mb = Ma;
+    } else if (*Mb < 1 || *Mb > COV_MAX_POINTS) {
+        return fail(ABO_EINVAL, "%s: Mb = %lld outside 1..%lld", fn, (long long)*Mb, (long long)COV_MAX_POINTS);
     }
-    if (!mu_a && !mu_b && !cov) return ABO_OK;
-    HIPCHK(hipSetDevice(g->prm.device));
+    return ABO_OK;
+}
+
+// The V and product stage both calls share.  Per set: K_ZX from the generator (the mean falls out of the same pass: abo_predict's bits),
+// V = K_ZX·L⁻ᵀ on the fp64 GEMM against the lower-triangular W (k ≤ i: half the product), its columns ≥ N zeroed — rows ≥ N of shared
+// factor storage may hold a discarded appended branch, and a 128-tile of W reaches past the view's N.  Then the prior block (cov.hip) and
+// the product subtracted in place (C = −V_a·V_bᵀ + C).  Zb == NULL: the lower 128-tiles only, mirrored.  Launches only, on the handle's
+// stream; every workspace of the stage is sized before its first launch (pack: doubles of Kxz the caller wants behind it).
+struct CovBlock {
+    bool sym;
+    int64_t Map, Mbp;
+    double* V[2];          // V_a, V_b (= V_a in the symmetric form): [Mp][Np]
+    double* mu[2];         // the means of the two sets (mu[1] = mu[0] in the symmetric form)
+    double* C;             // [Map][Mbp], zero padded
+};
+int32_t cov_block(abo_gp* g, const double* Za, int64_t Ma, const double* Zb, int64_t Mb, int32_t z_space, bool want_cov,
+                  const bool want_set[2], size_t pack, CovBlock* out) {
     hipStream_t s = g->stream;
     const int64_t Np = g->Np, ld = g->st->cap;
-    const int N = (int)g->N, dp = g->dp;
+    const int N = (int)g->N, dp = g->dp, d = g->d;
+    const bool sym = Zb == nullptr;
     const int64_t Map = pad_up(Ma, TB), Mbp = pad_up(Mb, TB);
     const int nsets = sym ? 1 : 2;
     const int64_t Ms[2] = {Ma, Mb}, Mps[2] = {Map, Mbp};
     const double* Zin[2] = {Za, Zb};
-    const bool host_out = out_space == ABO_HOST;
     // every workspace before the first launch: a buffer that grew between two launches would go back to the pool with work queued on it
     if (z_space == ABO_HOST) HIPCHK(g->Zdev.ensure(sizeof(double) * (size_t)(Ma + (sym ? 0 : Mb)) * d));
     HIPCHK(g->mu_all.ensure(sizeof(double) * (size_t)(Map + Mbp)));
-    if (cov) {
-        const size_t kx = (size_t)(Map > Mbp ? Map : Mbp) * Np, pk = host_out ? (size_t)Ma * Mb : 0;    // K_ZX of one set, later the compact block
-        HIPCHK(g->Kxz.ensure(sizeof(double) * (kx > pk ? kx : pk)));
+    if (want_cov) {
+        const size_t kx = (size_t)(Map > Mbp ? Map : Mbp) * Np;                                          // K_ZX of one set, later the compact block
+        HIPCHK(g->Kxz.ensure(sizeof(double) * (kx > pack ? kx : pack)));
         HIPCHK(g->cov_Zs.ensure(sizeof(double) * (size_t)(Map + (sym ? 0 : Mbp)) * dp));
         HIPCHK(g->cov_V.ensure(sizeof(double) * (size_t)(Map + (sym ? 0 : Mbp)) * Np));
         HIPCHK(g->cov_C.ensure(sizeof(double) * (size_t)Map * Mbp));
     }
-    double* Vset[2] = {g->cov_V.as<double>(), g->cov_V.as<double>() + (cov ? Map * Np : 0)};
-    double* Zsset[2] = {g->cov_Zs.as<double>(), g->cov_Zs.as<double>() + (cov ? Map * dp : 0)};
+    double* Vset[2] = {g->cov_V.as<double>(), g->cov_V.as<double>() + (want_cov ? Map * Np : 0)};
+    double* Zsset[2] = {g->cov_Zs.as<double>(), g->cov_Zs.as<double>() + (want_cov ? Map * dp : 0)};
     double* muset[2] = {g->mu_all.as<double>(), g->mu_all.as<double>() + Map};
-    double* const mu_out[2] = {mu_a, mu_b};
     for (int q = 0; q < nsets; ++q) {
-        if (!cov && !mu_out[q]) continue;
+        if (!want_cov && !want_set[q]) continue;
         const double* Zd = Zin[q];
         if (z_space == ABO_HOST) {
             double* stage = g->Zdev.as<double>() + (q ? Ma * d : 0);
@@ -1505,10 +1518,10 @@ int32_t abo_predict_cov(abo_gp* g, const double* Za, int64_t Ma, const double* Z
             Zd = stage;
         }
         KgenArgs ka = kgen_model_args(g, true);             // (one output: pt = 1, and mean_vec is its [0] alone)
-        ka.Z = Zd; ka.alpha = g->alpha.as<double>(); ka.Kout = cov ? g->Kxz.as<double>() : nullptr;
+        ka.Z = Zd; ka.alpha = g->alpha.as<double>(); ka.Kout = want_cov ? g->Kxz.as<double>() : nullptr;
         ka.mu = muset[q]; ka.ldk = Np; ka.M = Ms[q]; ka.Mc = (int)Mps[q];
         HIPCHK(launch_kgen(ka, s));
-        if (!cov) continue;
+        if (!want_cov) continue;
         HIPCHK(launch_scale_points(Zd, Zsset[q], (int)Ms[q], (int)Mps[q], g->d, dp, 1.0 / g->prm.ell, s));
         GemmArgs a{};               // V[j][i] = Σ_{k ≤ i} Kzx[j][k]·W[i][k] = (L⁻¹k(X, z_j))[i]; padded rows j ≥ M are zero as those of Kzx are
         a.A = g->Kxz.as<double>(); a.lda = Np; a.B = g->st->W.as<double>(); a.ldb = ld;
@@ -1517,23 +1530,114 @@ int32_t abo_predict_cov(abo_gp* g, const double* Za, int64_t Ma, const double* Z
         HIPCHK(launch_gemm_nt(a, s));
         HIPCHK(launch_qei_zero_tail(Vset[q], Np, N, (int)Np, (int)Mps[q], s));
     }
-    if (cov) {
-        double* Cp = g->cov_C.as<double>();
+    double* Cp = want_cov ? g->cov_C.as<double>() : nullptr;
+    if (want_cov) {
         HIPCHK(launch_cov_prior(Zsset[0], Zsset[sym ? 0 : 1], (int)Ma, (int)Mb, dp, g->prm.family, g->prm.sigma_f2, sym ? 1 : 0, Cp, Mbp, s));
         GemmArgs b{};               // C −= V_a·V_bᵀ
         b.A = Vset[0]; b.lda = Np; b.B = Vset[sym ? 0 : 1]; b.ldb = Np; b.C = Cp; b.ldc = Mbp;
         b.M = (int)Map; b.N = (int)Mbp; b.K = (int)Np; b.kmode = K_FULL; b.lower_only = sym ? 1 : 0; b.batch = 1; b.alpha = -1.0; b.beta = 1.0;
         HIPCHK(launch_gemm_nt(b, s));
         if (sym) HIPCHK(launch_loo_mirror(Cp, Mbp, (int)Map, s));
+    }
+    *out = CovBlock{sym, Map, Mbp, {Vset[0], Vset[sym ? 0 : 1]}, {muset[0], muset[sym ? 0 : 1]}, Cp};
+    return ABO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Joint posterior covariance between two point sets (include/abo_hip.h): the shared stage above, then the compact copy-out.  Always the
+// fp64 engine: the int8-residue contraction squares one operand, a signed cross product is outside its error analysis.
+int32_t abo_predict_cov(abo_gp* g, const double* Za, int64_t Ma, const double* Zb, int64_t Mb, int32_t d, int32_t z_space, double* mu_a,
+                        double* mu_b, double* cov, int32_t out_space) {
+    if (const int32_t rc = cov_check(g, "abo_predict_cov", Za, Ma, Zb, &Mb, d, z_space, out_space)) return rc;
+    const bool sym = Zb == nullptr;
+    if (sym && mu_b) return fail(ABO_EINVAL, "abo_predict_cov: Zb is NULL (the symmetric form) but mu_b is given; the means are mu_a");
+    if (!mu_a && !mu_b && !cov) return ABO_OK;
+    HIPCHK(hipSetDevice(g->prm.device));
+    hipStream_t s = g->stream;
+    const bool host_out = out_space == ABO_HOST;
+    const bool want_set[2] = {mu_a != nullptr, mu_b != nullptr};
+    CovBlock cb{};
+    if (const int32_t rc = cov_block(g, Za, Ma, Zb, Mb, z_space, cov != nullptr, want_set, cov && host_out ? (size_t)Ma * Mb : 0, &cb)) return rc;
+    if (cov) {
         double* packed = host_out ? g->Kxz.as<double>() : cov;
-        HIPCHK(launch_cov_pack(Cp, Mbp, (int)Ma, (int)Mb, sym ? 1 : 0, packed, s));
+        HIPCHK(launch_cov_pack(cb.C, cb.Mbp, (int)Ma, (int)Mb, sym ? 1 : 0, packed, s));
         if (host_out) HIPCHK(hipMemcpyAsync(cov, packed, sizeof(double) * (size_t)Ma * Mb, hipMemcpyDeviceToHost, s));
     }
-    for (int q = 0; q < nsets; ++q) {
+    double* const mu_out[2] = {mu_a, mu_b};
+    const int64_t Ms[2] = {Ma, Mb};
+    for (int q = 0; q < (sym ? 1 : 2); ++q) {
         if (!mu_out[q]) continue;
-        const int32_t rc = copy_out(mu_out[q], muset[q], sizeof(double) * (size_t)Ms[q], out_space, s);
+        const int32_t rc = copy_out(mu_out[q], cb.mu[q], sizeof(double) * (size_t)Ms[q], out_space, s);
         if (rc) return rc;
     }
+    HIPCHK(wait_stream(s));
+    return ABO_OK;
+}
+
+// Knowledge gradient over a discrete decision set (include/abo_hip.h): the covariance stage of abo_predict_cov, then per
+// candidate the variance and the slope scale (kg.hip: launch_kg_prep), the row kernel on the padded block where it lies, and the
+// library's selection on the scores.  Nothing of the Ma × Mb block goes to the host.
+int32_t abo_acq_kg(abo_gp* g, const double* Za, int64_t Ma, const double* Zb, int64_t Mb, int32_t d, int32_t z_space, double noise,
+                   int32_t flags, int64_t idx_base, double* scores, int32_t k, double* top_val, int64_t* top_idx, int32_t out_space) {
+    if (const int32_t rc = cov_check(g, "abo_acq_kg", Za, Ma, Zb, &Mb, d, z_space, out_space)) return rc;
+    const bool sym = Zb == nullptr;
+    if (flags & ~ABO_KG_SELF) return fail(ABO_EINVAL, "abo_acq_kg: flags = %d holds bits other than ABO_KG_SELF", flags);
+    if (sym && (flags & ABO_KG_SELF))
+        return fail(ABO_EINVAL, "abo_acq_kg: ABO_KG_SELF with Zb NULL (the symmetric form holds every candidate's own point already)");
+    if (!std::isfinite(noise)) return fail(ABO_EINVAL, "abo_acq_kg: noise is not finite (negative: the noise the factor was built with)");
+    if (k < 0) return fail(ABO_EINVAL, "abo_acq_kg: k = %d is negative", k);
+    if (k > 0 && (!top_val || !top_idx)) return fail(ABO_EINVAL, "abo_acq_kg: k > 0 needs top_val and top_idx");
+    if (idx_base < 0) return fail(ABO_EINVAL, "abo_acq_kg: idx_base = %lld is negative", (long long)idx_base);
+    if (!scores && k == 0) return ABO_OK;
+    HIPCHK(hipSetDevice(g->prm.device));
+    hipStream_t s = g->stream;
+    const bool host_out = out_space == ABO_HOST;
+    const double nz = noise < 0.0 ? g->st->noise_used : noise;
+    // this call's own workspaces, like the stage's before the first launch
+    HIPCHK(g->kg_w.ensure(sizeof(double) * 2 * (size_t)Ma));
+    double* sc_d = scores;
+    if (!scores || host_out) { HIPCHK(g->score_all.ensure(sizeof(double) * (size_t)Ma)); sc_d = g->score_all.as<double>(); }
+    TopkWork w{};
+    double* tv = top_val;
+    int64_t* ti = top_idx;
+    if (k > 0) {
+        const int64_t we = topk_workspace_entries(Ma, k);
+        HIPCHK(g->tk_keys0.ensure(sizeof(uint64_t) * we));
+        HIPCHK(g->tk_keys1.ensure(sizeof(uint64_t) * we));
+        HIPCHK(g->tk_idx0.ensure(sizeof(int64_t) * we));
+        HIPCHK(g->tk_idx1.ensure(sizeof(int64_t) * we));
+        w = TopkWork{{g->tk_keys0.as<uint64_t>(), g->tk_keys1.as<uint64_t>()}, {g->tk_idx0.as<int64_t>(), g->tk_idx1.as<int64_t>()}};
+        if (host_out) {
+            HIPCHK(g->top_val.ensure(sizeof(double) * k));
+            HIPCHK(g->top_idx.ensure(sizeof(int64_t) * k));
+            tv = g->top_val.as<double>();
+            ti = g->top_idx.as<int64_t>();
+        }
+    }
+    const bool want_set[2] = {true, true};
+    CovBlock cb{};
+    if (const int32_t rc = cov_block(g, Za, Ma, Zb, Mb, z_space, true, want_set, 0, &cb)) return rc;
+    double* den = g->kg_w.as<double>();
+    double* self_b = den + Ma;
+    // v_i: the symmetric form's diagonal; the rectangular form's from the squared row norms of V_a (one wave per row, launch_kg_prep)
+    HIPCHK(launch_kg_prep(cb.V[0], g->Np, (int)g->N, sym ? cb.C : nullptr, cb.Mbp, (int)Ma, g->prm.sigma_f2, nz, den, self_b, s));
+    KgArgs ka{};
+    ka.a = cb.mu[1]; ka.asign = -1.0; ka.B = cb.C; ka.ldb = cb.Mbp; ka.den = den;
+    if (flags & ABO_KG_SELF) { ka.self_a = cb.mu[0]; ka.self_b = self_b; }
+    ka.Ma = (int)Ma; ka.Mb = (int)Mb; ka.val = sc_d; ka.nenv = nullptr;
+    HIPCHK(launch_kg_rows(ka, s));
+    if (k > 0) {
+        HIPCHK(launch_topk(sc_d, Ma, k, idx_base, w, tv, ti, s));
+        if (host_out) {
+            if (const int32_t rc = copy_out(top_val, tv, sizeof(double) * k, ABO_HOST, s)) return rc;
+            if (const int32_t rc = copy_out(top_idx, ti, sizeof(int64_t) * k, ABO_HOST, s)) return rc;
+        }
+    }
+    if (scores && host_out)
+        if (const int32_t rc = copy_out(scores, sc_d, sizeof(double) * (size_t)Ma, ABO_HOST, s)) return rc;
     HIPCHK(wait_stream(s));
     return ABO_OK;
 }

@@ -850,4 +850,20 @@ int32_t abo_test_score(int32_t device, const double* mu, const double* var, doub
     return ABO_OK;
 }
 
+// ---- the knowledge gradient's row kernel (csrc/kg.hip): the lines as handed in, one launcher, the null stream
+int32_t abo_test_kg_lines(int32_t device, const double* a, const double* B, int64_t ldb, int32_t Ma, int32_t Mb, const double* self_a,
+                          const double* self_b, double* val, int32_t* nenv) {
+    if (!a || !B || !val || !nenv) return fail(ABO_EINVAL, "abo_test_kg_lines: null argument");
+    if ((self_a == nullptr) != (self_b == nullptr)) return fail(ABO_EINVAL, "abo_test_kg_lines: self_a and self_b go together");
+    if (Ma < 0 || Mb < 1 || Mb > KG_MAX_LINES || ldb < Mb)
+        return fail(ABO_EINVAL, "abo_test_kg_lines: Ma >= 0, 1 <= Mb <= %d, ldb >= Mb", KG_MAX_LINES);
+    KgArgs k{};
+    k.a = a; k.B = B; k.ldb = ldb; k.den = nullptr; k.self_a = self_a; k.self_b = self_b; k.asign = 1.0; k.Ma = Ma; k.Mb = Mb;
+    k.val = val; k.nenv = nenv;
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(launch_kg_rows(k, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
 }  // extern "C"

@@ -464,6 +464,100 @@ def sample_joint(model: HipStandardGP, x, n: int, rng=None, jitter=None):
                                   f"{ladder[-1]:.3e}")
 
 
+# ---- knowledge gradient over a discrete decision set (abo_acq_kg) -----------------------------------------
+KG_CHUNK = COV_MAX_POINTS          # candidates per abo_acq_kg call
+
+
+def _host_top_k(scores, k):
+    """the library's order on the host: descending, ties to the lowest index, NaN first; (NaN, −1) behind len(scores) < k"""
+    s = np.asarray(scores, dtype=np.float64)
+    key = np.where(np.isnan(s), np.inf, s)
+    order = np.argsort(-key, kind="stable")[:k]
+    val, idx = np.full(k, np.nan), np.full(k, -1, dtype=np.int64)
+    val[:order.shape[0]], idx[:order.shape[0]] = s[order], order
+    return val, idx
+
+
+def knowledge_gradient(model: HipStandardGP, candidates, decision=None, noise=None, include_self=True, k: int = 0):
+    """Knowledge gradient of every candidate over a discrete decision set (minimisation): the expected decrease of
+    min_j μ(decision_j) from one observation at the candidate (Frazier, Powell and Dayanik 2009; include/abo_hip.h: abo_acq_kg).
+    decision None: the candidates themselves (the symmetric form; include_self is ignored); else up to 8192 points, and include_self
+    adds each candidate's own point to its row (KGCP — what one wants when `decision` is the training set).  noise None: the noise the
+    factor was built with; a number ≥ 0: that observation noise.  Returns the scores, and (scores, top_val, top_idx) when k > 0 —
+    descending, ties to the lowest index.  Host inputs give NumPy arrays, tensors on the model's GPU give tensors there.  More than
+    8192 candidates against a given decision set run in chunks of 8192, their selections merged on the host in the same order; the
+    symmetric form takes at most 8192.  An ARD model is served through `to_model_space`."""
+    what = "knowledge_gradient"
+    _cov_model(model, what)
+    k = int(k)
+    if k < 0:
+        raise ValueError(f"{what}: k = {k} is negative")
+    nz = -1.0 if noise is None else float(noise)
+    if noise is not None and not (math.isfinite(nz) and nz >= 0.0):
+        raise ValueError(f"{what}: noise must be a finite number ≥ 0 (None: the model's own), got {noise}")
+    if np.isscalar(candidates):
+        candidates = [float(candidates)]
+    pa, ma, d, space, keep_a = as_points(to_model_space(model, candidates))
+    want = getattr(model, "_d", None)
+    if want is not None and d != want:
+        raise _lib.DimensionMismatch(f"DimensionMismatch: candidates have dimension {d}, model dimension {want}")
+    if ma < 1:
+        raise ValueError(f"{what}: no candidates")
+    pb, mb, keep_b, flags = None, 0, None, 0
+    if decision is None:
+        if ma > COV_MAX_POINTS:
+            raise ValueError(f"{what}: the symmetric form (decision=None) takes 1 to {COV_MAX_POINTS} candidates, got {ma}")
+    else:
+        pb, mb, db, space_b, keep_b = _cov_points(model, decision, "decision")
+        if db != d:
+            raise _lib.DimensionMismatch(f"DimensionMismatch: candidates have dimension {d}, decision has dimension {db}")
+        if space_b != space:
+            raise ValueError("candidates and decision must both be host arrays or both be tensors on the model's GPU")
+        flags = _lib.KG_SELF if include_self else 0
+    h = model._require()
+    on_device = space == DEVICE
+    if on_device:
+        import torch
+        scores = torch.empty(ma, dtype=torch.float64, device=keep_a.device)
+    else:
+        scores = np.empty(ma, dtype=np.float64)
+    chunk = max(1, int(KG_CHUNK))
+    nchunks = (ma + chunk - 1) // chunk
+    parts = []
+    for c in range(nchunks):
+        i0 = c * chunk
+        n = min(chunk, ma - i0)
+        kk = min(k, n) if nchunks > 1 else k          # (a chunk's selection never needs more than its own points)
+        if on_device:
+            tv = torch.empty(kk, dtype=torch.float64, device=keep_a.device)
+            ti = torch.empty(kk, dtype=torch.int64, device=keep_a.device)
+            ptrs = (scores[i0:].data_ptr(), tv.data_ptr() if kk else None, ti.data_ptr() if kk else None)
+        else:
+            tv, ti = np.empty(kk, dtype=np.float64), np.empty(kk, dtype=np.int64)
+            ptrs = (scores[i0:].ctypes.data, tv.ctypes.data if kk else None, ti.ctypes.data if kk else None)
+        st = _lib.lib().abo_acq_kg(h, pa + i0 * d * 8, n, pb, mb, d, space, nz, flags, i0, ptrs[0], kk, ptrs[1], ptrs[2], space)
+        _lib.check(st)
+        parts.append((tv, ti))
+    del keep_b
+    if k == 0:
+        return scores
+    if nchunks == 1:
+        return scores, parts[0][0], parts[0][1]
+    # merge on the host: the chunks' selections hold every candidate of the overall selection; ranked by (score, index) in the library's order
+    if on_device:
+        cv = np.concatenate([p[0].cpu().numpy() for p in parts])
+        ci = np.concatenate([p[1].cpu().numpy() for p in parts])
+    else:
+        cv, ci = np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+    by_index = np.argsort(ci, kind="stable")                       # ties to the lowest candidate index
+    val, pos = _host_top_k(cv[by_index], k)
+    idx = np.where(pos >= 0, ci[by_index][np.maximum(pos, 0)], -1)
+    if on_device:
+        import torch
+        return scores, torch.from_numpy(val).to(keep_a.device), torch.from_numpy(idx).to(keep_a.device)
+    return scores, val, idx
+
+
 # ---- NLML ----------------------------------------------------------------------------------------
 def nlml_fitted(model: HipStandardGP) -> float:
     """NLML of the model's own fitted state (no refit)."""

@@ -49,7 +49,7 @@ extern "C" {
                                   (struct abo_paths_append_stats is new); ABO_ACQ_LOGEI (kind 5 in every entry point that takes a kind
                                   or an abo_acq_term, and in the pruned top-k selection); ABO_ACQ_MES and abo_score_mes, abo_acq_mes,
                                   abo_cand_acq_mes, abo_refine_mes, abo_optimize_acquisition_mes; abo_get_prune_levels; abo_loo, abo_loo_grad;
-                                  abo_predict_cov; abo_remove, ABO_REMOVE_REMOVED / _REFIT */
+                                  abo_predict_cov; abo_remove, ABO_REMOVE_REMOVED / _REFIT; abo_acq_kg, ABO_KG_SELF */
 
 /* status codes */
 enum {
@@ -713,6 +713,31 @@ int32_t abo_loo_grad(abo_gp* gp, double* nlpl, double* d_log_ell, double* d_log_
 int32_t abo_predict_cov(abo_gp* gp, const double* Za, int64_t Ma, const double* Zb, int64_t Mb, int32_t d, int32_t z_space, double* mu_a,
                         double* mu_b, double* cov, int32_t out_space);
 
+/* added within ABI 7: knowledge gradient over a discrete decision set (Frazier, Powell and Dayanik 2009; with ABO_KG_SELF the KGCP of Scott
+ * et al. 2011) — the expected decrease of the minimum of the posterior mean over the decision set Zb from ONE observation at a candidate
+ * za_i (minimisation, as every acquisition here):
+ *   KG_i = min_j mu_j − E[min_j (mu_j + s_ij·Z)] = E[max_j (a_j + b_ij·Z)] − max_j a_j >= 0,   Z ~ N(0, 1),
+ *   a_j = −mu(zb_j),   b_ij = s_ij = cov(f(za_i), f(zb_j)) / sqrt(v_i + noise),   v_i = var f(za_i)  (latent, + 1e-18 as abo_predict's).
+ * Exact: per candidate the Mb lines sorted by (b, a), of equal slopes the largest intercept kept, one scan for the upper envelope
+ * e_0 … e_m with breakpoints c_1 … c_m, KG = Σ_t (b_{e_t} − b_{e_{t−1}})·h(−|c_t|), h(z) = phi(z) + z·Phi(z) — every term >= 0, summed in
+ * envelope order.  It needs no best_y and no xi or beta.  mu and the covariance are abo_predict_cov's (the means abo_predict's bit for
+ * bit); the Ma × Mb block stays on the device: one number per candidate comes back.
+ * Zb == NULL is the symmetric form: the decision set is Za itself (Mb must be 0 or Ma), the covariance the half-product plus mirror,
+ * v_i its diagonal; row i's own point is in the set.  With Zb given, flags = ABO_KG_SELF adds the candidate's own line
+ * (a = −mu(za_i), b = v_i / sqrt(v_i + noise)) to row i — what one wants when Zb is the training set; the flag is ABO_EINVAL in the symmetric
+ * form, as is any other bit.  noise < 0: the noise the factor was built with (abo_loo's); noise >= 0 as given; NaN or Inf: ABO_EINVAL.
+ * Degenerate rows: v_i + noise <= 1e-12 gives exactly 0.0 (the sigma² <= 1e-12 branch of the EI / PI epilogues); one line, or all slopes
+ * equal, gives exactly 0.0; a non-finite mean or covariance in the row gives NaN.
+ * scores (Ma values, may be NULL) and the k selected pairs (top_val, top_idx + idx_base; Julia's stable reverse order: descending, ties to
+ * the lowest index, NaN first; (NaN, −1) behind Ma < k) in out_space; Za / Zb in z_space.
+ * 1 <= Ma, Mb <= 8192; d must be the model's (ABO_EDIM); a null, an unfitted or a gradient-enhanced handle is ABO_EINVAL; every argument is
+ * checked before any device work.  Always on the fp64 MFMA kernels, for abo_predict_cov's reason: the same bits on every call and under
+ * either abo_set_contraction setting.  Works on appended views and on a parent after a child was appended, as abo_predict_cov does.
+ * Cost: abo_predict_cov's, plus per candidate a sort of Mb pairs in LDS and a sequential envelope scan of Mb steps by one lane. */
+enum { ABO_KG_SELF = 1 };
+int32_t abo_acq_kg(abo_gp* gp, const double* Za, int64_t Ma, const double* Zb, int64_t Mb, int32_t d, int32_t z_space, double noise,
+                   int32_t flags, int64_t idx_base, double* scores, int32_t k, double* top_val, int64_t* top_idx, int32_t out_space);
+
 /* --- introspection (tests) ----------------------------------------------------------------------
  * L (N×N row-major, strictly-upper part zero), alpha (N), Linv = L⁻¹ (N×N row-major); any may be
  * NULL.  Host buffers. */
@@ -1133,6 +1158,12 @@ int32_t abo_test_oz_modpack(int32_t device, const int32_t* x, int64_t n4, int32_
 /* HOST only, no device: the tile list of a residue GEMM over Ti x Tj tiles and nmod moduli as the kernel decodes it: *count = 8 * per_list
  * (the launcher's `blocks`), tiles[y * per_list + q] = ti | tj << 9 | l << 20, or -1 for a padding block (tiles may be null) */
 int32_t abo_test_oz_tickets(int32_t Ti, int32_t Tj, int32_t nmod, int32_t* tiles, int64_t* count);
+/* --- the knowledge gradient's row kernel (csrc/kg.hip) on lines handed in directly, no model ---
+ * launch_kg_rows on the null stream: row i < Ma has the Mb lines (intercept a[j], slope B[i·ldb + j]) and — self_a and self_b given, both
+ * or neither — its own line (self_a[i], self_b[i]); val[i] = E[max_j (a_j + b_ij·Z)] − max_j a_j, nenv[i] = lines on the upper envelope
+ * (0 for a row with a non-finite value, whose val is NaN).  1 <= Mb <= 8192, ldb >= Mb.  Every pointer is DEVICE memory. */
+int32_t abo_test_kg_lines(int32_t device, const double* a, const double* B, int64_t ldb, int32_t Ma, int32_t Mb, const double* self_a,
+                          const double* self_b, double* val, int32_t* nenv);
 #endif /* ABO_TEST_HOOKS */
 
 #ifdef __cplusplus

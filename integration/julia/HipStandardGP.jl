@@ -586,6 +586,9 @@ include("LeaveOneOut.jl")
 # joint posterior covariance between point sets (abo_predict_cov): posterior_cov and mean_and_cov
 include("PosteriorCov.jl")
 
+# knowledge gradient over a discrete decision set (abo_acq_kg): knowledge_gradient
+include("KnowledgeGradient.jl")
+
 # a model without some of its observations in O(N²) (abo_remove): remove_points
 include("RemovePoints.jl")
 
