@@ -1,4 +1,5 @@
-// Internal C++ interface between api.hip (single-device handles) and mgpu.hip (the multi-device driver).
+// Internal C++ interface between the single-device host driver (api.hip, posterior.hip, acq.hip, cand.hip, qei_host.hip) and the units
+// that see its handles from outside: mgpu.hip (the multi-device driver), update.hip, paths.hip, qei_mc.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -32,7 +33,7 @@ int32_t refine_terms(abo_gp* g, const abo_acq_term* terms, int32_t nterms, const
 void pick_best_point(const double* starts_x, const double* starts_val, const double* rx, const double* rf, int k, int d,
                      double* best_x, double* best_val);
 
-// ---- greedy q-EI, block form (api.hip; include/abo_hip.h: abo_cand_qei_*): the per-shard steps with records in DEVICE memory, and
+// ---- greedy q-EI, block form (qei_host.hip; include/abo_hip.h: abo_cand_qei_*): the per-shard steps with records in DEVICE memory, and
 // the batch driver over the n shards of one set (n = 1: abo_cand_qei; n > 1: abo_mgpu_cand_qei, whose shards run on their worker
 // threads and exchange records through the group's all-gather)
 int32_t qei_eligible(abo_gp* g, abo_cand* c, int q);       // ABO_OK when the block form can run on this shard (else the reason)
@@ -60,7 +61,7 @@ int32_t qei_drive(const QeiShards& S, int q, double xi, double best_y, int disti
 // ---- Monte-Carlo joint q-EI (qei_mc.hip: abo_cand_qei_mc) on the block state of ONE set.  _open: qei_eligible, then the set's blocks
 // continue (or start afresh) as under qei_begin, with the chain left exactly as it is (only its real entries [0, nreal) are read);
 // *keep receives the statistics of the set's last greedy batch, which _close puts back.  qei_block builds blocks on the open state.
-struct QeiMcStats { int builds; double block_ms, pass_ms, pass_bytes, pass_flop; };
+struct QeiBatchStats { int builds; double block_ms, pass_ms, pass_bytes, pass_flop; };   // block builds of a batch, their time, the last pass over K_ZX
 struct QeiMcView {
     double* mu; double* var; const double* Z;        // device, [M], [M], [M][d]
     const double* blk; const double* chain;          // device, [slots][Mp] block columns, [rows][Mp] the set's chain
@@ -69,12 +70,12 @@ struct QeiMcView {
     const int* blk_base;                             // host, [nslots / T16]
     const int64_t* slot_gidx;                        // host, [nslots]
     const double* chain_s;                           // host, [nreal …] pivots of the chain entries
-    QeiMcStats now;                                  // statistics of the open batch so far
+    QeiBatchStats now;                              // statistics of the open batch so far
 };
 // (hidden: the shipped library exports the C-ABI's abo_cand_qei_mc, not these)
-__attribute__((visibility("hidden"))) int32_t qei_mc_open(abo_gp* g, abo_cand* c, int q, int T, int64_t idx_base, QeiMcStats* keep);
+__attribute__((visibility("hidden"))) int32_t qei_mc_open(abo_gp* g, abo_cand* c, int q, int T, int64_t idx_base, QeiBatchStats* keep);
 __attribute__((visibility("hidden"))) void qei_mc_view(abo_cand* c, QeiMcView* v);        // valid until the next block build
-__attribute__((visibility("hidden"))) void qei_mc_close(abo_cand* c, const QeiMcStats& keep);
+__attribute__((visibility("hidden"))) void qei_mc_close(abo_cand* c, const QeiBatchStats& keep);
 
 hipStream_t gp_stream(abo_gp* g);
 int gp_device(const abo_gp* g);
@@ -97,6 +98,7 @@ bool gp_append_view(abo_gp* g, AppendView* out);
 int32_t cand_downdate_column(abo_gp* g, abo_cand* c, double* tmp, const double** col, int* route);
 
 // ---- abo_update / abo_mgpu_update (update.hip): what they read of a handle, and the append / pool / wait machinery of api.hip
+// (the gp_* accessors are api.hip's, the cand_* ones cand.hip's)
 struct GpState {
     bool fitted = false;
     int device = 0, d = 0, p_out = 1;

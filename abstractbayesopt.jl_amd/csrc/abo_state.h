@@ -1,6 +1,6 @@
-// Private state of the single-device host driver: what its units — api.hip, posterior.hip, acq.hip, and test_hooks.hip in the test
-// library — share: the handle struct with the types it is made of, the event slots of a handle, and the internal functions that are
-// called across a unit boundary or by the abo_test_* hooks.  Nothing else includes this header: mgpu.hip, update.hip, paths.hip and
+// Private state of the single-device host driver: what its units — api.hip, posterior.hip, acq.hip, cand.hip, qei_host.hip, and
+// test_hooks.hip in the test library — share: the handle and candidate-set structs with the types they are made of, the event slots of
+// a handle, and the internal functions that are called across a unit boundary or by the abo_test_* hooks.  Nothing else includes this header: mgpu.hip, update.hip, paths.hip and
 // qei_mc.hip see the handles through the accessors of abo_internal.h.  Declarations only: every variable and every function declared
 // here is defined once, in the unit its comment names.
 #pragma once
@@ -37,7 +37,7 @@ hipError_t wait_stream(hipStream_t s);                     // the polled wait ev
 extern std::atomic<uint64_t> g_storage_gen;                // next Storage::gen
 hipError_t pool_alloc(int dev, size_t bytes, void** p, size_t* cap);
 void pool_free(int dev, void* p, size_t cap);
-// api.hip — what every entry point of the three units starts and ends with
+// api.hip — what every entry point of the host units starts and ends with
 int32_t check_fitted(abo_gp* g, int32_t d);                // also tells phase_events() the size of the model the calling thread works on
 int32_t stage_candidates(abo_gp* g, const double* Z, int64_t M, int32_t z_space, const double** Zd);
 int32_t copy_in(void* dst, const void* src, size_t bytes, int32_t space, hipStream_t s);
@@ -285,8 +285,75 @@ struct abo_gp {
     }
 };
 
+// candidate set resident in HBM with its posterior (C5: O(N·M) down-dates instead of re-evaluation) — cand.hip; its block-form
+// q-EI state (Qei) is driven by qei_host.hip.  Each device buffer named once, as on the handle.
+#define ABO_CAND_BUFS(X)                                                                                                            \
+    X(Z) X(mu) X(var) X(score) X(cdot) X(tk_keys0) X(tk_keys1) X(tk_idx0) X(tk_idx1) X(top_val) X(top_idx) X(mu_bak) X(var_bak)      \
+    X(Kzx) X(qblk) X(qchain) X(qwork) X(qrec) X(qmu) X(qvar) X(qdev)
+struct abo_cand {
+    int device = 0, d = 0;
+    int64_t M = 0;
+    uint64_t synced_gen = 0;              // Storage::gen of the factor the mu/var belong to (0 = none)
+    int64_t synced_N = -1;
+    uint64_t bak_gen = 0;                 // abo_cand_save snapshot
+    int64_t bak_N = -1;
+    // the last one-row abo_cand_downdate: the append it served (abo_gp::ap_serial) and where it left the column c(z) — 0: cdot (which
+    // nothing else writes), 1: entry dd_chain of the chain.  The resident sample-path values (paths.hip) read the column there.
+    uint64_t dd_serial = 0;
+    int dd_src = -1, dd_chain = -1;
+    uint64_t mu_epoch = 1;                // grows whenever the stored μ — and with it the exclusions — may have changed other than by a down-date
+    ABO_CAND_BUFS(ABO_DEVBUF_MEMBER)
+    // Kzx: resident K_ZX (candidate-major, kzx_ld doubles per candidate, column k = training row k of synced_st): kept when
+    // it fits the budget (ABO_CAND_KZX_GIB, default 64), so that a down-date streams it once instead of re-evaluating
+    // N·M kernel values; kzx_ld = 0 → not resident, the down-date recomputes
+    int64_t kzx_ld = 0;
+    bool resident(const abo_gp* g) const { return kzx_ld > 0 && kzx_ld == g->st->cap; }       // … and laid out for g's factor storage
+    bool in_sync(const abo_gp* g) const { return g->st->gen == synced_gen && g->N == synced_N; }
+    // block form of greedy q-EI (qei.hip).  Base = the model the set was synced with when the state was last reset (gen, N).
+    //   qblk   [nblk_cap][T16][Mp]  covariances Cov(z, x_t) of the block points under the model of the block's build (ring of blocks)
+    //   qchain [rows][Mp]           c_i(z) = Cov_{i−1}(z, x_i) of every conditioning since the base, in order: entries [0, nreal) are
+    //                               REAL appends (abo_cand_downdate), entries [nreal, nchain) the fantasies of the open / last batch
+    // Blocks and real entries OUTLIVE a batch: the next batch on the appended model keeps them (a BO step's picks are mostly the
+    // previous step's runners-up: their columns exist already), a block column is corrected by the chain entries made since the
+    // block's build (slot_base).  The fantasies of the last batch stay until the next one begins: appending its picks for real, in
+    // order, finds each down-date column there (c_i does not depend on the observed value).
+    struct Qei {
+        bool open = false;
+        uint64_t gen = 0;
+        int64_t N = -1, Mp = 0;
+        int64_t idx_base = -1;                    // the global index of the shard's first candidate the slots below were keyed with (−1: none yet)
+        int T16 = 0, nblk_cap = 0, next_blk = 0, qmax = 0;
+        std::vector<int64_t> slot_gidx;           // global candidate index per block row (−1: empty)
+        std::vector<double> slot_x;               // [rows][d] the block points
+        std::vector<int> blk_base;                // [nblk_cap] chain entries that existed when the block was built (already in its columns)
+        int nreal = 0, nchain = 0, chain_rows = 0;
+        std::vector<double> chain_x;              // [nchain][d] the conditioned points
+        std::vector<double> chain_s;              // [nchain] s_i = σ²_{i−1}(x_i) + σ²_n
+        abo::QeiBatchStats stats{};               // of the current / last batch
+        int batch0 = 0;                           // nchain when the batch began
+    } qei;
+    void set_device(int dev) {
+        device = dev;
+#define X(name) name.dev = dev;
+        ABO_CAND_BUFS(X)
+#undef X
+    }
+    void free_all() {
+#define X(name) name.release();
+        ABO_CAND_BUFS(X)
+#undef X
+        kzx_ld = 0;
+        qei = Qei();
+    }
+};
+
 #pragma GCC visibility push(hidden)
 namespace abo {
+
+void set_exiting();                                        // api.hip: latches exiting() — for a destroy that finds the runtime gone
+// cand.hip: the k best of the set's M scores sc_d (device), into top_val / top_idx in out_space; launches and copies only
+int32_t cand_topk(abo_gp* g, abo_cand* c, const double* sc_d, int32_t k, int64_t idx_base, double* top_val, int64_t* top_idx, int32_t out_space);
+int32_t qei_resync(abo_gp* g, abo_cand* c, int64_t rows_now, bool* ok);   // qei_host.hip: the set's block state in line with a model of rows_now rows
 
 // api.hip: the fields of KgenArgs that describe the MODEL of a fitted handle — Xs, N, Np, d, dp, family, s, sigma_f2, pt, and with_mean:
 // mean_c, mean_vec (else both zero: the launch forms no mean) —, everything else as KgenArgs{} leaves it.  A call site adds its launch

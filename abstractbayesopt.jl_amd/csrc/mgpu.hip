@@ -8,7 +8,7 @@
 // stable reverse sort globally (descending score, ties → lowest index, NaN first).  The reference has no multi-device
 // code of its own; BASELINE configs 4 and 5 define this path.
 //
-// No arithmetic lives here: every device runs the single-device entry points of api.hip on its own handle.
+// No arithmetic lives here: every device runs the single-device entry points (api.hip and its sibling units) on its own handle.
 #include <dlfcn.h>
 #include <rccl/rccl.h>   // types and prototypes only: the functions are resolved with dlsym (no link-time dependency)
 
@@ -927,7 +927,7 @@ int32_t abo_mgpu_cand_qei(abo_mgpu* mg, abo_mcand* mc, int32_t q, double xi, dou
     const auto t0 = std::chrono::steady_clock::now();
     mc->qei_last = abo_qei_stats{};
     mc->qei_last.picks = q;
-    // Block form (include/abo_hip.h, api.hip: qei_drive): the covariance columns of the T best candidates from ONE pass over each
+    // Block form (include/abo_hip.h, qei_host.hip: qei_drive): the covariance columns of the T best candidates from ONE pass over each
     // shard's resident K_ZX, no fantasy appends; what the shards exchange are pick records {EI, index, μ, σ², x[d], c_1(x) … c_n(x)}
     // (one per pick) and, when a block is built, T of them per shard.  Every shard applies the same exchanged numbers, so the
     // sharded batch repeats the single handle's arithmetic bit for bit.  Falls back to the plain loop below when a shard does not

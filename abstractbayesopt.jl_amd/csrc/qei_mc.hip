@@ -396,7 +396,7 @@ int32_t abo_cand_qei_mc(abo_gp* g, abo_cand* c, int32_t q, double xi, double bes
                                 "the block form: pass block = 16..%d", QEI_MAXT);
     if (cand_size(c) < q)
         return fail(ABO_EINVAL, "abo_cand_qei_mc: %lld candidates for q = %d distinct picks", (long long)cand_size(c), q);
-    QeiMcStats keep{};
+    QeiBatchStats keep{};
     int32_t rc = qei_mc_open(g, c, q, T, idx_base, &keep);       // (its refusals name abo_cand_qei_mc and their reason)
     if (rc) return rc;
     rc = qei_mc_drive(g, c, q, xi, best_y, base, S, base_space, idx_base, T > QEI_MAXT ? QEI_MAXT : T, x_out, idx_out, qei_out);

@@ -81,7 +81,7 @@ def test_argument_validation_needs_no_gpu():
 
 
 def test_every_host_unit_reports_through_the_one_error_slot():
-    """The host driver is four translation units (api.hip, posterior.hip, acq.hip, and test_hooks.hip in the test library) with ONE
+    """The host driver is six translation units (api.hip, posterior.hip, acq.hip, cand.hip, qei_host.hip, and test_hooks.hip in the test library) with ONE
     last-error slot per thread, defined in api.hip: null-argument calls across its surfaces and into a hook — the argument check is the
     first thing each of these does, no device is touched — return ABO_EINVAL, and abo_last_error then holds THAT call's message, the
     function's name in it.  A unit with a private copy of the slot would leave the previous call's text (or none) there.
@@ -99,7 +99,8 @@ def test_every_host_unit_reports_through_the_one_error_slot():
         ("abo_acq_lhs", lambda: lib.abo_acq_lhs(None, 1, 1, None, None, 0, 0, 0.0, 0.0, 1, None, None, None)),
         ("abo_refine", lambda: lib.abo_refine(None, 0, 0.0, 0.0, None, None, 1, None, 0, None, None, None, None)),
         ("abo_fit_acq", lambda: lib.abo_fit_acq(None, None, 1, 1, None, 0, None, None, 0, 0, 0, 0.0, 0.0, 0, None, 0, None, None, 0)),
-        ("abo_cand_create", lambda: lib.abo_cand_create(None, None, 0, 1, 0, None)),
+        ("abo_cand_create", lambda: lib.abo_cand_create(None, None, 0, 1, 0, None)),                                       # cand.hip
+        ("abo_cand_qei", lambda: lib.abo_cand_qei(None, None, 1, 0.0, 0.0, 0, 0, 0, None, None, None, None)),           # qei_host.hip
         ("abo_test_acq_grad", lambda: lib.abo_test_acq_grad(None, 0, 0.0, 0.0, None, 0, 1, None, None)),          # test_hooks.hip, the other unit
     ]
     for name, call in calls + calls[::-1]:              # both orders: every message replaces its predecessor's

@@ -157,9 +157,12 @@ def test_resident_values_and_picks_follow_the_model(from_chain):
           float(np.max(np.abs(ev - r["steps"][-1]["vals"]))) / math.sqrt(hp[2]), 2.0 * bar)
 
 
-def test_the_recomputed_column_serves_a_set_whose_down_date_was_not_the_last_writer():
+@pytest.mark.parametrize("kzx_gib", ["64", "0"], ids=["resident", "recomputing"])
+def test_the_recomputed_column_serves_a_set_whose_down_date_was_not_the_last_writer(monkeypatch, kzx_gib):
     """two sets down-dated with the same appended model: each finds its own column; a set that was refreshed to the appended model
-    instead of down-dated has no column in place and gets it recomputed (column_from_chain == 2) — never a stale one"""
+    instead of down-dated has no column in place and gets it recomputed (column_from_chain == 2) — never a stale one.  Under both
+    budgets of the resident K_ZX: with it the column is one product over K_ZX, without it the kernel values are evaluated again"""
+    monkeypatch.setenv("ABO_CAND_KZX_GIB", kzx_gib)
     rng, X, y, hp, base, model = make(1, 3, 120, 2, 16, 128, 1e-3, 0.5, seed=77, n_max=512)
     Z = rng.random((1500, 3))
     cands = abo.ResidentCandidates(model, Z)
