@@ -9,7 +9,7 @@ from .acquisition import (AbstractAcquisition, EnsembleAcquisition, ExpectedImpr
                           update_and_evaluate)
 from .domains import ContinuousDomain
 from . import gradient_gp as _g
-from .gradient_gp import (GradientNormUCB, HipGradientGP, gradConstMean, posterior_grad_cov, posterior_grad_mean,
+from .gradient_gp import (GradientNormUCB, HipGradientGP, gradConstMean, gradnorm_ucb_host, posterior_grad_cov, posterior_grad_mean,
                           posterior_grad_var)
 from .hyperparams import (lengthscale_bounds, loo_and_grad, monte_carlo_fill_distance, nlml_and_grad, nlml_and_grad_ard,
                           optimize_hyperparameters)

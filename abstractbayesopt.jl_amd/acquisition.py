@@ -260,6 +260,16 @@ def evaluate(acq: AbstractAcquisition, surrogate: HipStandardGP, x, k: int = 0, 
             raise ValueError("evaluate: KnowledgeGradient takes no idx_base")
         r = acq.evaluate(surrogate, x, k=k)
         return (r[0] if return_scores else None, r[1], r[2]) if k > 0 else (r if return_scores else None, None, None)
+    if getattr(acq, "kind", None) == ACQ_GRADNORM_UCB and not hasattr(surrogate, "p"):
+        # a value-only model: abo_predict_deriv scores the batch (abo_acq_terms keeps refusing the term on such a handle), the
+        # selection is the host's
+        from .surrogate import _host_top_k
+        scores = acq(surrogate, x)
+        tv = ti = None
+        if k > 0:
+            tv, ti = _host_top_k(scores, k)
+            ti = np.where(ti >= 0, ti + idx_base, -1)
+        return (scores if return_scores else None), tv, ti
     if isinstance(acq, EnsembleAcquisition) or getattr(acq, "kind", None) == ACQ_GRADNORM_UCB:
         terms = flatten_terms(acq, surrogate)
         if terms is None or hasattr(surrogate, "devices"):

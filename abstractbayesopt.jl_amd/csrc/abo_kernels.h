@@ -269,6 +269,27 @@ inline bool kgen_writes_residues(const KgenArgs& a, int n) {
     return a.dp <= 32 && !a.dlogell && (n == 14 || (kgen_short_moduli(n) && a.res_kmax > 0 && a.pt == 1));
 }
 hipError_t launch_kgen(const KgenArgs& a, hipStream_t s);
+// ---- value-only model against (f, ∇f) query outputs (kgen_deriv.hip; abo_predict_deriv) ----
+// For the chunk's points j < npts (global index pt0 + j) and p = d + 1, with e = (Xs_k − s·z_j), u = ‖e‖²:
+//   Kout[j·p][k] = sigma_f2·φ(u),   Kout[j·p + c + 1][k] = −sigma_f2·φ'(u)·2e_c·s   for k < N, 0 for N ≤ k < Np
+//   mu_rows[j·p + q] = (q == 0 ? mean_c : 0) + Σ_k Kout[j·p + q][k]·alpha[k]   (a fixed order: the same bits on every launch)
+// Rows npts·p ≤ r < rows_pad of Kout (columns < Np) and of mu_rows are written as 0; nothing else is.  Families SE, Matérn-5/2 and
+// Matérn-7/2 (φ, φ' of kgen_grad_core.h), d ≤ 32 with dp ∈ {1, 2, 4, 8, 16, 32}; hipErrorInvalidValue, and no launch, for anything else,
+// for a chunk that leaves [0, M) and for rows_pad < npts·p.
+struct KgenDerivArgs {
+    const double* Xs;     // [Np][dp]   training points, pre-scaled by 1/ell, zero padded
+    const double* Z;      // [M][d]     raw query points, scaled on load
+    const double* alpha;  // [Np] (only k < N is read), or nullptr: zeros
+    double* Kout;         // [rows_pad][ldk]
+    double* mu_rows;      // [rows_pad], or nullptr
+    int64_t ldk;
+    int64_t M, pt0;       // query points overall; first point of this chunk
+    int npts;             // points of this chunk
+    int64_t rows_pad;     // rows of Kout the launch writes (≥ npts·(d + 1): what the contraction behind it reads)
+    int N, Np, d, dp, family;
+    double s, sigma_f2, mean_c;
+};
+hipError_t launch_kgen_deriv(const KgenDerivArgs& a, hipStream_t s);
 // ---- the μ-only tail of the pruned selection's bound pass (kgen_tail.hip) ----
 // over the N training points: norms[0] = Σ_{k ≥ k0} |alpha_k|, norms[1] = Σ_k |alpha_k|, norms[2] = max_{k ≥ k0} |Xs_k|² — one
 // workgroup, fixed order

@@ -384,6 +384,8 @@ int32_t posterior(abo_gp* g, const double* Zd, int64_t Mpts, int kind, double p0
                   double* score_out, const PostOpts& o = {});
 // gradient-enhanced model: mean of all P outputs, P×P covariance block and GradientNormUCB score per point; launches only
 int32_t grad_eval_device(abo_gp* g, const double* Zd, int64_t M, double beta, double* mu_d, double* cov_d, double* sc_d);
+// value-only model: the same outputs for the (f, ∇f) posterior, P = d + 1 (abo_predict_deriv); always on the fp64 GEMM; launches only
+int32_t deriv_eval_device(abo_gp* g, const double* Zd, int64_t M, double beta, double* mu_d, double* cov_d, double* sc_d);
 void collect_posterior_timings(abo_gp* g, bool with_var);  // behind the call's synchronisation: phase times and work of its passes
 bool wants_int8(const abo_gp* g, bool want_var, int pc, int* nmod);   // the engine of a posterior call's contraction, and its moduli
 double grad_prior_var(const abo_gp* g);                    // prior variance of a gradient output

@@ -1,6 +1,7 @@
 // The chunked posterior pass of the single-device host driver and what feeds it: the choice of the contraction engine and of the chunk,
 // the int8 engine's scratch and its residue planes of W, the pass itself (posterior) with the options the pruned selection's bound
-// passes use, the all-output evaluation of a gradient-enhanced model (grad_eval_device), the timings both leave — and the entry points
+// passes use, the all-output evaluation of a gradient-enhanced model (grad_eval_device) and the derivative posterior of a value-only
+// one (deriv_eval_device), the timings they leave — and the entry points
 // that are nothing but such a pass over the caller's points.  Host-side orchestration only; declared in abo_state.h.
 #include <hip/hip_runtime.h>
 
@@ -418,6 +419,70 @@ int32_t grad_eval_device(abo_gp* g, const double* Zd, int64_t M, double beta, do
     return ABO_OK;
 }
 
+// VALUE-ONLY model (p_out == 1): the same three outputs for the (f, ∇f) posterior of M points, p = d + 1 — mu_d [M][p], cov_d [M][p][p],
+// sc_d [M] in DEVICE memory, any of them null; launches only.  The pt == 1 sibling of grad_eval_device: per chunk the cross-kernel
+// generator of kgen_deriv.hip, V = K·L⁻ᵀ on the triangular fp64 MFMA product and the per-point epilogue of misc.hip.
+// The contraction ALWAYS runs on the fp64 GEMM, whatever the handle's contraction says: the int8-residue engine scales the derivative
+// query outputs of a gradient-enhanced factor by a per-row power of two that goes with that factor's own derivative rows
+// (oz_grad_exp); the scaling for derivative outputs against a value-only factor is a piece of work of its own.
+// Points per chunk: V ≤ 256 MiB as in grad_eval_device, capped by a positive abo_params.chunk.  Every row of V, every mean and every
+// block is formed by the same instructions in the same order wherever the chunk boundaries fall (the small and the tiled GEMM kernel
+// agree bit for bit: gemm.hip): the result does not depend on the chunk, or on the call.
+// The chunks' phases are timed in the per-chunk event slots of a posterior pass (collect_posterior_timings reads them).
+int32_t deriv_eval_device(abo_gp* g, const double* Zd, int64_t M, double beta, double* mu_d, double* cov_d, double* sc_d) {
+    hipStream_t s = g->stream;
+    const int P = g->d + 1;
+    const int64_t Np = g->Np;
+    int64_t pts = (((int64_t)1 << 28) / (Np * (int64_t)sizeof(double))) / P;
+    if (g->prm.chunk > 0 && pts > g->prm.chunk) pts = g->prm.chunk;
+    if (pts < 1) pts = 1;
+    if (pts > M) pts = M;
+    const int64_t rows_pad = pad_up(pts * P, TB);
+    const int64_t nchunk = (M + pts - 1) / pts;
+    g->passes.clear();
+    g->tm.var_gemm_launches = 0;
+    g->oz_prepare_pending = false;
+    g->tm.oz_prepare_ms = 0.0;
+    HIPCHK(g->events(ev_chunk(nchunk, EVC_KGEN_BEGIN)));
+    g->passes.push_back({0, nchunk, M * P, g->N, 0, false});
+    g->tm.contraction_engine = ABO_CONTRACT_FP64;
+    g->tm.oz_nmod = 0;
+    HIPCHK(g->Kxz.ensure(sizeof(double) * rows_pad * Np));
+    HIPCHK(g->partial.ensure(sizeof(double) * rows_pad * Np));       // V
+    HIPCHK(g->mu_c.ensure(sizeof(double) * rows_pad));
+    for (int64_t c = 0; c < nchunk; ++c) {
+        const int64_t p0 = c * pts;
+        const int64_t np = (M - p0) < pts ? (M - p0) : pts;
+        const int64_t rows = pad_up(np * P, TB);
+        auto ev = [&](EvChunk slot) { return g->evs()[ev_chunk(c, slot)]; };
+        KgenDerivArgs ka{};
+        ka.Xs = g->st->Xs.as<double>(); ka.Z = Zd; ka.alpha = g->alpha.as<double>();
+        ka.Kout = g->Kxz.as<double>(); ka.mu_rows = g->mu_c.as<double>(); ka.ldk = Np;
+        ka.M = M; ka.pt0 = p0; ka.npts = (int)np; ka.rows_pad = rows;
+        ka.N = (int)g->N; ka.Np = (int)Np; ka.d = g->d; ka.dp = g->dp; ka.family = g->prm.family;
+        ka.s = 1.0 / g->prm.ell; ka.sigma_f2 = g->prm.sigma_f2; ka.mean_c = g->prm.mean_c;
+        PHASE_EVENT(ev(EVC_KGEN_BEGIN), s);
+        HIPCHK(launch_kgen_deriv(ka, s));
+        PHASE_EVENT(ev(EVC_KGEN_END), s);
+        GemmArgs a{};               // V[row][i] = Σ_k Kxz[row][k]·W[i][k]
+        a.A = g->Kxz.as<double>(); a.lda = Np; a.B = g->st->W.as<double>(); a.ldb = g->st->cap;
+        a.C = g->partial.as<double>(); a.ldc = Np; a.M = (int)rows; a.N = (int)Np; a.K = (int)Np;
+        a.kmode = K_B_LOWER; a.batch = 1; a.alpha = 1.0; a.beta = 0.0;           // W[i][k] = 0 for k > i: half the product
+        PHASE_EVENT(ev(EVC_CONTRACT_BEGIN), s);
+        HIPCHK(launch_gemm_nt(a, s));
+        PHASE_EVENT(ev(EVC_CONTRACT_END), s);
+        g->tm.var_gemm_launches += 1;
+        GradCovArgs ca{};
+        ca.V = g->partial.as<double>(); ca.mu_rows = g->mu_c.as<double>(); ca.ldv = Np; ca.R = (int)g->N; ca.p = P;
+        ca.pt0 = p0; ca.prior0 = g->prm.sigma_f2; ca.prior_g = grad_prior_var(g); ca.beta = beta;
+        ca.cov_out = cov_d; ca.mu_out = mu_d; ca.score_out = sc_d;
+        PHASE_EVENT(ev(EVC_EPILOGUE_BEGIN), s);
+        HIPCHK(launch_grad_cov(ca, (int)np, s));
+        PHASE_EVENT(ev(EVC_EPILOGUE_END), s);
+    }
+    return ABO_OK;
+}
+
 // phase times and algorithmic work of the call's posterior passes (what was launched: a bound pass counts its R rows, a survivor pass
 // its survivors — with ONE exception: survivors whose scores were taken from the threshold pass, acq.hip: prune_survivors, are counted
 // as if their pass had been launched; the pass of no chunks that stands for them adds work and no time)
@@ -544,6 +609,44 @@ int32_t abo_predict_grad_cov(abo_gp* g, const double* Z, int64_t M, int32_t d, i
     if (cov && out_space == ABO_HOST) { rc = copy_out(cov, cov_d, sizeof(double) * M * P * P, ABO_HOST, s); if (rc) return rc; }
     if (score && out_space == ABO_HOST) { rc = copy_out(score, sc_d, sizeof(double) * M, ABO_HOST, s); if (rc) return rc; }
     HIPCHK(wait_stream(s));
+    return ABO_OK;
+}
+
+int32_t abo_predict_deriv(abo_gp* g, const double* Z, int64_t M, int32_t d, int32_t z_space, double beta, double* mu,
+                          double* cov, double* score, int32_t out_space) {
+    // every refusal names the call and comes before any device work
+    if (!g) return fail(ABO_EINVAL, "abo_predict_deriv: null handle");
+    if (!g->fitted) return fail(ABO_EINVAL, "abo_predict_deriv: the surrogate is not conditioned on data yet (call abo_fit first)");
+    if (g->p_out > 1) return fail(ABO_EINVAL, "abo_predict_deriv: the model is gradient-enhanced (abo_predict_grad_cov serves it)");
+    if (d != g->d) return fail(ABO_EINVAL, "abo_predict_deriv: candidate dimension %d, model dimension %d", d, g->d);
+    if (g->d > 32) return fail(ABO_EINVAL, "abo_predict_deriv: d = %d, at most 32 coordinates are supported", g->d);
+    if (g->prm.family != ABO_KERNEL_SE && g->prm.family != ABO_KERNEL_MATERN52 && g->prm.family != ABO_KERNEL_MATERN72)
+        return fail(ABO_EINVAL, "abo_predict_deriv: kernel family %d has no derivative posterior here (SE, Matern-5/2 and Matern-7/2 do)", g->prm.family);
+    if (M < 0 || (M > 0 && !Z)) return fail(ABO_EINVAL, "abo_predict_deriv: bad candidate buffer (null Z or M < 0)");
+    if (M == 0) return ABO_OK;
+    int32_t rc = check_fitted(g, d);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(g->prm.device));
+    hipStream_t s = g->stream;
+    const int P = g->d + 1;
+    const double* Zd = nullptr;
+    rc = stage_candidates(g, Z, M, z_space, &Zd);
+    if (rc) return rc;
+    double* mu_d = nullptr; double* cov_d = nullptr; double* sc_d = nullptr;
+    if (mu) { if (out_space == ABO_DEVICE) mu_d = mu; else { HIPCHK(g->mu_all.ensure(sizeof(double) * M * P)); mu_d = g->mu_all.as<double>(); } }
+    if (cov) { if (out_space == ABO_DEVICE) cov_d = cov; else { HIPCHK(g->var_all.ensure(sizeof(double) * M * P * P)); cov_d = g->var_all.as<double>(); } }
+    if (score) { if (out_space == ABO_DEVICE) sc_d = score; else { HIPCHK(g->score_all.ensure(sizeof(double) * M)); sc_d = g->score_all.as<double>(); } }
+    HIPCHK(hipEventRecord(g->evs()[EV_ACQ_BEGIN], s));
+    rc = deriv_eval_device(g, Zd, M, beta, mu_d, cov_d, sc_d);
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(g->evs()[EV_ACQ_SCORED], s));
+    if (mu && out_space == ABO_HOST) { rc = copy_out(mu, mu_d, sizeof(double) * M * P, ABO_HOST, s); if (rc) return rc; }
+    if (cov && out_space == ABO_HOST) { rc = copy_out(cov, cov_d, sizeof(double) * M * P * P, ABO_HOST, s); if (rc) return rc; }
+    if (score && out_space == ABO_HOST) { rc = copy_out(score, sc_d, sizeof(double) * M, ABO_HOST, s); if (rc) return rc; }
+    HIPCHK(wait_stream(s));
+    collect_posterior_timings(g, true);
+    g->tm.acq_topk_ms = 0.0;
+    g->tm.acq_total_ms = ev_ms(g->evs()[EV_ACQ_BEGIN], g->evs()[EV_ACQ_SCORED]);
     return ABO_OK;
 }
 

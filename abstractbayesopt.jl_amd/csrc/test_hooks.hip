@@ -602,6 +602,24 @@ int32_t abo_test_kgen(int32_t device, const abo_test_kgen_args* t) {
     return ABO_OK;
 }
 
+// launch_kgen_deriv with the caller's arguments as they are
+int32_t abo_test_kgen_deriv(int32_t device, const double* Xs, const double* alpha, const double* Z, double* Kout, double* mu_rows,
+                            int64_t ldk, int64_t M, int64_t pt0, int32_t npts, int64_t rows_pad, int32_t N, int32_t Np, int32_t d, int32_t dp,
+                            int32_t family, double s, double sigma_f2, double mean_c) {
+    if (!Xs || !Z || !Kout) return fail(ABO_EINVAL, "abo_test_kgen_deriv: null argument");
+    KgenDerivArgs a{};
+    a.Xs = Xs; a.Z = Z; a.alpha = alpha; a.Kout = Kout; a.mu_rows = mu_rows; a.ldk = ldk; a.M = M; a.pt0 = pt0; a.npts = npts;
+    a.rows_pad = rows_pad; a.N = N; a.Np = Np; a.d = d; a.dp = dp; a.family = family; a.s = s; a.sigma_f2 = sigma_f2; a.mean_c = mean_c;
+    HIPCHK(hipSetDevice(device));
+    const hipError_t e = launch_kgen_deriv(a, nullptr);
+    if (e == hipErrorInvalidValue)
+        return fail(ABO_EINVAL, "abo_test_kgen_deriv: launch_kgen_deriv refused family = %d, d = %d, dp = %d, N = %d, Np = %d, npts = %d, rows_pad = %lld",
+                    family, d, dp, N, Np, npts, (long long)rows_pad);
+    HIPCHK(e);
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
 int32_t abo_test_cand_newcol(int32_t device, const double* Xs, const double* Z, double* Kzx, int64_t ld, int64_t M, int32_t col, int32_t grad,
                              int32_t pt, int32_t q, int32_t d, int32_t dp, int32_t family, double s, double sigma_f2) {
     if (!Xs || !Z || !Kzx) return fail(ABO_EINVAL, "abo_test_cand_newcol: null argument");

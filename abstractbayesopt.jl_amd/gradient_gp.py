@@ -16,7 +16,7 @@ from . import _lib
 from ._lib import DEVICE, HOST
 from .acquisition import AbstractAcquisition
 from .kernels import Kernel, extract_scale_and_lengthscale, with_lengthscale
-from .surrogate import HipStandardGP, _Handle, _is_torch, as_points, refuse_ard
+from .surrogate import HipStandardGP, _Handle, _is_torch, ard_lengthscales, as_points, refuse_ard, to_model_space
 
 
 class gradConstMean:
@@ -119,20 +119,75 @@ def _grad_predict(model: HipGradientGP, x, want_mu=True, want_var=True):
     return mu, var
 
 
-def posterior_grad_mean(model: HipGradientGP, x):
-    """posterior_grad_mean (GradientGP.jl:936-938): all p outputs, ordered by outputs (length p·M)."""
+def gradnorm_ucb_host(mu, cov, beta: float):
+    """GradientNormUCB (gradNormUCB.jl:43-51) from point-major means (M, p) and blocks (M, p, p), on the gradient block:
+    −(mᵀm + trΣ) + β·sqrt(max(4mᵀΣm + 2‖Σ‖_F², 1e-12))"""
+    m, S = mu[:, 1:], cov[:, 1:, 1:]
+    mean = np.einsum("jc,jc->j", m, m) + np.einsum("jcc->j", S)
+    var = 4.0 * np.einsum("jc,jce,je->j", m, S, m) + 2.0 * np.einsum("jce,jce->j", S, S)
+    return -mean + float(beta) * np.sqrt(np.maximum(var, 1e-12))
+
+
+def _deriv_predict(model: HipStandardGP, x, beta: float = 0.0, want_mu=True, want_cov=True, want_score=False):
+    """The posterior of (f, ∇f) under a VALUE-ONLY model (abo_predict_deriv): point-major means (M, p), per-point blocks (M, p, p) and
+    GradientNormUCB(β) scores (M,), p = d + 1, as NumPy arrays (None for what was not asked for).
+    An ARD model crosses the C-ABI on coordinates x′_c = x_c/ℓ_c, so what comes back is the gradient with respect to x′: the chain rule
+    ∇_x = D⁻¹∇_x′, Σ_x = D⁻¹Σ_x′D⁻¹ with D = diag(1, ℓ_1 … ℓ_d) over all p outputs (the mixed f/∇f row and column take one factor)
+    is applied here, and the score is formed from the rescaled mean and block."""
+    if hasattr(model, "devices"):
+        raise TypeError("posterior_grad_* / GradientNormUCB: a sharded model (HipShardedGP) is not supported: abo_predict_deriv has no "
+                        "multi-device twin; use a single-device HipStandardGP")
+    if not isinstance(model, HipStandardGP):
+        raise TypeError(f"posterior_grad_* needs a HipStandardGP or a HipGradientGP, not {type(model).__name__}")
+    if np.isscalar(x):
+        x = [float(x)]
+    ell = ard_lengthscales(model)
+    zp, m, d, zspace, keep = as_points(to_model_space(model, x))
+    if zspace != HOST:
+        keep = keep.cpu().numpy(); zp = keep.ctypes.data
+    p = d + 1
+    ard = ell is not None
+    mu = np.empty((m, p)) if want_mu or (ard and want_score) else None
+    cov = np.empty((m, p, p)) if want_cov or (ard and want_score) else None
+    sc = np.empty(m) if want_score and not ard else None
+    ptr = lambda a: a.ctypes.data if a is not None else None
+    _lib.check(_lib.lib().abo_predict_deriv(model._require(), zp, m, d, HOST, float(beta), ptr(mu), ptr(cov), ptr(sc), HOST))
+    if ard:
+        dinv = np.concatenate(([1.0], 1.0 / ell))
+        if mu is not None:
+            mu = mu * dinv[None, :]
+        if cov is not None:
+            cov = cov * dinv[None, :, None] * dinv[None, None, :]
+        if want_score:
+            sc = gradnorm_ucb_host(mu, cov, beta)
+    return (mu if want_mu else None), (cov if want_cov else None), sc
+
+
+def posterior_grad_mean(model: HipStandardGP, x):
+    """posterior_grad_mean (GradientGP.jl:936-938): all p outputs, ordered by outputs (length p·M).  A value-only HipStandardGP gives
+    the same layout from the closed-form posterior of its gradient (abo_predict_deriv; NumPy out)."""
+    if not hasattr(model, "p"):
+        return np.ascontiguousarray(_deriv_predict(model, x, want_cov=False)[0].T).reshape(-1)
     return _grad_predict(model, x, True, False)[0]
 
 
-def posterior_grad_var(model: HipGradientGP, x):
-    """posterior_grad_var (GradientGP.jl:951-953)."""
+def posterior_grad_var(model: HipStandardGP, x):
+    """posterior_grad_var (GradientGP.jl:951-953); a value-only HipStandardGP as in posterior_grad_mean."""
+    if not hasattr(model, "p"):
+        return np.ascontiguousarray(np.einsum("jqq->qj", _deriv_predict(model, x, want_mu=False)[1])).reshape(-1)
     return _grad_predict(model, x, False, True)[1]
 
 
-def posterior_grad_cov(model: HipGradientGP, x, beta: float = 0.0, return_all: bool = False):
+def posterior_grad_cov(model: HipStandardGP, x, beta: float = 0.0, return_all: bool = False):
     """posterior_grad_cov (GradientGP.jl:966-971) for the outputs of ONE point → (p, p); for M points the
     per-point blocks (M, p, p) (cross-point covariances are not formed).  return_all=True also gives the
-    point-major means (M, p) and the GradientNormUCB(β) scores (M,) computed in the same pass."""
+    point-major means (M, p) and the GradientNormUCB(β) scores (M,) computed in the same pass.
+    A value-only HipStandardGP is served by abo_predict_deriv, with p = d + 1."""
+    if not hasattr(model, "p"):
+        mu, cov, sc = _deriv_predict(model, x, beta=beta, want_mu=return_all, want_score=return_all)
+        if return_all:
+            return mu, cov, sc
+        return cov[0] if cov.shape[0] == 1 else cov
     L = _lib.lib()
     zp, m, d, zspace, keep = as_points(x)
     if zspace != HOST:
@@ -262,10 +317,14 @@ class GradientNormUCB(AbstractAcquisition):
     def _p0(self):
         return self.beta
 
-    def __call__(self, surrogate: HipGradientGP, x):
-        if not isinstance(surrogate, HipGradientGP):
-            raise TypeError("GradientNormUCB needs a gradient-enhanced surrogate")
-        return posterior_grad_cov(surrogate, x, beta=self.beta, return_all=True)[2]
+    def __call__(self, surrogate: HipStandardGP, x):
+        if isinstance(surrogate, HipGradientGP):
+            return posterior_grad_cov(surrogate, x, beta=self.beta, return_all=True)[2]
+        # the reference defines it on the posterior of the gradient, not on how the model was trained: a value-only model's comes
+        # from abo_predict_deriv
+        if not isinstance(surrogate, HipStandardGP) or hasattr(surrogate, "p"):
+            raise TypeError("GradientNormUCB needs a HipGradientGP or a single-device HipStandardGP")
+        return _deriv_predict(surrogate, x, beta=self.beta, want_mu=False, want_cov=False, want_score=True)[2]
 
     def __eq__(self, other):
         return isinstance(other, GradientNormUCB) and other.beta == self.beta

@@ -49,7 +49,7 @@ extern "C" {
                                   (struct abo_paths_append_stats is new); ABO_ACQ_LOGEI (kind 5 in every entry point that takes a kind
                                   or an abo_acq_term, and in the pruned top-k selection); ABO_ACQ_MES and abo_score_mes, abo_acq_mes,
                                   abo_cand_acq_mes, abo_refine_mes, abo_optimize_acquisition_mes; abo_get_prune_levels; abo_loo, abo_loo_grad;
-                                  abo_predict_cov; abo_remove, ABO_REMOVE_REMOVED / _REFIT; abo_acq_kg, ABO_KG_SELF */
+                                  abo_predict_cov; abo_remove, ABO_REMOVE_REMOVED / _REFIT; abo_acq_kg, ABO_KG_SELF; abo_predict_deriv */
 
 /* status codes */
 enum {
@@ -311,6 +311,27 @@ int32_t abo_predict_grad(abo_gp* gp, const double* Z, int64_t M, int32_t d, int3
  * block (src/acquisition_functions/gradNormUCB.jl:43-51).  Any output may be NULL. */
 int32_t abo_predict_grad_cov(abo_gp* gp, const double* Z, int64_t M, int32_t d, int32_t z_space, double beta,
                              double* mu, double* cov, double* score, int32_t out_space);
+
+/* added within ABI 7: the same three outputs for a VALUE-ONLY model (abo_create) — the posterior of (f, ∇f) at M points under a GP
+ * conditioned on function values alone, p = d + 1 outputs per point.  With J(z) = ∂k(X, z)/∂z (N × d), V = L⁻¹[k(X, z) J(z)]:
+ *   mu[j] = (mean_c + k(X, z_j)ᵀalpha, J(z_j)ᵀalpha),   cov[j] = diag(sigma_f2, k″·I) − VᵀV,   k″ = −2·sigma_f2·φ'(0)/ell²
+ * (the prior variance of a gradient output: sigma_f2/ell² SE, 5/3 of it Matérn-5/2, 7/5 Matérn-7/2).  mu [M][p], cov [M][p][p]
+ * (point-major, symmetric, + 1e-18 on the diagonal as abo_predict_grad_cov adds it), score [M] = the GradientNormUCB value on the
+ * gradient block exactly as abo_predict_grad_cov defines it; any of them may be NULL; Z in z_space, the outputs in out_space.
+ * mu[j][0] and cov[j][0][0] are abo_predict's mean and variance to rounding.  M = 0 returns ABO_OK and writes nothing.
+ * ABO_EINVAL, before any device work and with the call's name in abo_last_error: a null or unfitted handle; a gradient-enhanced
+ * handle (abo_predict_grad_cov serves it); d not the model's; d > 32; the Matérn-3/2 family (the derivative blocks are built for the three
+ * families a gradient-enhanced model takes); M < 0; a null Z with M > 0.
+ * The contraction ALWAYS runs on the fp64 MFMA GEMM, whatever abo_set_contraction says (abo_timings.contraction_engine reports
+ * ABO_CONTRACT_FP64): the int8-residue engine's per-row scaling for derivative query outputs on a value-only factor is a piece of work
+ * of its own.  The result is the same bit for bit on every call and for every abo_params.chunk (a positive chunk caps the points per
+ * chunk; otherwise V = p·N doubles per point stays within 256 MiB per chunk).  Works on appended views and after abo_remove, as
+ * abo_predict does.  abo_timings: acq_kxz_ms the generator, acq_var_gemm_ms the GEMM, acq_finalize_ms the per-point epilogue.
+ * Out of scope: multi-device handles (abo_mgpu_*) have no twin of this call; abo_acq_terms and the on-device refinement keep refusing a
+ * GRADNORM_UCB term on a value-only handle; abo_optimize_acquisition is untouched.
+ * Cost: p·M·N² flop for V (half of it skipped in the triangle) and p²·M·N/2 for the blocks; workspace 2·p·N doubles per point of a chunk. */
+int32_t abo_predict_deriv(abo_gp* gp, const double* Z, int64_t M, int32_t d, int32_t z_space, double beta,
+                          double* mu, double* cov, double* score, int32_t out_space);
 
 /* --- acquisition over a candidate batch -------------------------------------------------------
  * scores = acqf(surrogate, grid_points); sortperm(scores; rev=true)[1:k]
@@ -1022,6 +1043,15 @@ typedef struct abo_test_kgen_args {
  * ABO_EINVAL, and no launch, where launch_kgen refuses: an unknown family, a dp outside the dispatch table, planes for a shape or a
  * moduli count the fused output is not built for, a res_kmax that is no multiple of 128 or exceeds Np */
 int32_t abo_test_kgen(int32_t device, const abo_test_kgen_args* args);
+/* launch_kgen_deriv (csrc/kgen_deriv.hip) alone, on the null stream: the rows (f, ∂f/∂z_1 … ∂f/∂z_d) of the query points pt0 … pt0 + npts − 1
+ * of Z [M][d] against the N function values of a value-only model — Xs ALREADY scaled by s and zero padded [Np][dp], alpha [Np] (may be
+ * null: zeros) — into Kout [rows_pad][ldk] and mu_rows [rows_pad] (may be null); all pointers DEVICE memory.  Rows behind npts·(d + 1)
+ * up to rows_pad and the columns N … Np − 1 are written as 0, nothing else is.  ABO_EINVAL, and no launch, where the launcher refuses:
+ * d > 32, a dp outside 1, 2, 4, 8, 16, 32 or below d, a family other than SE / Matérn-5/2 / Matérn-7/2, Np no multiple of 128, N > Np,
+ * ldk < Np, a chunk outside [0, M), rows_pad < npts·(d + 1) */
+int32_t abo_test_kgen_deriv(int32_t device, const double* Xs, const double* alpha, const double* Z, double* Kout, double* mu_rows,
+                            int64_t ldk, int64_t M, int64_t pt0, int32_t npts, int64_t rows_pad, int32_t N, int32_t Np, int32_t d, int32_t dp,
+                            int32_t family, double s, double sigma_f2, double mean_c);
 /* launch_cand_newcol (grad = 0: column `col` of a resident K_ZX, Xs row `col`) or launch_cand_newcol_grad (grad = 1: training row
  * (point pt, output q) against the function value of every candidate, written to column `col`) */
 int32_t abo_test_cand_newcol(int32_t device, const double* Xs, const double* Z, double* Kzx, int64_t ld, int64_t M, int32_t col, int32_t grad,

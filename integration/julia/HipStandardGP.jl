@@ -208,6 +208,21 @@ posterior_var(m::HipStandardGP, x::AbstractVector)  = _predict(m, x, false, true
 posterior_mean(m::HipStandardGP, x::Real) = posterior_mean(m, [x])                        # StandardGP.jl:329
 posterior_var(m::HipStandardGP, x::Real)  = posterior_var(m, [x])                         # StandardGP.jl:345
 
+# posterior of (f, ∇f) under the value-only model (abo_predict_deriv): means p × M, covariance blocks p × p × M and GradientNormUCB(β)
+# scores, p = d + 1; posterior_grad_mean / _var return by outputs, as GradientGP.jl:936-953 do.  One device only.
+function _deriv(m::HipStandardGP, x, β)
+    m.gpx === nothing && throw(ArgumentError("surrogate is not conditioned on data yet (gpx === nothing)"))
+    m.gpx.multi && error("posterior_grad_*: a sharded model has no abo_predict_deriv; use a single-device HipStandardGP")
+    Z = _pack(x); d, M = size(Z); p = d + 1
+    mu = Matrix{Float64}(undef, p, M); cov = Array{Float64}(undef, p, p, M); sc = Vector{Float64}(undef, M)
+    GC.@preserve Z mu cov sc _check(@abocall LIBABO.abo_predict_deriv(m.gpx.ptr::Ptr{Cvoid}, Z::Ptr{Float64}, M::Int64, d::Int32,
+        0::Int32, Float64(β)::Float64, mu::Ptr{Float64}, cov::Ptr{Float64}, sc::Ptr{Float64}, 0::Int32)::Int32)
+    mu, cov, sc
+end
+posterior_grad_mean(m::HipStandardGP, x) = vec(permutedims(_deriv(m, x isa Real ? [x] : x, 0.0)[1]))
+posterior_grad_var(m::HipStandardGP, x) = (c = _deriv(m, x isa Real ? [x] : x, 0.0)[2]; [c[q, q, j] for q in axes(c, 1) for j in axes(c, 3)])
+posterior_grad_cov(m::HipStandardGP, x) = (c = _deriv(m, x isa Real ? [x] : x, 0.0)[2]; size(c, 3) == 1 ? c[:, :, 1] : c)
+
 # ---- fused acquisition: more specific than (EI)(::AbstractSurrogate, x) at ExpectedImprovement.jl:40 ---------------
 function _acq(m::HipStandardGP, x, kind, p0, best; k=0, scores=true)
     Z = _pack(x); d, M = size(Z)
