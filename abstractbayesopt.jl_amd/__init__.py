@@ -13,7 +13,7 @@ from .gradient_gp import (GradientNormUCB, HipGradientGP, gradConstMean, gradnor
                           posterior_grad_var)
 from .hyperparams import (lengthscale_bounds, loo_and_grad, monte_carlo_fill_distance, nlml_and_grad, nlml_and_grad_ard,
                           optimize_hyperparameters)
-from .incremental import ResidentCandidates, append, greedy_qei, mc_qei, remove_points
+from .incremental import ResidentCandidates, append, append_points, greedy_qei, mc_qei, remove_points
 from .multigpu import HipShardedGP, HipShardedGradientGP, ShardedCandidates
 from .kernels import (ApproxMatern52Kernel, ApproxMatern72Kernel, ConstMean, Kernel, Matern32Kernel, Matern52Kernel,
                       ScaledKernel, SqExponentialKernel, ZeroMean, with_lengthscale)

@@ -26,13 +26,13 @@ EXPORTS = ["abo_create", "abo_set_contraction", "abo_create_grad", "abo_predict_
            "abo_paths_create", "abo_paths_destroy", "abo_paths_eval", "abo_paths_eval_cand", "abo_paths_stats_get",
            "abo_paths_append", "abo_paths_attach", "abo_paths_detach", "abo_paths_top", "abo_paths_values", "abo_paths_append_stats_get",
            "abo_score_mes", "abo_acq_mes", "abo_cand_acq_mes", "abo_refine_mes", "abo_optimize_acquisition_mes",
-           "abo_loo", "abo_loo_grad", "abo_predict_cov", "abo_remove", "abo_acq_kg", "abo_predict_deriv"]
+           "abo_loo", "abo_loo_grad", "abo_predict_cov", "abo_remove", "abo_acq_kg", "abo_predict_deriv", "abo_append_batch"]
 TEST_EXPORTS = ["abo_test_gemm_nt", "abo_test_kappa", "abo_test_oz_plan", "abo_test_oz_contract", "abo_test_acq_grad",
                 "abo_test_acq_grad_terms", "abo_test_prune_plan", "abo_test_prune_force", "abo_test_prune_levels", "abo_test_prune_plan_levels", "abo_test_prune_bounds", "abo_test_prune_mean", "abo_test_prune_head",
                 "abo_test_kappa_tail", "abo_test_prune_tail32", "abo_test_prune_reuse", "abo_test_prune_reused", "abo_test_prune_head32", "abo_test_bound_head32", "abo_test_kappa_tail32", "abo_test_prune_bound_moduli", "abo_test_prune_bound_plan", "abo_test_oz_contract_bound", "abo_test_acq_partials", "abo_test_mes_partials", "abo_test_acq_grad_mes",
                 "abo_test_gemm_args", "abo_test_gemm_path", "abo_test_gemm_swz_q", "abo_test_gemm_swz_map", "abo_test_qei_pass", "abo_test_splitk_reduce",
                 "abo_test_var_gemm", "abo_test_kgen", "abo_test_kgen_deriv", "abo_test_cand_newcol",
-                "abo_test_chol_diag", "abo_test_chol_panel", "abo_test_trtri_batched", "abo_test_chol_blocked", "abo_test_trmv",
+                "abo_test_chol_diag", "abo_test_chol_panel", "abo_test_trtri_batched", "abo_test_chol_blocked", "abo_test_trmv", "abo_test_tri_skinny", "abo_test_live_views",
                 "abo_test_nlml_terms", "abo_test_append",
                 "abo_test_topk_plan", "abo_test_topk", "abo_test_prune_compact", "abo_test_prune_min_scatter", "abo_test_prune_map",
                 "abo_test_finalize", "abo_test_cand_gemv", "abo_test_downdate", "abo_test_grad_cov", "abo_test_gather_points",
@@ -283,6 +283,8 @@ def lib():
         L.abo_test_trtri_batched.argtypes = [i32, vp, vp, vp, i64, i32, vp]
         L.abo_test_chol_blocked.argtypes = [i32, vp, vp, vp, i64, i32, i32, i32, i32, vp]
         L.abo_test_trmv.argtypes = [i32, vp, i64, vp, vp, i32, i32]
+        L.abo_test_tri_skinny.argtypes = [i32, vp, i64, vp, vp, i32, i32, i32]
+        L.abo_test_live_views.argtypes = [vp, vp, i32, C.POINTER(i32)]
         L.abo_test_nlml_terms.argtypes = [i32, vp, i64, vp, vp, i32, vp]
         L.abo_test_append.argtypes = [i32, C.POINTER(AboTestAppendArgs)]
         L.abo_test_topk_plan.argtypes = [i64, i32, vp]
@@ -374,6 +376,7 @@ def lib():
     L.abo_mgpu_optimize_acquisition_terms.argtypes = L.abo_optimize_acquisition_terms.argtypes
     L.abo_update.argtypes = [vp, C.POINTER(AboParams), vp, vp, i64, i32, vp, i32, C.POINTER(i64), C.POINTER(i32), C.POINTER(vp)]
     L.abo_remove.argtypes = [vp, vp, i32, C.POINTER(i32), C.POINTER(vp)]
+    L.abo_append_batch.argtypes = [vp, vp, i32, i32, vp, i32, C.POINTER(i64), C.POINTER(vp)]
     L.abo_mgpu_update.argtypes = [vp, C.POINTER(AboParams), vp, vp, i64, i32, vp, C.POINTER(i64), C.POINTER(i32), C.POINTER(vp)]
     L.abo_fit_acq.argtypes = [vp, vp, i64, i32, vp, i32, C.POINTER(i64), vp, i64, i32, i32, f64, f64, i64, vp, i32, vp, vp, i32]
     for name in EXPORTS + (TEST_EXPORTS if hooks else []):

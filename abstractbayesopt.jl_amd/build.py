@@ -10,7 +10,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "lib", "libabo_hip.so")
 LIB_TEST = os.path.join(PKG, "lib", "libabo_hip_test.so")
 TEST_SOURCE = "test_hooks.hip"     # linked into the test library only; the one unit compiled under -DABO_TEST_HOOKS (the header declares the hooks under it)
-SOURCES = ["kgen.hip", "kgen_res.hip", "kgen_res_short.hip", "kgen_res_short9.hip", "kgen_res_short10.hip", "kgen_tail.hip", "kgen_tail32.hip", "kgen_head32.hip", "kgen_grad_res.hip", "kgen_deriv.hip", "gemm.hip", "ozaki.hip", "chol.hip", "misc.hip", "qei.hip", "qei_mc.hip", "paths.hip", "refine.hip", "api.hip", "posterior.hip", "acq.hip", "cand.hip", "qei_host.hip", "mgpu.hip", "update.hip", "loo.hip", "cov.hip", "remove.hip", "kg.hip"]
+SOURCES = ["kgen.hip", "kgen_res.hip", "kgen_res_short.hip", "kgen_res_short9.hip", "kgen_res_short10.hip", "kgen_tail.hip", "kgen_tail32.hip", "kgen_head32.hip", "kgen_grad_res.hip", "kgen_deriv.hip", "gemm.hip", "ozaki.hip", "chol.hip", "misc.hip", "qei.hip", "qei_mc.hip", "paths.hip", "refine.hip", "api.hip", "posterior.hip", "acq.hip", "cand.hip", "qei_host.hip", "mgpu.hip", "update.hip", "loo.hip", "cov.hip", "remove.hip", "kg.hip", "append_batch.hip"]
 # -amdgpu-mfma-vgpr-form: keep fp64 MFMA accumulators in VGPRs; the AGPR form makes hipcc shuttle
 # every accumulator through v_accvgpr_read/write each k-step (2.2x slower, profiles/r01_mfma_f64_probe.txt)
 # -ldl / -pthread: the multi-device driver resolves RCCL with dlopen and runs one host thread per shard

@@ -497,6 +497,39 @@ struct AppendArgs {
 };
 hipError_t launch_append(const AppendArgs& a, hipStream_t s);
 
+// ---- blocked bordered append (append_batch.hip): k ≤ APPEND_BATCH_MAX new points in one step, kp = k padded to 16 ----------------
+constexpr int APPEND_BATCH_MAX = 64;
+// rows of Xraw / Xs / ybuf / delta for the k new points Xb [k][d], yb [k] (device); *info = 0
+hipError_t launch_append_batch_points(const double* Xb, const double* yb, int k, int d, int dp, double s, double mean_c, double* Xraw_rows,
+                                      double* Xs_rows, double* y_at, double* delta_at, int64_t* info, hipStream_t st);
+// Kb [N + k][kp]: rows j < N = k(x_j, new point i), rows N + jj = the new points among themselves (bitwise symmetric, σ_f² on the
+// diagonal), zero in columns ≥ k.  Xs_new [k][dp] scaled, Xraw [N + k][d]; launch_cand_newcol's arithmetic.
+hipError_t launch_append_batch_newcols(const double* Xs_new, const double* Xraw, double* Kb, int N, int k, int d, int dp, int family,
+                                       double s, double sigma_f2, hipStream_t st);
+// out [N][kp] = tri(Wm)·V on the fp64 matrix pipe, V [N][kp]; lower as launch_trmv; only rows and columns < N of Wm are used.
+// part: tri_skinny_part_doubles(N, kp) doubles of scratch.  kp a multiple of 16 up to 64, ld a multiple of 4 and ≥ N padded to 16.
+size_t tri_skinny_part_doubles(int N, int kp);
+hipError_t launch_tri_skinny(const double* Wm, int64_t ld, const double* V, double* out, double* part, int N, int kp, int lower,
+                             hipStream_t s);
+// BᵀB and K_bᵀα in append_batch_gram_blocks(N) ordered partial sums (gpart: that many × (kp² + kp) doubles), then the k × k part in one
+// workgroup: sm = {L_s [kp][kp], L_s⁻¹ [kp][kp], β [kp]}, scal = {2·Σ log diag L_s, ‖L_s⁻¹r‖²}; a non-positive pivot j sets
+// *info = N + j + 1 (if it was 0) and writes nothing else.  Kb as launch_append_batch_newcols leaves it, delta_b: the k centred targets.
+int append_batch_gram_blocks(int N);
+hipError_t launch_append_batch_small(const double* Bm, const double* Kb, const double* alpha, const double* delta_b, int N, int k,
+                                     double noise, double* gpart, double* sm, double* scal, int64_t* info, hipStream_t s);
+// rows N … N+k−1 of L and W, the matching columns of WT, α' (zero from N + k to cap); nothing when *info ≠ 0
+struct AppendBatchArgs {
+    double* L; double* W; double* WT;
+    int64_t ld;
+    const double* B; const double* C;        // [N][kp]: W·K_b and Wᵀ·B
+    const double* sm;                        // launch_append_batch_small's
+    const double* alpha_old; double* alpha_new;
+    int64_t N, cap;
+    int k, kp;
+    const int64_t* info;
+};
+hipError_t launch_append_batch_write(const AppendBatchArgs& a, hipStream_t s);
+
 // ---- posterior epilogue + selection (misc.hip) ----------------------------------------------
 struct FinalizeArgs {
     const double* partial;   // [T][ldp]

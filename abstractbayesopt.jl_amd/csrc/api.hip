@@ -947,6 +947,108 @@ int32_t remove_one_impl(abo_gp* g, abo_gp* n, int64_t j, const int64_t* idx_d) {
     return ABO_OK;
 }
 
+// Blocked bordered update (append_batch.hip): view `g` (N points) → new view `n` (N + k points, 1 ≤ k ≤ 64) sharing g's
+// storage, in one step.  Xd / yd: the k points and targets on the DEVICE, followed by the rest − k that the caller will append next:
+// when the rows cannot be claimed (capacity used up, or another view appended past g) all `rest` are gathered behind g's data and
+// refitted, as append_impl falls back (*refitted = true).  One host read-back: info and the two scalars.
+int32_t append_batch_step(abo_gp* g, abo_gp* n, const double* Xd, const double* yd, int k, int64_t rest, int64_t* info, bool* refitted) {
+    Storage* st = g->st;
+    const int d = g->d;
+    const int64_t N = g->N;
+    hipStream_t s = n->stream;
+    *refitted = false;
+    // (all `rest` points must fit, not this step's alone: a batch of several steps that will not fit goes straight to the refit)
+    if (N + rest > st->cap || !st->claim_rows(N, N + k)) {
+        const int64_t Nn = N + rest;
+        ScratchBuf xs(g->prm.device, s), ys(g->prm.device, s);
+        HIPCHK(xs.b.ensure(sizeof(double) * Nn * d));
+        HIPCHK(ys.b.ensure(sizeof(double) * Nn));
+        HIPCHK(hipMemcpyAsync(xs.b.p, st->Xraw.p, sizeof(double) * N * d, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(ys.b.p, st->ybuf.p, sizeof(double) * N, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(xs.b.as<double>() + N * d, Xd, sizeof(double) * rest * d, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(ys.b.as<double>() + N, yd, sizeof(double) * rest, hipMemcpyDeviceToDevice, s));
+        HIPCHK(wait_stream(s));
+        if (n->prm.n_max < 2 * Nn) n->prm.n_max = 2 * Nn;
+        *refitted = true;
+        return fit_impl(n, xs.b.as<double>(), Nn, d, ys.b.as<double>(), ABO_DEVICE, info);
+    }
+    // rows [N, N + k) are claimed: every failure below gives them back
+    struct Claim { Storage* st; int64_t n; bool keep = false; ~Claim() { if (!keep) st->drop_view(n); } } claim{st, N + k};
+    const int64_t ld = st->cap;
+    const int kp = (int)pad_up(k, 16);
+    const int64_t Npk = pad_up(N + k, TB);
+    const int G = append_batch_gram_blocks((int)N);
+    HIPCHK(n->alpha.ensure(sizeof(double) * ld));
+    HIPCHK(n->info.ensure(sizeof(int64_t)));
+    HIPCHK(n->scal.ensure(sizeof(double) * 8));
+    // scratch of the step: K_b with K_bb behind it, B, C, the slice sums of a block product, the Gram sums, {L_s, L_s⁻¹, β} — about
+    // 11·N·kp doubles, 8 of the 11 being the slice sums: 92 MB at N = 16384, k = 64 (5.8 MB at N = 8192, k = 8); from the pool, back
+    // to it when the step returns
+    const size_t nkb = (size_t)(N + kp) * kp, nb = (size_t)N * kp, npart = tri_skinny_part_doubles((int)N, kp);
+    const size_t ngram = (size_t)G * (kp * kp + kp), nsm = (size_t)2 * kp * kp + kp;
+    ScratchBuf work(g->prm.device, s);
+    HIPCHK(work.b.ensure(sizeof(double) * (nkb + 2 * nb + npart + ngram + nsm)));
+    double* Kb = work.b.as<double>();
+    double* Bm = Kb + nkb;
+    double* Cm = Bm + nb;
+    double* part = Cm + nb;
+    double* gpart = part + npart;
+    double* sm = gpart + ngram;
+    double* Xraw = st->Xraw.as<double>();
+    const double sc_ell = 1.0 / g->prm.ell;
+    HIPCHK(launch_append_batch_points(Xd, yd, k, d, st->dp, sc_ell, g->prm.mean_c, Xraw + N * d, st->Xs.as<double>() + N * st->dp,
+                                      st->ybuf.as<double>() + N, st->delta.as<double>() + N, n->info.as<int64_t>(), s));
+    HIPCHK(launch_append_batch_newcols(st->Xs.as<double>() + N * st->dp, Xraw, Kb, (int)N, k, d, st->dp, g->prm.family, sc_ell,
+                                       g->prm.sigma_f2, s));
+    // only rows / columns < N of W and WT: anything beyond may be the stale remains of a discarded branch
+    tl_phase_np = Npk;
+    const bool timed = phase_events();
+    // (scratch slots EV_BASE + 0 … 3: begin and end of each block product — the k × k part runs between them)
+    if (timed) { HIPCHK(n->events(EV_BASE + 4)); HIPCHK(hipEventRecord(n->evs()[EV_BASE], s)); }
+    HIPCHK(launch_tri_skinny(st->W.as<double>(), ld, Kb, Bm, part, (int)N, kp, 1, s));
+    if (timed) HIPCHK(hipEventRecord(n->evs()[EV_BASE + 1], s));
+    HIPCHK(launch_append_batch_small(Bm, Kb, g->alpha.as<double>(), st->delta.as<double>() + N, (int)N, k, st->noise_used, gpart, sm,
+                                     n->scal.as<double>(), n->info.as<int64_t>(), s));
+    if (timed) HIPCHK(hipEventRecord(n->evs()[EV_BASE + 2], s));
+    HIPCHK(launch_tri_skinny(st->WT.as<double>(), ld, Bm, Cm, part, (int)N, kp, 0, s));
+    if (timed) HIPCHK(hipEventRecord(n->evs()[EV_BASE + 3], s));
+    AppendBatchArgs wa{};
+    wa.L = st->K.as<double>(); wa.W = st->W.as<double>(); wa.WT = st->WT.as<double>(); wa.ld = ld; wa.B = Bm; wa.C = Cm; wa.sm = sm;
+    wa.alpha_old = g->alpha.as<double>(); wa.alpha_new = n->alpha.as<double>(); wa.N = N; wa.cap = ld; wa.k = k; wa.kp = kp;
+    wa.info = n->info.as<int64_t>();
+    HIPCHK(launch_append_batch_write(wa, s));
+    double sc[2] = {0.0, 0.0};
+    int64_t inf = 0;
+    PinStage pin(n->ctx);                            // the NEW handle's staging block: `g` may be in use by another thread
+    HIPCHK(pin.d2h(sc, n->scal.p, sizeof sc, s));
+    HIPCHK(pin.d2h(&inf, n->info.p, sizeof inf, s));
+    HIPCHK(wait_stream(s));
+    pin.flush();
+    if (inf != 0) {
+        if (info) *info = inf;
+        return fail(ABO_ENOTPD, "PosDefException: matrix is not positive definite; Cholesky factorization failed at %lld",
+                    (long long)inf);
+    }
+    storage_unref(n->st);
+    st->refs.fetch_add(1);
+    n->st = st;
+    claim.keep = true;                               // (registered by claim_rows)
+    n->N = N + k; n->npts = N + k; n->Np = Npk; n->d = d; n->dp = st->dp;
+    // an appended view, but of no ONE-row append: no down-date vector (vext stays unallocated), no appended point — abo_cand_downdate
+    // and abo_paths_append (gp_append_view) refuse a view without them, whatever the set or the paths were last synced with
+    n->from_append = true;
+    n->ap_x.clear();
+    n->ap_serial = g_append_serial.fetch_add(1);
+    n->ap_s2 = 0.0; n->ap_beta = 0.0;
+    // the two block products B = L⁻¹K_b, C = L⁻ᵀB: each streams one triangle of its matrix once (8·N²/2 bytes), whatever k
+    n->tm.append_trmv_ms = timed ? ev_ms(n->evs()[EV_BASE], n->evs()[EV_BASE + 1]) + ev_ms(n->evs()[EV_BASE + 2], n->evs()[EV_BASE + 3]) : 0.0;
+    n->tm.append_trmv_bytes = 8.0 * (double)N * (double)N;
+    n->logdet = g->logdet + sc[0];
+    n->quad = g->quad + sc[1];
+    n->fitted = true;
+    return ABO_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1105,6 +1207,81 @@ int32_t abo_append_grad(abo_gp* g, const double* x, int32_t d, const double* y, 
     rc = append_grad_impl(g, n, x, y, info);
     if (rc) { abo_destroy(n); return rc; }
     *out = n;
+    return ABO_OK;
+}
+
+int32_t abo_append_batch(abo_gp* g, const double* X, int32_t k, int32_t d, const double* y, int32_t space, int64_t* info, abo_gp** out) {
+    if (info) *info = 0;
+    if (!g || !X || !y || !out) return fail(ABO_EINVAL, "abo_append_batch: null argument");
+    if (k < 1) return fail(ABO_EINVAL, "abo_append_batch: k = %d, need at least one point", k);
+    if (space != ABO_HOST && space != ABO_DEVICE) return fail(ABO_EINVAL, "abo_append_batch: unknown memory space %d", space);
+    if (!g->fitted) return fail(ABO_EINVAL, "abo_append_batch: surrogate is not conditioned on data yet (call abo_fit first)");
+    if (g->p_out > 1)
+        return fail(ABO_EINVAL, "abo_append_batch: gradient-enhanced models are not supported (abo_append_grad, one observation at a time)");
+    if (d != g->d) return fail(ABO_EINVAL, "abo_append_batch: point dimension %d, model dimension %d", d, g->d);
+    if (g->N + (int64_t)k > (int64_t)1 << 20) return fail(ABO_EINVAL, "abo_append_batch: N + k = %lld too large", (long long)(g->N + k));
+    tl_phase_np = g->Np;
+    HIPCHK(hipSetDevice(g->prm.device));
+    abo_gp* n = nullptr;
+    int32_t rc = abo_create(&g->prm, &n);
+    if (rc) return rc;
+    n->oz_engine = g->oz_engine; n->oz_nmod = g->oz_nmod;
+    if (k == 1) {                                    // abo_append's own path, bit for bit: the view abo_cand_downdate / abo_paths_append follow
+        std::vector<double> xh(X, X + (space == ABO_HOST ? d : 0));
+        double yh = space == ABO_HOST ? y[0] : 0.0;
+        if (space == ABO_DEVICE) {
+            xh.resize(d);
+            hipError_t e = hipMemcpyAsync(xh.data(), X, sizeof(double) * d, hipMemcpyDeviceToHost, n->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(&yh, y, sizeof(double), hipMemcpyDeviceToHost, n->stream);
+            if (e == hipSuccess) e = wait_stream(n->stream);
+            if (e != hipSuccess) { abo_destroy(n); return fail(ABO_EHIP, "abo_append_batch: reading the point failed: %s", hipGetErrorString(e)); }
+        }
+        rc = append_impl(g, n, xh.data(), yh, info);
+        if (rc) { abo_destroy(n); return rc; }
+        *out = n;
+        return ABO_OK;
+    }
+    // the points on the device (host arrays: staged once for every step; the caller's arrays are free again when the call returns)
+    ScratchBuf stage(g->prm.device, n->stream);
+    const double* Xd = X;
+    const double* yd = y;
+    if (space == ABO_HOST) {
+        hipError_t e = stage.b.ensure(sizeof(double) * (size_t)k * (d + 1));
+        if (e == hipSuccess) e = hipMemcpyAsync(stage.b.p, X, sizeof(double) * (size_t)k * d, hipMemcpyHostToDevice, n->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(stage.b.as<double>() + (size_t)k * d, y, sizeof(double) * (size_t)k, hipMemcpyHostToDevice, n->stream);
+        if (e == hipSuccess) e = wait_stream(n->stream);
+        if (e != hipSuccess) {
+            abo_destroy(n);
+            return fail(e == hipErrorOutOfMemory ? ABO_ENOMEM : ABO_EHIP, "abo_append_batch: staging the points failed: %s", hipGetErrorString(e));
+        }
+        Xd = stage.b.as<double>();
+        yd = Xd + (size_t)k * d;
+    }
+    // successive blocked steps of at most 64 rows; an intermediate view goes back with its handle (its rows with it on failure)
+    abo_gp* cur = g;
+    double trmv_ms = 0.0, trmv_bytes = 0.0;
+    for (int32_t done = 0; done < k;) {
+        if (!n) {
+            rc = abo_create(&g->prm, &n);
+            if (rc) { if (cur != g) abo_destroy(cur); return rc; }
+            n->oz_engine = g->oz_engine; n->oz_nmod = g->oz_nmod;
+        }
+        const int kc = k - done < APPEND_BATCH_MAX ? k - done : APPEND_BATCH_MAX;
+        bool refitted = false;
+        rc = append_batch_step(cur, n, Xd + (size_t)done * d, yd + done, kc, k - done, info, &refitted);
+        if (cur != g) abo_destroy(cur);
+        if (rc) { abo_destroy(n); return rc; }
+        if (refitted) {
+            done = k;
+        } else {
+            done += kc;
+            trmv_ms += n->tm.append_trmv_ms; trmv_bytes += n->tm.append_trmv_bytes;
+            n->tm.append_trmv_ms = trmv_ms; n->tm.append_trmv_bytes = trmv_bytes;
+        }
+        cur = n;
+        n = nullptr;
+    }
+    *out = cur;
     return ABO_OK;
 }
 

@@ -170,6 +170,12 @@ int32_t abo_cand_downdate(abo_gp* g, abo_cand* c) {
     if (!g->from_append || g->st->gen != c->synced_gen || g->N != c->synced_N + P)
         return fail(ABO_EINVAL, "abo_cand_downdate: the model is not the one-point append of the model this candidate set "
                                 "was last evaluated with (call abo_cand_refresh)");
+    // a view that abo_append_batch made in a blocked step is an appended view WITHOUT a down-date vector (and without the one appended
+    // point): whatever the set was last synced with — a view of N − 1 rows on the same storage that has since been destroyed passes
+    // the test above — there is no rank-one column to apply
+    if (!g->vext.p || (P == 1 && (int)g->ap_x.size() != g->d))
+        return fail(ABO_EINVAL, "abo_cand_downdate: the model was made by a blocked batch append (abo_append_batch, k >= 2), which leaves "
+                                "no one-point down-date (call abo_cand_refresh)");
     HIPCHK(hipSetDevice(g->prm.device));
     hipStream_t s = g->stream;
     if (c->M > 0) {

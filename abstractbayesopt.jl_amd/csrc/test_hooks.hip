@@ -695,6 +695,32 @@ int32_t abo_test_trmv(int32_t device, const double* Wm, int64_t ld, const double
     return ABO_OK;
 }
 
+int32_t abo_test_tri_skinny(int32_t device, const double* Wm, int64_t ld, const double* V, double* out, int32_t N, int32_t k, int32_t lower) {
+    if (!Wm || !V || !out) return fail(ABO_EINVAL, "abo_test_tri_skinny: null argument");
+    if (N < 1 || k < 1 || k > APPEND_BATCH_MAX || (ld & 3) || ld < pad_up(N, 16) || (lower != 0 && lower != 1))
+        return fail(ABO_EINVAL, "abo_test_tri_skinny: N >= 1, 1 <= k <= 64, ld a multiple of 4 and >= N rounded up to 16, lower 0 or 1");
+    HIPCHK(hipSetDevice(device));
+    const int kp = (int)pad_up(k, 16);
+    ScratchBuf part(device, nullptr);
+    HIPCHK(part.b.ensure(sizeof(double) * tri_skinny_part_doubles(N, kp)));
+    HIPCHK(launch_tri_skinny(Wm, ld, V, out, part.b.as<double>(), N, kp, lower, nullptr));
+    HIPCHK(wait_stream(nullptr));
+    return ABO_OK;
+}
+
+int32_t abo_test_live_views(abo_gp* gp, int64_t* out, int32_t cap, int32_t* n) {
+    if (!gp || !out || !n || cap < 0) return fail(ABO_EINVAL, "abo_test_live_views: null argument");
+    if (!gp->fitted || !gp->st) return fail(ABO_EINVAL, "abo_test_live_views: surrogate is not conditioned on data yet");
+    std::lock_guard<std::mutex> lk(gp->st->mu);
+    int32_t i = 0;
+    for (const int64_t v : gp->st->live) {
+        if (i < cap) out[i] = v;
+        ++i;
+    }
+    *n = i;
+    return ABO_OK;
+}
+
 int32_t abo_test_nlml_terms(int32_t device, const double* L, int64_t ld, const double* delta, const double* alpha, int32_t N, double* out) {
     if (!L || !delta || !alpha || !out) return fail(ABO_EINVAL, "abo_test_nlml_terms: null argument");
     if (N < 1 || ld < N) return fail(ABO_EINVAL, "abo_test_nlml_terms: N >= 1, ld >= N");

@@ -38,6 +38,73 @@ def append(model: HipStandardGP, x, y) -> HipStandardGP:
     return model._clone(_Handle(hp.value))
 
 
+def batch_points(xs, ys):
+    """the arrays append_points hands to abo_append_batch: k points (an (k, d) array, a vector of d-vectors, or a float64 torch tensor,
+    host or device) and their k targets in the same memory space → (x pointer, k, d, y pointer, space, keepalive).  An empty batch
+    raises ValueError, points and targets that disagree in number DimensionMismatch."""
+    xp, k, d, space, keep_x = as_points(xs)
+    if hasattr(ys, "is_cuda"):
+        import torch
+        if ys.dtype != torch.float64:
+            raise TypeError("torch inputs must be float64")
+        yt = ys.reshape(-1).contiguous()
+        if space == DEVICE:
+            if not yt.is_cuda:
+                yt = yt.to(keep_x.device)
+            torch.cuda.current_stream(yt.device).synchronize()
+            yp, ky, keep_y = yt.data_ptr(), int(yt.shape[0]), yt
+        else:
+            ya = np.ascontiguousarray(yt.cpu().numpy())
+            yp, ky, keep_y = ya.ctypes.data, int(ya.shape[0]), ya
+    else:
+        ya = np.ascontiguousarray(np.asarray(ys, dtype=np.float64).reshape(-1))
+        ky = int(ya.shape[0])
+        if space == DEVICE:
+            import torch
+            keep_y = torch.from_numpy(ya).to(keep_x.device)
+            torch.cuda.current_stream(keep_y.device).synchronize()
+            yp = keep_y.data_ptr()
+        else:
+            yp, keep_y = ya.ctypes.data, ya
+    if k == 0 or ky == 0:
+        raise ValueError("append_points: the batch is empty")
+    if k != ky:
+        raise _lib.DimensionMismatch(f"append_points: {k} points but {ky} targets")
+    return xp, k, d, yp, space, (keep_x, keep_y)
+
+
+def append_points(model: HipStandardGP, xs, ys) -> HipStandardGP:
+    """Condition on k more observations (xs[i], ys[i]) in ONE blocked step of O(k·N²) flops that streams the factor's two triangles
+    once instead of k times (include/abo_hip.h: abo_append_batch) — what a batch loop calls after evaluating the q points of
+    greedy_qei / mc_qei / thompson_batch.  Returns a new model sharing the factor storage; `model` stays valid.  The result's
+    `append_path` says what ran: "appended", or "refit" when the storage had no room or another view had appended past `model`.
+    k = 1 is `append` itself.  Raises PosDefException(N + j + 1) if pivot j of the batch's Schur complement is not positive.
+    Resident candidate sets and sample paths in sync with `model` stay with it for k ≥ 2: on the new model a set needs `refresh`."""
+    if hasattr(model, "devices"):
+        raise TypeError("append_points: a sharded model (HipShardedGP) is not supported: the factor is spread over its devices; "
+                        "use a single-device HipStandardGP")
+    if hasattr(model, "p"):
+        raise TypeError("append_points: a gradient-enhanced model (HipGradientGP) is not supported: an observation is p factor rows; "
+                        "append them one at a time")
+    if not isinstance(model, HipStandardGP):
+        raise TypeError(f"append_points needs a HipStandardGP, not {type(model).__name__}")
+    refuse_ard(model, "append_points")
+    xp, k, d, yp, space, keep = batch_points(xs, ys)
+    h = model._require()
+    n, dm = C.c_int64(), C.c_int32()
+    _lib.check(_lib.lib().abo_get_n(h, C.byref(n), C.byref(dm)))
+    if d != dm.value:
+        raise _lib.DimensionMismatch(f"append_points: points of dimension {d}, model dimension {dm.value}")
+    hp = C.c_void_p()
+    info = C.c_int64(0)
+    _lib.check(_lib.lib().abo_append_batch(h, xp, k, d, yp, space, C.byref(info), C.byref(hp)), info.value)
+    del keep
+    out = model._clone(_Handle(hp.value))
+    # (the refit fallback leaves a freshly fitted handle: no bordered product ran, its byte count reads 0)
+    out.append_path = "appended" if out.timings()["append_trmv_bytes"] > 0 else "refit"
+    return out
+
+
 def remove_indices(idx) -> np.ndarray:
     """the indices remove_points hands to abo_remove: an int or a sequence of ints in any order → sorted int64; a repeated index, a
     non-integer or an empty sequence raises ValueError / TypeError here (the range is the library's check: it knows N)"""

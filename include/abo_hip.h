@@ -49,7 +49,8 @@ extern "C" {
                                   (struct abo_paths_append_stats is new); ABO_ACQ_LOGEI (kind 5 in every entry point that takes a kind
                                   or an abo_acq_term, and in the pruned top-k selection); ABO_ACQ_MES and abo_score_mes, abo_acq_mes,
                                   abo_cand_acq_mes, abo_refine_mes, abo_optimize_acquisition_mes; abo_get_prune_levels; abo_loo, abo_loo_grad;
-                                  abo_predict_cov; abo_remove, ABO_REMOVE_REMOVED / _REFIT; abo_acq_kg, ABO_KG_SELF; abo_predict_deriv */
+                                  abo_predict_cov; abo_remove, ABO_REMOVE_REMOVED / _REFIT; abo_acq_kg, ABO_KG_SELF; abo_predict_deriv;
+                                  abo_append_batch */
 
 /* status codes */
 enum {
@@ -293,6 +294,43 @@ int32_t abo_update(abo_gp* prev, const abo_params* params, const double* mean_c,
  * gradient-enhanced handle, k < 1, N − k < 1, indices unsorted, repeated or out of range. */
 enum { ABO_REMOVE_REMOVED = 0, ABO_REMOVE_REFIT = 1 };
 int32_t abo_remove(abo_gp* gp, const int64_t* idx, int32_t k, int32_t* path, abo_gp** out);
+
+/* The model conditioned on k more observations in ONE blocked bordered step: the inverse of abo_remove, and what a batch loop calls
+ * after it has evaluated the q points of greedy_qei / mc_qei / thompson_batch in parallel.  X: k × d doubles,
+ * row-major; y: k values; both in `space` (ABO_HOST / ABO_DEVICE).  *out is a new view on gp's factor storage, conditioned on gp's
+ * N points followed by the k new ones in the given order; gp and every other view stay valid and keep their bits, as with abo_append.
+ * With W = L⁻¹, K_b = k(X_train, X_b) (N × k), δ_b = y − mean_c:
+ *   B = W·K_b,   S = k(X_b, X_b) + noise_used·I − BᵀB = L_s·L_sᵀ,   C = Wᵀ·B = K⁻¹K_b,
+ *   L' = [[L, 0], [Bᵀ, L_s]],   W' = [[W, 0], [−L_s⁻¹Cᵀ, L_s⁻¹]],   r = δ_b − K_bᵀα,  β = S⁻¹r,  α' = [α − Cβ ; β],
+ *   logdet' = logdet + 2·Σ log diag L_s,   quad' = quad + ‖L_s⁻¹r‖².
+ * The two products stream one triangle of L⁻¹ / L⁻ᵀ each ONCE for all k columns (k sequential abo_append stream them k times and
+ * wait for the host k times), as skinny products on the fp64 matrix pipe; one host read-back per step.
+ *   k = 1        abo_append's own code path: bit for bit its result, a view abo_cand_downdate / abo_paths_append follow.
+ *   2 ≤ k ≤ 64   one blocked step.
+ *   k > 64       successive blocked steps of at most 64 rows; the intermediate views are released.
+ * A non-positive pivot j (0-based within the batch) of S: ABO_ENOTPD with *info = N + j + 1, the order of the failing leading minor
+ * as a refit's potrf reports it; the claimed rows are given back (those of released intermediate views too) and gp stays appendable.
+ * No room in the storage, or another view has appended past gp: the N + k points are gathered on the device and refitted with
+ * capacity max(n_max, 2(N + k)), exactly as abo_append falls back; abo_timings.append_trmv_bytes of the result then reads 0.
+ * The result is an appended view: abo_nlml_grad* refuse it; abo_predict*, abo_acq* under both contraction engines, abo_nlml, abo_loo,
+ * abo_predict_cov, abo_acq_kg, abo_remove, abo_append, abo_append_batch and abo_update (as prev) work on it.  For k ≥ 2 a candidate
+ * set or sample paths in sync with gp stay with gp: abo_cand_downdate / abo_paths_append on the new view return ABO_EINVAL (the set
+ * needs abo_cand_refresh), as after abo_remove.
+ * abo_timings of the new handle: append_trmv_ms = the two block products (phase events on), append_trmv_bytes = 8·N² per blocked
+ * step.  The same call on the same view gives the same bits every time (no floating-point atomics; the inner dimension of a product
+ * is cut into a fixed number of slices that are added in slice order).
+ * ABO_EINVAL, before any device work: a null or unfitted handle, a gradient-enhanced handle, k < 1, d not the model's, a null X or y.
+ * Measured (profiles/append_batch_latency.txt, d = 8, Matérn-5/2, ms, median):
+ *     N = 1024    k = 8: 0.16 (8 sequential abo_append 0.50, refit 0.65)   k = 16: 0.16 (0.99, 0.65)   k = 64: 0.39 (3.88, 0.66)
+ *     N = 8192    k = 4: 0.39 (0.53, 12.0)   k = 16: 0.42 (2.28, 12.2)   k = 32: 0.54 (4.84, 12.4)   k = 64: 0.96 (10.2, 12.3)
+ *     N = 16384   k = 4: 1.03 (1.50, 57.3)   k = 16: 1.06 (6.40, 58.2)   k = 64: 2.03 (27.8, 58.1)
+ * The blocked step is below the sequential appends from k = 4 on and below the refit everywhere in the table (k = 64 at N = 1024:
+ * 0.60 of it).  At k = 2 it is SLOWER than the sequential appends (0.39 against 0.26 ms at N = 8192; 1.04 against 0.76 at 16384),
+ * at k = 3 level with them (0.40 against 0.40 ms at N = 8192; 0.80 and 0.91 of them at N = 1024 and 16384): its two block products
+ * take three times the device time of one append's mat-vec pair (0.26 against 0.087 ms at N = 8192), whatever k up to 16; a caller
+ * with two points may as well call abo_append twice.  No crossover rule is applied.
+ * Scratch of a step, from the pool and back to it on return: about 11·N·kp doubles, kp = k padded to 16 (92 MB at N = 16384, k = 64). */
+int32_t abo_append_batch(abo_gp* gp, const double* X, int32_t k, int32_t d, const double* y, int32_t space, int64_t* info, abo_gp** out);
 
 /* --- posterior ------------------------------------------------------------------------------
  * posterior_mean / posterior_var (src/surrogates/StandardGP.jl:361-363, :377-379), fused as in
@@ -1078,6 +1116,12 @@ int32_t abo_test_chol_blocked(int32_t device, double* K, double* W, double* WT, 
                               int32_t super_rows, int64_t* info);
 /* launch_trmv: out[r] = Σ_k Wm[r][k]·v[k] over the triangle (lower = 1: k ≤ r, 0: r ≤ k < Np), r < Np; ld even */
 int32_t abo_test_trmv(int32_t device, const double* Wm, int64_t ld, const double* v, double* out, int32_t Np, int32_t lower);
+/* launch_tri_skinny (append_batch.hip): out [N][kp] = tri(Wm)·V over the triangle as abo_test_trmv, V [N][kp] and out row-major with
+ * kp = k padded to a multiple of 16 (the caller pads V with zero columns), 1 ≤ k ≤ 64; only rows and columns < N of Wm are read for
+ * the sum; ld a multiple of 4 and ≥ N padded to 16.  Device pointers. */
+int32_t abo_test_tri_skinny(int32_t device, const double* Wm, int64_t ld, const double* V, double* out, int32_t N, int32_t k, int32_t lower);
+/* the sizes (factor rows) of the live views on gp's factor storage, ascending, into out[0 … cap); *n = how many there are */
+int32_t abo_test_live_views(abo_gp* gp, int64_t* out, int32_t cap, int32_t* n);
 /* launch_nlml_terms: out[0] = 2·Σ_{i<N} log L[i][i], out[1] = Σ_{i<N} delta[i]·alpha[i] */
 int32_t abo_test_nlml_terms(int32_t device, const double* L, int64_t ld, const double* delta, const double* alpha, int32_t N, double* out);
 /* launch_append with every field of its argument block (csrc/abo_kernels.h: AppendArgs) */

@@ -607,6 +607,9 @@ include("KnowledgeGradient.jl")
 # a model without some of its observations in O(N²) (abo_remove): remove_points
 include("RemovePoints.jl")
 
+# k more observations in one blocked bordered step (abo_append_batch): append_points
+include("AppendPoints.jl")
+
 # path s takes its best index not taken by paths 1 … s − 1 (idx: k × q orderings, 0 = no candidate)
 function _distinct_picks(idx::AbstractMatrix{Int64})
     picks = Int64[]
